@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the hot path on MI355X: audio-seconds segmented per wall-second.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts N ranks itself (a fresh `python -m torch.distributed.run` child, one process per GPU,
 RCCL) unless it is already running under one (RANK / WORLD_SIZE in the environment, as the driver launches it).
@@ -25,13 +25,16 @@ beams 4, decode length pinned to --gen-tokens with EOS suppressed (random weight
 Windows are independent, so ranks shard them with no data-path collective ("weak" scaling: fixed
 windows per GPU); the only exchange is the all_gather of token ids to every rank.
 
-The timed configuration is CHECKED, not only timed (`check` in the JSON; the bench exits non-zero when it fails):
-every step must produce the same tokens (determinism), and the first-step logits / tokens of a subset of the
-windows are compared with the exact-parity f32 mode of the same kernels on the same weights.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  The timed configuration is CHECKED, not only timed (`check` in the
+JSON; the bench exits non-zero when it fails): every step must produce the same tokens (determinism).
+`--dump-outputs DIR` writes what the last timed step returned (token ids and lengths of every window) as DIR/<name>.npy.
 
-Prints ONE JSON line (rank 0) with the contract keys plus `roofline`, `cpu_baseline`, `check` and `extra`
-(the other SURVEY §8d lines: 128 generated tokens, 10 s / 2.5 s windows, the front-end's HBM rate, a one-hour
-recording through WhisperSegmenter.segment(), in-flight batching under a synthetic length distribution).
+`--full` then runs everything beyond the headline: `check` also compares the first-step logits / tokens of a subset of the
+windows with the exact-parity f32 mode of the same kernels on the same weights; `roofline` (a live-event pass over the dominant
+GEMM), `cpu_baseline`, `extra` (the other SURVEY §8d lines: 128 generated tokens, 10 s / 2.5 s windows, the front-end's HBM rate,
+a one-hour recording through WhisperSegmenter.segment(), in-flight batching under a synthetic length distribution, the other
+modes and BASELINE configurations) and, at world size > 1, `dist_configs`.
 """
 import argparse
 import ctypes as C
@@ -151,11 +154,24 @@ def end_to_end_bound(model, dtype, beams, gen, W, enc_frac=1.0, dec_frac=1.0, cr
             "mfma_issue_multiplier": mult}
 
 
-def synth_pcm(n_windows, win_len, sr, seed):
+def synth_pcm(n_windows, win_len, sr, seed, chunk=1 << 22):
+    """0.1 sin(2 pi 440 t) + 0.01 N(0, 1), float32.  Built chunk by chunk on the host threads: the noise is drawn in order from the
+    one seeded generator (consecutive draws continue its stream) and everything else is elementwise, so the samples are
+    bit-identical to a single-pass evaluation of the formula — only the 1024-window default (2 GB) takes seconds instead of ~20."""
+    from concurrent.futures import ThreadPoolExecutor
     rng = np.random.default_rng(seed)
     n = n_windows * win_len
-    t = np.arange(n, dtype=np.float64) / sr
-    return (0.1 * np.sin(2 * np.pi * 440 * t) + 0.01 * rng.standard_normal(n)).astype(np.float32)
+    out = np.empty(n, dtype=np.float32)
+
+    def fill(lo, noise):
+        t = np.arange(lo, lo + len(noise), dtype=np.float64) / sr
+        out[lo:lo + len(noise)] = (0.1 * np.sin(2 * np.pi * 440 * t) + 0.01 * noise).astype(np.float32)
+
+    with ThreadPoolExecutor(max_workers=host_threads()) as pool:
+        jobs = [pool.submit(fill, lo, rng.standard_normal(min(chunk, n - lo))) for lo in range(0, n, chunk)]
+        for j in jobs:
+            j.result()
+    return out
 
 
 def host_threads():
@@ -425,6 +441,13 @@ def main(argv=None, backend=make_backend):
                          "the seven parity sweeps; bf16x3: the same with bfloat16 pairs (6 198); f16m6: hi*hi on the half matrix cores "
                          "and both cross terms on the fp6 MX matrix cores — 27 %% faster and outside the tolerance on 10 of 6 000 held-out "
                          "recordings; bf16 / f16: plain 16-bit modes (outside it on 9 %% / 1.5 %%); f32: exact-parity mode")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything beyond it: the exact-mode self-check, the live roofline pass of the "
+                         "dominant GEMM, the supplementary lines (extra), the CPU baselines and, at world size > 1, configs[3] / "
+                         "configs[4] (dist_configs); the --no-* options below switch single parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (token ids and lengths of every window, as float32) to "
+                         "DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-windows", type=int, default=4, help="windows of the CPU baseline sample (4 x 30 s: ~25 s of CPU work for the HF model and the port together)")
     ap.add_argument("--check-windows", type=int, default=4, help="windows re-decoded in f32 mode for the self-check")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -438,6 +461,8 @@ def main(argv=None, backend=make_backend):
     ap.add_argument("--device", default="cuda", help=argparse.SUPPRESS)      # tests drive the distributed logic on "cpu" with a stub backend
     ap.add_argument("--check-on-cpu", action="store_true", help=argparse.SUPPRESS)   # ... including the self-check branch
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     in_torchrun = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not in_torchrun:
@@ -452,7 +477,15 @@ def main(argv=None, backend=make_backend):
     device = torch.device("cuda", local_rank) if on_gpu else torch.device("cpu")
     if on_gpu:
         torch.cuda.set_device(device)
-    made = backend(args, device)
+    sr, sts = args.sr, args.spec_time_step
+    win_len = int(1000 * sts * sr)
+    W = args.windows
+    slots = args.slots or min(W, 1024)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=1) as pcm_pool:      # the host-side PCM is built while the engine is set up
+        pcm_job = pcm_pool.submit(synth_pcm, W, win_len, sr, rank)
+        made = backend(args, device)
+        pcm_host = pcm_job.result()
     lib, eng, make_extractor = made[:3]
     segmenter_of = made[3] if len(made) > 3 else (lambda: make_segmenter(args, eng))      # (the CPU tests hand in a stand-in)
     distributed = world > 1 or torch.distributed.is_initialized()
@@ -461,14 +494,11 @@ def main(argv=None, backend=make_backend):
         if on_gpu:
             torch.cuda.synchronize()
 
-    sr, sts = args.sr, args.spec_time_step
-    win_len = int(1000 * sts * sr)
-    W = args.windows
-    slots = args.slots or min(W, 1024)
     if distributed:   # one copy of the weights is authoritative: broadcast rank 0's over RCCL/xGMI
         wdist.broadcast_weights(eng.weights, src=0)
     extractor = make_extractor(sr, sts)
-    pcm = torch.from_numpy(synth_pcm(W, win_len, sr, seed=rank)).to(device)          # resident in HBM
+    pcm = torch.from_numpy(pcm_host).to(device)          # resident in HBM
+    del pcm_host
     starts = (torch.arange(W, dtype=torch.int64) * win_len).to(device)
     codebook = {str(i): i for i in range(10)}
 
@@ -512,13 +542,17 @@ def main(argv=None, backend=make_backend):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        hashes.add(digest(*step()[:2]))
+        last = step()[:2]
+        hashes.add(digest(*last))
     barrier()
     dt = time.perf_counter() - t0
     if distributed:
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *last)
 
     audio_seconds = args.steps * W * world * 1000 * sts
     value = audio_seconds / dt
@@ -540,7 +574,7 @@ def main(argv=None, backend=make_backend):
     # BASELINE configs[3] / configs[4] as written, through the product's own multi-GPU entry points: on every rank (collective), after the
     # headline is timed.  (WSEG_FORCE_DIST=1 initialises the group at world size 1 too: the GPU box's single-rank first contact.)
     dist_cfg = None
-    if distributed and not args.no_dist_configs:
+    if args.full and distributed and not args.no_dist_configs:
         try:
             dist_cfg = dist_configs(args, segmenter_of(), rank, world, device)
         except Exception as exc:
@@ -550,7 +584,7 @@ def main(argv=None, backend=make_backend):
         eng.release_workspace() if hasattr(eng, "release_workspace") else None
 
     roofline = None
-    if on_gpu and not args.no_roofline and args.dtype != "f32":
+    if args.full and on_gpu and not args.no_roofline and args.dtype != "f32":
         roofline = roofline_leg(args, lib, step, W, world, windows_per_s, enc_f + ckv_f + dec_f)
     # what end_to_end_frac can reach: every kernel at its own roof, and with the dominant GEMM at its MEASURED
     # fraction of the matrix pipe + cross-attention at its measured 6.4 TB/s (profiles/README.md)
@@ -561,16 +595,18 @@ def main(argv=None, backend=make_backend):
 
     check = None
     if (on_gpu or args.check_on_cpu) and rank == 0 and not args.no_check:
-        check = self_check(args, eng, step, main_in, hashes, W)      # collective-free: the other ranks wait at the final barrier
+        # collective-free: the other ranks wait at the final barrier.  A plain run checks determinism only (the digests of the
+        # steps it ran anyway); --full adds the re-decode in the exact mode
+        check = self_check(args, eng, step, main_in, hashes, W, against_f32=args.full)
     extra = None
-    if on_gpu and rank == 0 and world == 1 and not args.no_extra and args.model == "large":
+    if args.full and on_gpu and rank == 0 and world == 1 and not args.no_extra and args.model == "large":
         try:      # supplementary lines must never cost the contract line
             extra = extra_lines(args, eng, step, main_in, make_extractor, device, W, slots)
         except Exception as exc:
             extra = {"error": f"{type(exc).__name__}: {exc}"[:500]}
             torch.cuda.synchronize()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args, sr, sts, win_len)
         except Exception as exc:
@@ -621,6 +657,7 @@ def main(argv=None, backend=make_backend):
                                         "note": "ceiling of end_to_end_frac for this workload: dependent kernels, times add; matrix-core "
                                                 "kernels at the dense peak (x3 modes issue 3 MFMAs per algorithmic product), HBM-bound "
                                                 "kernels (cross- / self-attention, logits, decoder weight stream) at 8 TB/s"},
+            "full": args.full, "outputs": dumped,
             "roofline": roofline, "cpu_baseline": cpu, "check": check,
             # the r01 / r02 headline workload (256 windows through 256 slots) in the SAME mode, as a second top-level value
             "step_256_windows": (extra or {}).get("step_256_windows"),
@@ -696,18 +733,30 @@ def roofline_leg(args, lib, step, W, world, windows_per_s, flops_window):
     return out
 
 
-def self_check(args, eng, step, main_in, hashes, W):
+def dump_outputs(path, toks, lens):
+    """What the timed path returned in its last step, for output-for-output comparison of two builds on the same arguments
+    (the inputs are seeded): tokens.npy [windows, max_length] and lengths.npy [windows], float32 (token ids < 2^24 are exact)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"tokens": np.asarray(toks, dtype=np.float32), "lengths": np.asarray(lens, dtype=np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
+def self_check(args, eng, step, main_in, hashes, W, against_f32=True):
     """The timed configuration must be right, not only fast.
     (1) determinism: every warm-up / timed step saw the same input, so all token digests must be equal;
-    (2) the same kernels in exact-parity f32 mode (GEMMs on the fp32 matrix cores = k-ordered fmaf chains) on the SAME weight values decode a subset
+    (2) (against_f32, i.e. --full) the same kernels in exact-parity f32 mode (GEMMs on the fp32 matrix cores = k-ordered fmaf chains) on the SAME weight values decode a subset
         of the windows alone: first-step logits must agree (cosine >= 0.999 per row, max |diff| <= 10 % of the logit
         scale — the bf16 tolerance of tests/test_model_gpu.py), beams of a window must be identical at the first step;
         token agreement is reported (random weights give nearly flat logits, so bf16 rounding may legitimately flip an
         argmax; real checkpoints are covered by the golden tests)."""
     n = max(1, min(args.check_windows, W))
-    out = {"deterministic": len(hashes) == 1, "tokens_sha256": sorted(hashes)[0][:16], "subset_windows": n}
+    out = {"deterministic": len(hashes) == 1, "tokens_sha256": sorted(hashes)[0][:16]}
     ok = out["deterministic"]
-    if args.dtype != "f32":
+    if against_f32:
+        out["subset_windows"] = n
+    if against_f32 and args.dtype != "f32":
         toks, lens, logits = step(want_logits=True, gather=False)
         nb = args.beams
         got = logits[: n * nb].float().cpu()

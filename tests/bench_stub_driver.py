@@ -17,12 +17,15 @@ class StubExtractor:
 
 
 class StubEngine:
+    calls = 0      # generate() calls of this process (reported on stderr at exit: what a run decodes beyond its steps)
+
     def __init__(self, device):
         rank = int(os.environ.get("RANK", "0"))
         self.device = device
         self.weights = {"w": torch.full((4,), float(100 + rank))}     # differs per rank until rank 0's is broadcast
 
     def generate(self, feats, prompt, eos, pad, max_length=8, num_beams=4, return_first_logits=False, **kw):
+        StubEngine.calls += 1
         n = feats.shape[0]
         toks = torch.full((n, max_length), pad, dtype=torch.int32)
         toks[:, :3] = torch.tensor(prompt, dtype=torch.int32)
@@ -55,4 +58,7 @@ def backend(args, device):
 
 
 if __name__ == "__main__":
-    bench.main(backend=backend)
+    try:
+        bench.main(backend=backend)
+    finally:
+        print("stub generate calls: %d" % StubEngine.calls, file=sys.stderr, flush=True)

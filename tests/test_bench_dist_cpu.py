@@ -6,13 +6,15 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
 
 DRIVER = os.path.join(ROOT, "tests", "bench_stub_driver.py")
-ARGS = ["--device", "cpu", "--steps", "2", "--warmup", "1", "--windows", "5", "--model", "tiny", "--gen-tokens", "5",
-        "--sr", "16000", "--spec-time-step", "0.001", "--no-cpu-baseline", "--dist3-windows", "20", "--dist4-windows", "24"]
+BASE_ARGS = ["--device", "cpu", "--steps", "2", "--warmup", "1", "--windows", "5", "--model", "tiny", "--gen-tokens", "5",
+             "--sr", "16000", "--spec-time-step", "0.001"]
+ARGS = BASE_ARGS + ["--full", "--no-cpu-baseline", "--dist3-windows", "20", "--dist4-windows", "24"]
 
 
 def check_dist_configs(out, world):
@@ -102,3 +104,54 @@ def test_self_check_runs_on_rank_0_without_a_collective():
     chk = out["check"]
     assert chk is not None and chk["ok"] and chk["deterministic"] and chk["subset_windows"] == 3
     assert chk["beams_equal_at_first_step"] and chk["first_token_equal_to_f32"] == "3/3"
+
+
+def generate_calls(stderr):
+    return [int(ln.split(":")[1]) for ln in stderr.splitlines() if ln.startswith("stub generate calls:")]
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without --full the bench sets up, warms up, times --steps steps and prints the contract line: the engine decodes exactly
+    warmup + steps times, and no exact-mode comparison, supplementary line, CPU baseline or configs[3] / [4] runs."""
+    for steps in (2, 5):
+        args = BASE_ARGS + ["--steps", str(steps), "--check-on-cpu", "--check-windows", "3"]
+        res = subprocess.run([sys.executable, DRIVER] + args, env=clean_env(), capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = last_json(res.stdout)
+        assert generate_calls(res.stderr) == [1 + steps]
+        assert out["steps"] == steps and out["warmup"] == 1 and out["full"] is False
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["unit"] == "audio-sec/s" and out["higher_is_better"] is True and out["dtype"] == "f16x3"
+        assert out["value"] == pytest.approx(steps * 5 * 1.0 / (out["ms_per_step"] * steps / 1e3), rel=1e-6)
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["extra"] is None and out["dist_configs"] is None
+        assert out["check"]["ok"] and out["check"]["deterministic"] and "subset_windows" not in out["check"]
+    res = subprocess.run([sys.executable, DRIVER, "--gpus", "2"] + BASE_ARGS, env=clean_env(), capture_output=True, text=True, timeout=280)
+    assert res.returncode == 0, res.stderr[-3000:]
+    out = last_json(res.stdout)
+    assert out["world_size"] == 2 and out["dist_configs"] is None and out["extra"] is None
+    res = subprocess.run([sys.executable, DRIVER] + BASE_ARGS + ["--steps", "0"], env=clean_env(), capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode == 2 and "--steps" in res.stderr
+
+
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: the token ids and lengths the last timed step returned (all ranks' windows, gathered), float32 .npy,
+    identical from run to run with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        res = subprocess.run([sys.executable, DRIVER, "--gpus", "2"] + BASE_ARGS + ["--dump-outputs", str(d)], env=clean_env(),
+                             capture_output=True, text=True, timeout=280)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = last_json(res.stdout)
+        assert out["outputs"]["arrays"] == {"tokens": [10, 8], "lengths": [10]}
+        assert sorted(os.listdir(d)) == ["lengths.npy", "tokens.npy"]
+        toks, lens = np.load(d / "tokens.npy"), np.load(d / "lengths.npy")
+        assert toks.dtype == np.float32 and lens.dtype == np.float32
+        assert (toks[:, :3] == [50258, 50259, 50363]).all() and (toks[:, 4] == 15).all() and (lens == 6).all()
+        dumps.append((toks, lens))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+    assert not np.array_equal(dumps[0][0][:5], dumps[0][0][5:])      # each rank's own windows (PCM seeded by rank)
