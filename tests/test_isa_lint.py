@@ -30,7 +30,6 @@ ALLOW_SCRATCH = {
 # kernel regex -> VGPR ceiling (waves per SIMD the launch geometry counts on: MI355X_MICROARCH.md register-file table)
 VGPR_CAPS = {
     r"gemm_h16_pp_kernel<": 256,                                   # 8 waves of 512 threads: 2 per SIMD
-    r"gemm_w4_kernel<": 512,                                       # 4 waves: 1 per SIMD, accumulators in the AGPR half
     r"gemm_h16_persist_kernel<.*128, 128": 256,                    # 2 workgroups of 4 waves per CU: 2 waves per SIMD
     r"enc_attention_h16_kernel<.*true>": 168,                      # 3 workgroups per CU
     r"enc_attention_h16_kernel<.*false>": 128,                     # 4 workgroups per CU
@@ -92,7 +91,7 @@ def test_register_counts_under_their_occupancy_steps(digests):
             if re.search(pat, k["demangled"]):
                 seen.add(pat)
                 assert k["vgpr"] <= cap, (k["demangled"], k["vgpr"], k["agpr"], cap)      # (.vgpr_count is the unified total: it includes the AGPRs)
-    assert len(seen) >= len(VGPR_CAPS) - 1, sorted(set(VGPR_CAPS) - seen)      # (gemm_w4_kernel may not exist in every build)
+    assert len(seen) == len(VGPR_CAPS), sorted(set(VGPR_CAPS) - seen)
 
 
 def test_no_hazard_around_inline_asm_mfmas(digests):

@@ -1,4 +1,4 @@
-# warm vs cold weights, split targets; per-kernel durations from rocprofv3.  usage: bash tools/dec_gemm_sweep2.sh <out-dir>
+# warm vs cold weights; per-kernel durations from rocprofv3.  usage: bash tools/dec_gemm_sweep2.sh <out-dir>
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; mkdir -p $OUT
 run() {  # name rotate shapes env...
@@ -15,9 +15,3 @@ run a_warm 1 "$A"
 run a_cold 128 "$A"
 run b_warm 1 "$B"
 run b_cold 64 "$B"
-run a_cold_t160 128 "$A" WSEG_SKINNY_TARGET=160
-run a_cold_t512 128 "$A" WSEG_SKINNY_TARGET=512
-run a_warm_t160 1 "$A" WSEG_SKINNY_TARGET=160
-run a_warm_t512 1 "$A" WSEG_SKINNY_TARGET=512
-run a_cold_bm64 128 "$A" WSEG_SKINNY_BM=64
-run a_warm_bm64 1 "$A" WSEG_SKINNY_BM=64

@@ -5,7 +5,7 @@ tiny_model3) over the windows of a few sweep recordings (needs the GPU):
 
 On seeded random weights (tools/logit_error.py) the cross-attention is diffuse and the storage format of its K / V rows does not show;
 on a trained model single encoder positions carry the probability, and it does: this is the measurement behind the x3 modes' 24-bit
-block-floating-point rows (r06; knobs builds select the other formats: WSEG_X3_CKV=k24 | f32 | bfp with WSEG_LIB=.../libwseg_knobs.so).
+block-floating-point rows (r06).
 Prints one JSON line per (model, mode): max / mean |logit diff| over all windows, the logit scale, argmax agreement."""
 import argparse
 import json

@@ -7,22 +7,9 @@
 #include <stdlib.h>
 #include "../../include/wseg.h"
 
-// Experiment knobs.  The PRODUCT library reads no tuning environment variable: the macros below fold to their defaults.  An A/B
-// build keeps them live:  python -m whisperseg_amd.build --variant knobs -DWSEG_KNOBS=1  (tools/ab_variant.sh).  What the product
-// does read are the TEST knobs that select an alternative kernel computing the same bits (WSEG_F32_GEMM, WSEG_F32_ATTN,
-// WSEG_CROSS_NO_PK, WSEG_LOGMEL_GENERIC, WSEG_NO_GRAPH: tests compare both sides on the shipped library).
-#ifdef WSEG_KNOBS
-#define WSEG_KNOB_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#define WSEG_KNOB_SET(name) (getenv(name) != nullptr)
-#define WSEG_KNOB_IS(name, val) (getenv(name) && !strcmp(getenv(name), val))
-#else
-// (a tool that sets one of these variables against the product library would silently measure the default and label it an ablation:
-// the library says so once per variable on stderr — ADVICE r05)
-namespace wseg { bool knob_compiled_out(const char* name); }      // always false
-#define WSEG_KNOB_INT(name, dflt) (::wseg::knob_compiled_out(name) ? (dflt) : (dflt))
-#define WSEG_KNOB_SET(name) (::wseg::knob_compiled_out(name))
-#define WSEG_KNOB_IS(name, val) (::wseg::knob_compiled_out(name))
-#endif
+// The library reads no tuning environment variable.  What it does read are the TEST knobs that select an alternative path
+// computing the same bits (WSEG_F32_GEMM, WSEG_F32_ATTN, WSEG_CROSS_NO_PK, WSEG_NO_GRAPH, WSEG_NO_PROMPT_PASS,
+// WSEG_NO_FIRST_STEP_MERGE: tests compare both sides).
 
 namespace wseg {
 
@@ -157,8 +144,7 @@ struct f16_t;
 // Q, K, V^T and P as half hi + lo pairs and three MFMAs per product like the GEMMs (first-step logits within 5e-5 of the exact
 // mode at 32 layers; plain half operands: 4e-4, which is what leaves the parity sweep untouched too — tools/precision_study.py
 // "gemm=bf16x3,eattn=f16" 200 / 200 — but would make the attention the mode's largest error by 10x), whereas the decoder's
-// cross-attention K / V must keep >= 16 mantissa bits ("ckv=f16": 188 / 200) and stay fp32.  WSEG_X3_ENC_ATTN=f16 | f32
-// selects plain half / the fp32-MFMA kernel (EpiParams::qkv_mode).
+// cross-attention K / V must keep >= 16 mantissa bits ("ckv=f16": 188 / 200) and stay fp32.
 template <typename T> struct IO { typedef T P; typedef T H; typedef T A; static constexpr bool split = false; };
 template <typename HT> struct IO<X3<HT>> { typedef float P; typedef HT H; typedef f16_t A; static constexpr bool split = true; };
 
@@ -405,17 +391,9 @@ template <typename T> __device__ __forceinline__ float gelu_for(float x) { retur
 template <> __device__ __forceinline__ float gelu_for<float>(float x) { return gelu_erf(x); }
 // eight elements of an 8-column epilogue: pairs through the packed form in the 16-bit / split modes (bit-identical to gelu_for, 4.5 issue
 // slots per element fewer), the exact erff in f32 mode
-#ifndef WSEG_GELU_PACKED
-#define WSEG_GELU_PACKED 1      // A/B: build --variant sgelu -DWSEG_GELU_PACKED=0
-#endif
 template <typename T> __device__ __forceinline__ void gelu8_for(float* v) {
-  if constexpr (WSEG_GELU_PACKED) {
 #pragma unroll
-    for (int e = 0; e < 8; e += 2) { const gelu_f2 y = gelu_erf_fast2((gelu_f2){v[e], v[e + 1]}); v[e] = y[0]; v[e + 1] = y[1]; }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = gelu_erf_fast(v[e]);
-  }
+  for (int e = 0; e < 8; e += 2) { const gelu_f2 y = gelu_erf_fast2((gelu_f2){v[e], v[e + 1]}); v[e] = y[0]; v[e + 1] = y[1]; }
 }
 template <> __device__ __forceinline__ void gelu8_for<float>(float* v) {
 #pragma unroll

@@ -75,7 +75,7 @@ int launch_dec_self_attn(int dtype, const DecodeState& st, const void* q, void* 
 int launch_dec_cross_attn(int dtype, const DecodeState& st, const void* q, const void* ck, const void* cv, void* out,
                           int H, int Tk, int d, const PartialInfo* q_part, const void* q_bias, float scale, hipStream_t s,
                           const int* kv_slot = nullptr);
-// WSEG_F16M6: M6 rows (24-bit K / V kernel, <= 4 beams) or hi | lo rows that the caller converts (5..8 beams)?
+// WSEG_F16M6: M6 rows (block-floating-point K / V kernel, <= 4 beams) or hi | lo rows that the caller converts (5..8 beams)?
 bool dec_cross_attn_writes_mx(int dtype, int nb);
 // log-softmax + suppress + running score -> top-2nb per row (beam) / argmax of the processed logits (greedy)
 // scratch: part_val/part_idx [R][16][16], part_stat [R][16][2]

@@ -692,22 +692,16 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState s
 }
 
 // ------------------------------------------------------------------------------------------------
-// Split-precision modes: cross-attention over 24-bit K / V (EpiParams::kv24: per (slot, head) a [Tk][64] plane of the fp32
-// words' top halves, then a [Tk][64] plane of their third bytes; 192 instead of 256 bytes per row pair of an HBM-bound stream).
-// fp32 query and arithmetic; same structure as the packed 16-bit kernel above: 8 lanes per row, 8 raw rows per lane in flight
-// (16 + 8 bytes each), one v_perm_b32 per element to rebuild the fp32 word, two beams per v_pk_fma_f32, DPP row sums.
-// BFP (r06, EpiParams::kv24 == 3, the x3 modes' format): the same two planes hold 24-bit two's-complement INTEGERS and a third plane of
-// [Tk] fp32 row scales follows (196 bytes per row; st_bfp24_row in wseg_gemm_epi.h): the rebuilt word is 256 q, one v_cvt_f32_i32 per
-// element more, and the row scales are applied where a row is one number — the K scale to the finished score and the V scale to the
-// probability, both in the softmax pass over LDS — so neither streaming loop carries another register.
+// bf16x3 / f16x3: cross-attention over 24-bit block-floating-point K / V (r06, EpiParams::kv24 == 3; st_bfp24_row in wseg_gemm_epi.h):
+// per (slot, head) a [Tk][64] plane of the 24-bit two's-complement integers' top 16 bits, a [Tk][64] plane of their low bytes and
+// [Tk] fp32 row scales (196 bytes per row of an HBM-bound stream).  fp32 query and arithmetic; same structure as the packed 16-bit
+// kernel above: 8 lanes per row, 8 raw rows per lane in flight (16 + 8 bytes each), one v_perm_b32 per element to rebuild the 32-bit
+// word 256 q and one v_cvt_f32_i32 to convert it, two beams per v_pk_fma_f32, DPP row sums.  The row scales are applied where a row
+// is one number — the K scale to the finished score and the V scale to the probability, both in the softmax pass over LDS — so
+// neither streaming loop carries another register.  (Not done: requesting the first K rows in front of the query reduction — the rows
+// live across reduce1 and spill at 128 registers, r06: 8 rows 8-24 VGPRs, 4 rows 4-31.)
 // ------------------------------------------------------------------------------------------------
-#ifndef WSEG_CA_PREFETCH
-#define WSEG_CA_PREFETCH 1      // first V rows requested in front of the softmax pass, row scales parked in LDS (A/B: build --variant nopf -DWSEG_CA_PREFETCH=0)
-#endif
-#ifndef WSEG_CA_PREFETCH_K
-#define WSEG_CA_PREFETCH_K 0    // first K rows in front of the query reduction: rows live across reduce1 spill at 128 registers (r06: 8 rows 8-24 VGPRs, 4 rows 4-31)
-#endif
-template <typename TO, int NB, bool BFP>
+template <typename TO, int NB>
 __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState st, const float* __restrict__ q,
                                                                     const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                     void* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
@@ -727,19 +721,16 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
   const int nb = st.nb;
   const int sub = lane & 7, rowl = lane >> 3;
   const int ws = kv_slot ? kv_slot[w] : w;              // prompt pass: query rows of admitted window w, K / V of its slot
-  constexpr int ROWB = BFP ? 196 : 192;
-  const unsigned char* Kb = ck + ((size_t)ws * H + h) * Tk * ROWB;
-  const unsigned char* Vb = cv + ((size_t)ws * H + h) * Tk * ROWB;
+  const unsigned char* Kb = ck + ((size_t)ws * H + h) * Tk * 196;
+  const unsigned char* Vb = cv + ((size_t)ws * H + h) * Tk * 196;
   const unsigned char* Kl = Kb + (size_t)Tk * 128;
   const unsigned char* Vl = Vb + (size_t)Tk * 128;
-  const float* Ks = (const float*)(Kb + (size_t)Tk * 192);      // BFP: row scales
+  const float* Ks = (const float*)(Kb + (size_t)Tk * 192);      // row scales
   const float* Vs = (const float*)(Vb + (size_t)Tk * 192);
-  // BFP: the row scales wait in LDS for the softmax pass (read from global there, each wave's first access paid an HBM round trip with no
+  // the row scales wait in LDS for the softmax pass (read from global there, each wave's first access paid an HBM round trip with no
   // stream in flight); visible behind the barrier that closes the score pass
-  __shared__ float sks[BFP && WSEG_CA_PREFETCH ? 512 : 1], svs[BFP && WSEG_CA_PREFETCH ? 512 : 1];
-  if constexpr (BFP && WSEG_CA_PREFETCH) {
-    for (int t = tid; t < Tk; t += 256) { sks[t] = Ks[t]; svs[t] = Vs[t]; }
-  }
+  __shared__ float sks[512], svs[512];
+  for (int t = tid; t < Tk; t += 256) { sks[t] = Ks[t]; svs[t] = Vs[t]; }
   constexpr int NP = (NB + 1) / 2;
   f2 qq[8][NP];
   __shared__ float sq[NB][64];                          // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS
@@ -753,7 +744,6 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
       kl[u] = __builtin_nontemporal_load((const raw8*)(Kl + (size_t)t * 64 + sub * 8));
     }
   };
-  if constexpr (WSEG_CA_PREFETCH_K) load_k(0);          // the stream starts under the query's split-K reduction
   if (pi.part != nullptr) {
     if (tid < NB * 64) sq[tid >> 6][tid & 63] = reduce1<float>(pi, w * nb + min(tid >> 6, nb - 1), h * 64 + (tid & 63), q_bias) * scale;
     __syncthreads();
@@ -777,19 +767,19 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
       for (int e = 0; e < 8; ++e) qq[e][0][1] = 0.f;
     }
   }
-  // element e of a row slice: 32-bit word = [top half e][third byte e][0] — an fp32, or (BFP) the integer 256 q
+  // element e of a row slice: 32-bit word = [top half e][low byte e][0] = the integer 256 q
   auto unpack = [](const raw16& hi, const raw8& lo, float v[8]) {
 #pragma unroll
     for (int e2 = 0; e2 < 4; ++e2) {
       const unsigned hw = hi[e2], lw = lo[e2 >> 1];
       const unsigned s0 = (e2 & 1) ? 0x0504020cu : 0x0504000cu, s1 = (e2 & 1) ? 0x0706030cu : 0x0706010cu;
       const unsigned w0 = __builtin_amdgcn_perm(hw, lw, s0), w1 = __builtin_amdgcn_perm(hw, lw, s1);
-      v[2 * e2] = BFP ? (float)(int)w0 : __uint_as_float(w0);
-      v[2 * e2 + 1] = BFP ? (float)(int)w1 : __uint_as_float(w1);
+      v[2 * e2] = (float)(int)w0;
+      v[2 * e2 + 1] = (float)(int)w1;
     }
   };
   for (int t0 = 0; t0 < Tk; t0 += 32 * U) {
-    if (!WSEG_CA_PREFETCH_K || t0 > 0) load_k(t0);
+    load_k(t0);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * 32 + wave * 8 + rowl;
@@ -832,19 +822,15 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
       vl[u] = __builtin_nontemporal_load((const raw8*)(Vl + (size_t)t * 64 + sub * 8));
     }
   };
-  if constexpr (WSEG_CA_PREFETCH) load_v(0);
+  load_v(0);
   __syncthreads();
   WSEG_STAMP(3, 4);
   for (int j = wave; j < nb; j += 4) {
     float mx = -3.0e38f;
-    if constexpr (BFP) {
-      for (int t = lane; t < Tk; t += 64) { const float x = sc[t][j] * (WSEG_CA_PREFETCH ? sks[t] : Ks[t]); sc[t][j] = x; mx = fmaxf(mx, x); }
-    } else {
-      for (int t = lane; t < Tk; t += 64) mx = fmaxf(mx, sc[t][j]);
-    }
+    for (int t = lane; t < Tk; t += 64) { const float x = sc[t][j] * sks[t]; sc[t][j] = x; mx = fmaxf(mx, x); }
     mx = wave_max(mx);
     float sum = 0.f;
-    for (int t = lane; t < Tk; t += 64) { const float p = expf(sc[t][j] - mx); sc[t][j] = BFP ? p * (WSEG_CA_PREFETCH ? svs[t] : Vs[t]) : p; sum += p; }
+    for (int t = lane; t < Tk; t += 64) { const float p = expf(sc[t][j] - mx); sc[t][j] = p * svs[t]; sum += p; }
     sum = wave_sum(sum);
     if (lane == 0) sinv[j] = 1.0f / sum;
   }
@@ -857,7 +843,7 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[j][e] = (f2){0.f, 0.f};
   for (int t0 = 0; t0 < Tk; t0 += 32 * U) {
-    if (!WSEG_CA_PREFETCH || t0 > 0) load_v(t0);
+    if (t0 > 0) load_v(t0);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * 32 + wave * 8 + rowl;
@@ -902,30 +888,21 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 
 // ------------------------------------------------------------------------------------------------
 // Split-precision modes, r05: cross-attention over block-floating-point K / V (EpiParams::kv24 == 2: per (slot, head) a [Tk][64] plane
-// of int16 followed by [Tk] fp32 powers of two, value = int16 * scale of its row; 132 instead of the 24-bit format's 192 bytes per
-// row of an HBM-bound stream).  The structure is the 24-bit kernel's: 8 lanes per row, 8 raw rows per lane in flight (16 + 4 bytes
+// of int16 followed by [Tk] fp32 powers of two, value = int16 * scale of its row; 132 bytes per row of an HBM-bound stream).  The
+// structure is the 24-bit kernel's (dec_cross_attn_k24_kernel): 8 lanes per row, 8 raw rows per lane in flight (16 + 4 bytes
 // each), two beams per v_pk_fma_f32, DPP row sums; an element is one v_cvt_f32_i32 (sign-extended half word), the row's scale
 // multiplies the finished score (K) / the probability (V) — powers of two: exact, the sums are those of the dequantised values.
 // ------------------------------------------------------------------------------------------------
-#ifndef WSEG_BFP_U
-#define WSEG_BFP_U 8
-#endif
 // Occupancy: four workgroups per CU (128 registers).  The 4-beam instantiation fits with 5 instead of 8 V rows per lane in flight and the
 // scores as [position][beam] (one 16-byte LDS read per row instead of four addresses); with 8 it needs 168 registers = three per CU.
-#ifndef WSEG_BFP_OCC
-#define WSEG_BFP_OCC 4
-#endif
-#ifndef WSEG_BFP_UV
-#define WSEG_BFP_UV (WSEG_BFP_OCC == 4 ? 5 : 8)
-#endif
 template <typename TO, int NB>
-__global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(DecodeState st, const float* __restrict__ q,
+__global__ __launch_bounds__(256, 4) void dec_cross_attn_bfp_kernel(DecodeState st, const float* __restrict__ q,
                                                                     const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                     void* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
                                                                     const float* __restrict__ q_bias, float scale, const int* __restrict__ kv_slot) {
   typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
   typedef float f2 __attribute__((ext_vector_type(2)));
-  constexpr int U = WSEG_BFP_U;
+  constexpr int U = 8;
   __shared__ __attribute__((aligned(16))) float sc[512][NB];      // [position][beam]: one 16-byte read per row in the V pass
   __shared__ float red[4][NB][64];
   __shared__ float sinv[NB];
@@ -947,7 +924,7 @@ __global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(D
   // The first batch of K rows is requested BEFORE the query is assembled (reduce1: a chain of dependent split-K loads) and the first
   // batch of V rows before the softmax: neither depends on what it overtakes, and the kernel's fixed costs (~170 us of a 464-us launch at
   // 1 024 slots by a two-point fit against the 24-bit format) are exactly these serial sections.
-  constexpr int UV = NB == 4 ? WSEG_BFP_UV : U;      // rows per lane in flight in the V pass (the 4-beam accumulators leave room for 6 at 128 registers)
+  constexpr int UV = NB == 4 ? 5 : U;      // rows per lane in flight in the V pass (the 4-beam accumulators leave room for 6 at 128 registers)
   auto ld_rows = [&](const unsigned char* base, int t0, auto& r) __attribute__((always_inline)) {
     constexpr int UU = sizeof(r) / sizeof(r[0]);
 #pragma unroll
@@ -956,11 +933,8 @@ __global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(D
       r[u] = __builtin_nontemporal_load((const raw16*)(base + (size_t)t * 128 + sub * 16));
     }
   };
-#ifndef WSEG_BFP_PREFETCH
-#define WSEG_BFP_PREFETCH 1
-#endif
   raw16 kq[U];
-  if (WSEG_BFP_PREFETCH) ld_rows(Kb, 0, kq);
+  ld_rows(Kb, 0, kq);
   for (int i = tid; i < Tk; i += 256) { sks[i] = __builtin_nontemporal_load(Ks + i); svs[i] = __builtin_nontemporal_load(Vs + i); }
   if (pi.part != nullptr) {
     if (tid < NB * 64) sq[tid >> 6][tid & 63] = reduce1<float>(pi, w * nb + min(tid >> 6, nb - 1), h * 64 + (tid & 63), q_bias) * scale;
@@ -992,7 +966,7 @@ __global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(D
     }
   };
   for (int t0 = 0; t0 < Tk; t0 += 32 * U) {
-    if (t0 > 0 || !WSEG_BFP_PREFETCH) ld_rows(Kb, t0, kq);
+    if (t0 > 0) ld_rows(Kb, t0, kq);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * 32 + wave * 8 + rowl;
@@ -1023,7 +997,7 @@ __global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(D
     }
   }
   raw16 vq[UV];
-  if (WSEG_BFP_PREFETCH) ld_rows(Vb, 0, vq);
+  ld_rows(Vb, 0, vq);
   __syncthreads();
   for (int j = wave; j < nb; j += 4) {
     float mx = -3.0e38f;
@@ -1042,7 +1016,7 @@ __global__ __launch_bounds__(256, WSEG_BFP_OCC) void dec_cross_attn_bfp_kernel(D
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[j][e] = (f2){0.f, 0.f};
   for (int t0 = 0; t0 < Tk; t0 += 32 * UV) {
-    if (t0 > 0 || !WSEG_BFP_PREFETCH) ld_rows(Vb, t0, vq);
+    if (t0 > 0) ld_rows(Vb, t0, vq);
 #pragma unroll
     for (int u = 0; u < UV; ++u) {
       const int t = t0 + u * 32 + wave * 8 + rowl;
@@ -1533,19 +1507,17 @@ static void launch_cross_t(const DecodeState& st, const void* q, const void* ck,
   else WSEG_CA(8);
 #undef WSEG_CA
 }
-// wseg_kernels.h.  The three-MFMA modes' GEMMs are exact to ~6e-6 of a logit on the parity sweeps' models; the 24-bit FLOAT rows of
-// r03 - mid r06 (format 1) added 2e-5 — which cost f16x3 one of 4 200 sweep recordings (a greedy decision with a margin of 2.8e-5;
+// wseg_kernels.h.  The three-MFMA modes' GEMMs are exact to ~6e-6 of a logit on the parity sweeps' models; the 24-bit FLOAT rows they
+// stored from r03 to mid r06 added 2e-5 — which cost f16x3 one of 4 200 sweep recordings (a greedy decision with a margin of 2.8e-5;
 // fp32 rows reproduce it) —, 16-bit block-floating-point rows 6e-5: since r06 these modes store 24-bit block floating point (format 3:
-// the bytes of format 1 + 4 per row, error <= 2^-24 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven
-// sweeps.  The mixed mode's own fp6 cross terms cost 8e-5: it takes the 31 % smaller 16-bit rows (1.3e-4 in all).
-// Knob builds: WSEG_X3_CKV = f32 | k24 | bfp | bfp24 for every split mode (attribution / A-B).
+// 196 bytes per row, error <= 2^-24 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven sweeps.  The
+// mixed mode's own fp6 cross terms cost 8e-5: it takes the 31 % smaller 16-bit rows (format 2, 1.3e-4 in all).
 int x3_cross_kv_format(int dtype, int nb) {
-  static const int forced = WSEG_KNOB_IS("WSEG_X3_CKV", "f32") ? 0 : (WSEG_KNOB_IS("WSEG_X3_CKV", "k24") ? 1 : (WSEG_KNOB_IS("WSEG_X3_CKV", "bfp") ? 2 : (WSEG_KNOB_IS("WSEG_X3_CKV", "bfp24") ? 3 : -1)));
   if (nb > 4) return 0;
-  return forced >= 0 ? forced : (dtype == WSEG_F16M6 ? 2 : 3);
+  return dtype == WSEG_F16M6 ? 2 : 3;
 }
-// WSEG_F16M6: does the cross-attention write its output (the co-proj GEMM's operand) as M6 rows?  The 24-bit K / V kernel does (it
-// exists for up to 4 beams); 5..8 beams run the general fp32-K/V kernel, which writes hi | lo rows that the caller converts.
+// WSEG_F16M6: does the cross-attention write its output (the co-proj GEMM's operand) as M6 rows?  The block-floating-point K / V kernel
+// does (it exists for up to 4 beams); 5..8 beams run the general fp32-K/V kernel, which writes hi | lo rows that the caller converts.
 bool dec_cross_attn_writes_mx(int dtype, int nb) { return dtype == WSEG_F16M6 && x3_cross_kv_format(dtype, nb) != 0; }
 
 int launch_dec_cross_attn(int dtype, const DecodeState& st, const void* q, const void* ck, const void* cv, void* out, int H, int Tk, int d,
@@ -1553,39 +1525,26 @@ int launch_dec_cross_attn(int dtype, const DecodeState& st, const void* q, const
   if (Tk > 512) { set_error("cross-attention: %d encoder positions > 512", Tk); return WSEG_ERR_INVALID; }
   PartialInfo pi;
   if (q_part) pi = *q_part;
-  const bool m6 = dtype == WSEG_F16M6;      // M6-row output from the 24-bit K / V kernel only (dec_cross_attn_writes_mx)
+  const bool m6 = dtype == WSEG_F16M6;      // M6-row output from the block-floating-point K / V kernel only (dec_cross_attn_writes_mx)
   const int kvf = (dtype == WSEG_BF16X3 || dtype == WSEG_F16X3 || m6) ? x3_cross_kv_format(dtype, st.nb) : 0;
-  if (kvf == 2) {
+  if (kvf == 2) {      // f16m6
     dim3 grid(st.W * H), block(256);
-#define WSEG_BFP(TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_bfp_kernel<TO_, NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
-    if (dtype == WSEG_BF16X3) { if (st.nb <= 1) WSEG_BFP(X3<bf16_t>, 1); else if (st.nb <= 2) WSEG_BFP(X3<bf16_t>, 2); else WSEG_BFP(X3<bf16_t>, 4); }
-    else if (m6) { if (st.nb <= 1) WSEG_BFP(M6, 1); else if (st.nb <= 2) WSEG_BFP(M6, 2); else WSEG_BFP(M6, 4); }
-    else { if (st.nb <= 1) WSEG_BFP(X3<f16_t>, 1); else if (st.nb <= 2) WSEG_BFP(X3<f16_t>, 2); else WSEG_BFP(X3<f16_t>, 4); }
+#define WSEG_BFP(NB_) hipLaunchKernelGGL((dec_cross_attn_bfp_kernel<M6, NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
+    if (st.nb <= 1) WSEG_BFP(1); else if (st.nb <= 2) WSEG_BFP(2); else WSEG_BFP(4);
 #undef WSEG_BFP
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
-  if (kvf == 3) {
+  if (kvf == 3) {      // bf16x3 / f16x3
     dim3 grid(st.W * H), block(256);
-#define WSEG_K24(TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_k24_kernel<TO_, NB_, true>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
+#define WSEG_K24(TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_k24_kernel<TO_, NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
     if (dtype == WSEG_BF16X3) { if (st.nb <= 1) WSEG_K24(X3<bf16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<bf16_t>, 2); else WSEG_K24(X3<bf16_t>, 4); }
-    else if (m6) { if (st.nb <= 1) WSEG_K24(M6, 1); else if (st.nb <= 2) WSEG_K24(M6, 2); else WSEG_K24(M6, 4); }
     else { if (st.nb <= 1) WSEG_K24(X3<f16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<f16_t>, 2); else WSEG_K24(X3<f16_t>, 4); }
 #undef WSEG_K24
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
-  if (kvf == 1) {
-    dim3 grid(st.W * H), block(256);
-#define WSEG_K24(TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_k24_kernel<TO_, NB_, false>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
-    if (dtype == WSEG_BF16X3) { if (st.nb <= 1) WSEG_K24(X3<bf16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<bf16_t>, 2); else WSEG_K24(X3<bf16_t>, 4); }
-    else if (m6) { if (st.nb <= 1) WSEG_K24(M6, 1); else if (st.nb <= 2) WSEG_K24(M6, 2); else WSEG_K24(M6, 4); }
-    else { if (st.nb <= 1) WSEG_K24(X3<f16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<f16_t>, 2); else WSEG_K24(X3<f16_t>, 4); }
-#undef WSEG_K24
-    WSEG_LAUNCH_CHECK();
-    return WSEG_OK;
-  }
-  if (kv_slot) { set_error("cross-attention: the slot map exists for the 24-bit and block-floating-point K / V kernels only"); return WSEG_ERR_INVALID; }
+  if (kv_slot) { set_error("cross-attention: the slot map exists for the block-floating-point K / V kernels only"); return WSEG_ERR_INVALID; }
   static const bool deep = getenv("WSEG_CROSS_NO_PK") == nullptr;         // tuning knob: fp32-FMA kernel
   if ((dtype == WSEG_BF16 || dtype == WSEG_F16) && deep && Tk <= 512 && st.nb <= 4) {
     dim3 grid(st.W * H), block(256);

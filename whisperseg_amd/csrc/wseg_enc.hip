@@ -205,9 +205,6 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
     fetch_v(kt);
     const bool more = kt + 1 < n_tiles;
     if (more) fetch_k(kt + 1);
-#ifndef WSEG_EA_PRIO
-#define WSEG_EA_PRIO 1
-#endif
     // Both 32-key halves of the tile together (r05): two independent score accumulators (the 12 MFMAs of one half are a dependent chain on ONE
     // accumulator: alternating halves lets the matrix pipe run back to back), one running maximum / rescale per 64 keys instead of per 32.
     // Measured and dropped (profiles/r05_encattn_ab.txt): the second half's probabilities computed between the first half's P V MFMAs (+20 %: VALU
@@ -225,7 +222,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
       [[maybe_unused]] const char* cKls = (const char*)sKl[kt & 1];
       // (three workgroups share a CU: a wave that has MFMAs to issue goes first — MI355X_MICROARCH.md, static priority — while its
       // neighbours' softmax VALU fills the slots between them)
-      if (WSEG_EA_PRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int hs = 0; hs < 4; ++hs) {
         const bf16x8 kf0 = *(const bf16x8*)(cKs + (kfo ^ (hs << 5)));
@@ -241,7 +238,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
           s1 = H16<HT>::mfma32(kfl1, qf[hs], s1);
         }
       }
-      if (WSEG_EA_PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       if (key_base + 64 > T) {      // the ragged tile of a (window, head): a real branch — if-converted, its key indices, compares and selects
         asm volatile("");           // ran in every key block
 #pragma unroll
@@ -279,7 +276,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
       asm volatile("" ::: "memory");
       // O^T[hd][q] += V^T[hd][key] P^T[key][q]; the contraction slots of lane half g2 in MFMA (sub, mm) are the keys 32 sub + 16 mm + 4 g2 +
       // {0,1,2,3, 8,9,10,11} == registers 8 mm .. 8 mm + 7 of s<sub>: 16-key group G = 2 sub + mm of the operand-order V^T rows
-      if (WSEG_EA_PRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
         const f32x16& sv = sub == 0 ? s0 : s1;
@@ -306,7 +303,7 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
           }
         }
       }
-      if (WSEG_EA_PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       ps += lane_xor<32>(ps);
       l_run = l_run * alpha + ps;
     }
@@ -529,11 +526,6 @@ __global__ __launch_bounds__(256) void enc_attention_f32_mfma_kernel(const float
 // Launchers
 // ------------------------------------------------------------------------------------------------
 static bool is_x3(int dtype) { return dtype == WSEG_BF16X3 || dtype == WSEG_F16X3; }
-// attribution knob (tools/parity_sweep.py, profiles/): fp32-MFMA encoder attention in the split-precision modes
-int x3_enc_attention_mode() {
-  static const int v = WSEG_KNOB_IS("WSEG_X3_ENC_ATTN", "f32") ? 1 : (WSEG_KNOB_IS("WSEG_X3_ENC_ATTN", "f16") ? 0 : 2);      // (variant builds)
-  return v;
-}
 
 // Split-precision operand rows [M][2d words] <-> fp32 [M][d] (the C-ABI hands encoder states over as fp32 in these modes).
 template <typename HT>
@@ -706,16 +698,12 @@ static void launch_enc_attention_f32(const void* q, const void* k, const void* v
   }
 }
 
-bool enc_attention_writes_mx(int dtype) { return dtype == WSEG_F16M6 && x3_enc_attention_mode() == 2; }
-bool enc_attention_vt_tiled(int dtype) {
-  if (dtype == WSEG_F32) return false;
-  const bool split = dtype == WSEG_BF16X3 || dtype == WSEG_F16X3 || dtype == WSEG_F16M6;
-  return !(split && x3_enc_attention_mode() == 1);
-}
+bool enc_attention_writes_mx(int dtype) { return dtype == WSEG_F16M6; }
+bool enc_attention_vt_tiled(int dtype) { return dtype != WSEG_F32; }
 
 int launch_enc_attention(int dtype, const void* q, const void* k, const void* vt, void* out,
                          int B, int H, int T, int Tp, int d, hipStream_t s) {
-  if (dtype == WSEG_F16M6 && x3_enc_attention_mode() == 2) {      // split-precision attention writing M6 rows directly
+  if (dtype == WSEG_F16M6) {      // split-precision attention writing M6 rows directly
     if (Tp % 128) { set_error("enc_attention: Tp %d %% 128", Tp); return WSEG_ERR_INVALID; }
     dim3 grid(cdiv(T, 128), B * H);
     hipLaunchKernelGGL((enc_attention_h16_kernel<f16_t, M6, true>), grid, dim3(256), 0, s, (const f16_t*)q, (const f16_t*)k, (const f16_t*)vt, out, H, T, Tp, d,
@@ -723,22 +711,17 @@ int launch_enc_attention(int dtype, const void* q, const void* k, const void* vt
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
-  dtype = storage_dtype(dtype);
-  const bool x3 = is_x3(dtype);
-  const int mode = x3 ? x3_enc_attention_mode() : 0;
-  if (dtype == WSEG_BF16 || dtype == WSEG_F16 || (x3 && mode != 1)) {
+  if (dtype == WSEG_BF16 || dtype == WSEG_F16 || is_x3(dtype)) {
     if (Tp % 128) { set_error("enc_attention: Tp %d %% 128", Tp); return WSEG_ERR_INVALID; }
     dim3 grid(cdiv(T, 128), B * H);
     const size_t plane = (size_t)B * H * Tp * 64;
 #define WSEG_EA(HT_, TO_, SP_) hipLaunchKernelGGL((enc_attention_h16_kernel<HT_, TO_, SP_>), grid, dim3(256), 0, s, (const HT_*)q, (const HT_*)k, (const HT_*)vt, out, H, T, Tp, d, plane)
     if (dtype == WSEG_BF16) WSEG_EA(bf16_t, bf16_t, false);
     else if (dtype == WSEG_F16) WSEG_EA(f16_t, f16_t, false);
-    else if (dtype == WSEG_BF16X3) { if (mode == 2) WSEG_EA(f16_t, X3<bf16_t>, true); else WSEG_EA(f16_t, X3<bf16_t>, false); }   // IEEE-half
-    else { if (mode == 2) WSEG_EA(f16_t, X3<f16_t>, true); else WSEG_EA(f16_t, X3<f16_t>, false); }    // Q / K / V^T in both split modes
+    else if (dtype == WSEG_BF16X3) WSEG_EA(f16_t, X3<bf16_t>, true);      // IEEE-half Q / K / V^T in both split modes
+    else WSEG_EA(f16_t, X3<f16_t>, true);
 #undef WSEG_EA
-  } else if (dtype == WSEG_BF16X3) launch_enc_attention_f32<X3<bf16_t>>(q, k, vt, out, B, H, T, Tp, d, s);
-  else if (dtype == WSEG_F16X3) launch_enc_attention_f32<X3<f16_t>>(q, k, vt, out, B, H, T, Tp, d, s);
-  else launch_enc_attention_f32<float>(q, k, vt, out, B, H, T, Tp, d, s);
+  } else launch_enc_attention_f32<float>(q, k, vt, out, B, H, T, Tp, d, s);
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }

@@ -1,16 +1,16 @@
 // GEMM kernels for gfx950:  C[m][n] = sum_k A[m][k] * W[n][k]  with fused epilogues.
 //
-// bf16 path (production): MFMA v_mfma_f32_16x16x32_bf16, LDS-staged through global_load_lds (16 B per
-// lane, XOR-swizzled on the SOURCE address so the lane-linear LDS image is bank-conflict free for
-// ds_read_b128), double-buffered with a counted vmcnt so the next K-tile streams in under the MFMAs.
-// Operands are swapped (MFMA "A" = weight rows, "B" = activation rows) so that each lane ends up with
-// 4 CONSECUTIVE output columns of one output row: bias / residual / stores are 8-byte vectors.
-// Tile shapes: 128x128 (encoder, M = windows*500) and 64x64 / 32x64 with split-K (decoder steps, where
-// M = windows*beams is small and the kernel is a weight stream bounded by HBM, not MFMA).
-//
-// f32 path (exact-parity mode): plain VALU 64x64 tile, fmaf chain in k order.
-//
-// Both paths share one epilogue (epi_apply), also used by the split-K reduction kernel.
+// This file holds the MFMA kernels of the 16-bit (bf16 / f16), split-precision (bf16x3 / f16x3: hi | lo K tiles) and mixed (f16m6:
+// M6 rows, MX K tiles) modes and their launch policy; the exact-parity fp32 kernels live in wseg_gemm_f32.hip, the shared epilogues
+// in wseg_gemm_epi.h.  Operands are LDS-staged through global_load_lds (16 B per lane, XOR-swizzled on the SOURCE address so the
+// lane-linear LDS image is bank-conflict free for ds_read_b128) and swapped (MFMA "A" = weight rows, "B" = activation rows) so that
+// each lane ends up with 4 CONSECUTIVE output columns of one output row.  Kernel families:
+//   gemm_h16_kernel          64-column stream tiles (32 / 64 / 128 rows) with optional split-K into fp32 planes (decoder steps,
+//                            where M = windows*beams is small and the kernel is a weight stream), and the 128x128 tile below 16 tiles
+//   gemm_h16_persist_kernel  persistent 128x128 tiles (large GEMMs where the 256x256 tile does not qualify)
+//   gemm_h16_pp_kernel       persistent 256x256 ping-pong tiles (two 4-wave row groups), also as S split-K copies for decoder rows
+//   splitk_reduce*_kernel    sum the split-K planes and apply the epilogue (4 / 8 columns, or residual + LayerNorm)
+// launch_h16 / gemm_partial_t / gemm_resid_ln_t pick among them by shape.
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
@@ -48,15 +48,6 @@ __device__ unsigned long long g_pp_stamps[2 * 4 * 4 * 4 + 4];  // [group][K tile
 #define WSEG_PP_CLOCK() do { } while (0)
 #endif
 
-#ifndef WSEG_VT_TRANSPOSED
-#define WSEG_VT_TRANSPOSED 1      // (0: the row-wise 2-byte V^T stores of r01-r05, for same-box A/B builds)
-#endif
-#ifndef WSEG_SKINNY_NT
-#define WSEG_SKINNY_NT 1      // (0: same-box A/B builds)
-#endif
-#ifndef WSEG_PP_LATEWAIT
-#define WSEG_PP_LATEWAIT 1
-#endif
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // Barrier that closes the fragment reads of an LDS stage: every ds_read this wave has issued must have RETURNED before
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM <= 128 && BN <= 64 && WM * WN == 
   // one row tile (2-D grid): every (column tile, K range) of W is read by exactly this workgroup, once -> non-temporal weight stream
   // (r06, same-box A/B at 8 / 15 / 32 windows x 4 beams, f16m6: 3.03 -> 2.94, 3.47 -> 3.45, 4.40 -> 4.46 ms per decode step: the 128-row
   // tile keeps the default policy)
-  const bool w_once = WSEG_SKINNY_NT && BN == 64 && BM <= 64 && ntm == 0 && gridDim.y == 1;
+  const bool w_once = BN == 64 && BM <= 64 && ntm == 0 && gridDim.y == 1;
   auto issue = [&](int kt, int buf) {
 #pragma unroll
     for (int it = 0; it < A_IT; ++it)
@@ -343,13 +334,8 @@ __global__ __launch_bounds__(WM * WN * 64, (BM <= 128 && BN <= 64 && WM * WN == 
 // gfx9, so a load issued after a store cannot be consumed before that store has completed — a bias load per
 // output row made each of the 16 stores a full round trip (measured 16-42 % of a launch).
 // ------------------------------------------------------------------------------------------------
-// (NIT / I0: the accumulator array holds NIT column tiles of which I0 .. I0 + 3 are written — the 128x128 wave tiles of gemm_w4_kernel
-// go out as two 64-column halves)
-#ifndef WSEG_EPI_M6_LDS
-#define WSEG_EPI_M6_LDS 1      // (0: the register-only row writer + scalar GELU of r04, for same-box A/B builds)
-#endif
-template <typename T, int EPI, int MI, int NI, int NIT = NI, int I0 = 0>
-__device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NIT][MI], float* stage, const EpiParams& ep, int M, int mb,
+template <typename T, int EPI, int MI, int NI>
+__device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], float* stage, const EpiParams& ep, int M, int mb,
                                                 int nb, int lane, int wave) {
   static_assert(NI == 4, "64-column wave tiles");
   typedef typename IO<T>::P PT;
@@ -422,7 +408,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NIT][MI], flo
   // granule never straddles two windows.  vt_fast is wave-uniform.
   [[maybe_unused]] bool vt_fast = false;
   [[maybe_unused]] float vt_bias[4] = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (EPI == EPI_QKV_ENC && WSEG_VT_TRANSPOSED) {
+  if constexpr (EPI == EPI_QKV_ENC) {
     typedef typename IO<T>::A AT;
     vt_fast = sizeof(AT) == 2 && nb >= 2 * ep.d_model && (ep.t_len & 3) == 0 && (M & 3) == 0 && !(IO<T>::split && ep.qkv_mode == 1);
     if (vt_fast && ep.bias) {
@@ -434,9 +420,9 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NIT][MI], flo
   for (int j = 0; j < MI; ++j) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
-      *(float4*)(strip + fr * LDT + i * 16 + fg * 4) = make_float4(acc[I0 + i][j][0], acc[I0 + i][j][1], acc[I0 + i][j][2], acc[I0 + i][j][3]);
+      *(float4*)(strip + fr * LDT + i * 16 + fg * 4) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
     // same-wave LDS RAW: ds ops of one wave complete in order, the compiler waits lgkmcnt before the reads
-    if constexpr (EPI == EPI_QKV_ENC && WSEG_VT_TRANSPOSED) {
+    if constexpr (EPI == EPI_QKV_ENC) {
       if (vt_fast) {
         typedef typename IO<T>::A AT;
         const int g4 = lane & 3, hq = lane >> 2;
@@ -498,7 +484,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NIT][MI], flo
           const int kv = dec_kv[j * 2 + hh];
           if (kv >= 0) st8_h<PT>((PT*)(dec_sec == 1 ? ep.k : ep.v) + ((size_t)kv + (size_t)(nn >> 6) * KV_PAGE) * 64 + (nn & 63), v);
         }
-      } else if constexpr (WSEG_EPI_M6_LDS && IsMx<T>::v && (EPI == EPI_GELU || EPI == EPI_STORE)) {
+      } else if constexpr (IsMx<T>::v && (EPI == EPI_GELU || EPI == EPI_STORE)) {
         // M6 rows: the quad's word exchange goes through the strip slots the quad has just read (8 floats per lane = its 128 bytes)
         if constexpr (EPI == EPI_GELU) {
 #pragma unroll
@@ -730,7 +716,6 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
   typedef typename IO<T>::H HT;
   constexpr bool MXM = IsMx<T>::v;      // M6 rows: odd K tiles are MX tiles (16 scaled MFMAs per phase instead of 32 plain ones)
   constexpr bool X3M = IO<T>::split && !IsMx<T>::v;      // hi | lo K tiles: 24 instead of 16 MFMAs per phase, (W hi, A hi) (W hi, A lo) (W lo, A hi)
-  constexpr bool LATEWAIT = WSEG_PP_LATEWAIT != 0;      // see hi_tile, phase B
   constexpr int BM = 256, BN = 256, BK = 64, TM = 128, TN = 64, MI = 8, NI = 4;
   constexpr int HTILE = 128 * BK;                      // elements per half-tile (16 KB)
   constexpr int BUF = 4 * HTILE;                       // elements per K-tile buffer: [A0 | A1 | B0 | B1]
@@ -931,20 +916,16 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
       afr[j][0] = *(const bf16x8*)(cur + (4 + j) * 16 * BK + fa0);
       afr[j][1] = *(const bf16x8*)(cur + (4 + j) * 16 * BK + fa1);
     }
-    // Retirement of K tile g+1 (LATEWAIT, r04; the stamps showed 280 cycles of exposed load latency in this L part): group 1's pieces
+    // Retirement of K tile g+1 (r04; the stamps showed 280 cycles of exposed load latency in this L part): group 1's pieces
     // of its B pair — group 0 reads them at the start of the next interval but one — are retired here, everything else (a group's
     // own A half, group 0's B pieces) only behind this phase's MFMAs, one interval later.  Issue order per wave: B pair of g+1,
     // A half of g+1, B pair of g+2.
     const bool pb = MID || (!final && g + 2 < KT);
     if (pb) issue_b(PAR);                                           // B pair of K tile g+2
-    if constexpr (LATEWAIT) {
-      if (wr == 1) { if (pb) wait_vmcnt<8>(); else wait_vmcnt<4>(); }
-    } else {
-      if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
-    }
+    if (wr == 1) { if (pb) wait_vmcnt<8>(); else wait_vmcnt<4>(); }
     __builtin_amdgcn_sched_barrier(0);
     WSEG_PP_MFMA(1, 1, 0);
-    if constexpr (LATEWAIT) { if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+    if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
     if (!final) __builtin_amdgcn_s_barrier();
   };
   [[maybe_unused]] auto mx_tile = [&](int kt, auto mid_tag) {
@@ -982,11 +963,7 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
       am[0] = ld_mx_frag7<8192>(a0, a1); am[1] = ld_mx_frag7<10240>(a0, a1); am[2] = ld_mx_frag7<12288>(a0, a1); am[3] = ld_mx_frag7<14336>(a0, a1);
       const bool pb = MID || (!final && g + 2 < KT);
       if (pb) issue_b(1);
-      if constexpr (LATEWAIT) {
-        if (wr == 1) { if (pb) wait_vmcnt<8>(); else wait_vmcnt<4>(); }
-      } else {
-        if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
-      }
+      if (wr == 1) { if (pb) wait_vmcnt<8>(); else wait_vmcnt<4>(); }
       __builtin_amdgcn_sched_barrier(0);
       WSEG_PP_STAMP(1, 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1000,7 +977,7 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
         for (int j = 0; j < 4; ++j) mfma_mx6_asm(acc[i][4 + j], bm[i], am[j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (LATEWAIT) { if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+      if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
       WSEG_PP_STAMP(1, 3);
       if (!final) __builtin_amdgcn_s_barrier();
   };
@@ -1134,11 +1111,9 @@ static SkinnyPlan plan_skinny(const GemmArgs& g0, bool pairs = false) {      // 
   SkinnyPlan sp;
   // largest row tile that still yields >= 160 workgroups without splitting K; otherwise 128 rows + split-K
   sp.bm = g.M <= 32 ? 32 : (g.M <= 64 ? 64 : 128);
-  static const int force_bm = WSEG_KNOB_INT("WSEG_SKINNY_BM", 0);   // tuning knob (variant builds)
   if (g.M > 64) {
     const int nt = g.N / 64;
     if (nt * cdiv(g.M, 128) < 160 && nt * cdiv(g.M, 64) >= 160) sp.bm = 64;
-    if (force_bm == 64 || force_bm == 128) sp.bm = force_bm;
   }
   sp.bn = 64;
   sp.mt = cdiv(g.M, sp.bm);
@@ -1148,8 +1123,7 @@ static SkinnyPlan plan_skinny(const GemmArgs& g0, bool pairs = false) {      // 
   if (g.splitk_ws) {
     // split K (in whole 64-wide tiles, >= 2 tiles per split) until ~256 workgroups stream the weights
     const int nk = g.K / 64;
-    static const int target = WSEG_KNOB_INT("WSEG_SKINNY_TARGET", 256);   // tuning knob (variant builds)
-    for (int cand = 2; cand <= 16 && blocks * sp.splits < target; ++cand) {
+    for (int cand = 2; cand <= 16 && blocks * sp.splits < 256; ++cand) {
       if (nk % cand || nk / cand < 2 || (pairs && (nk / cand) % 2)) continue;
       if ((size_t)cand * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) break;
       sp.splits = cand;
@@ -1253,9 +1227,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_resid_ln_kernel(const float
 // 320 blocks of 128x128) is better in the stream family (decode step 10.71 -> 10.23 ms); at 1536 rows q|k|v (360 blocks)
 // and fc1 (480) are better on large tiles (13.50 vs 13.70 ms).
 static bool big_tile_path(const GemmArgs& g) {
-  static const long big_min = WSEG_KNOB_INT("WSEG_BIG_MIN_BLOCKS", 340);   // tuning knob (variant builds)
   const int pm = plan_rows(g);
-  return pm > 128 && g.N % 128 == 0 && (long)cdiv(pm, 128) * (g.N / 128) >= big_min;
+  return pm > 128 && g.N % 128 == 0 && (long)cdiv(pm, 128) * (g.N / 128) >= 340;
 }
 
 // Split-precision modes: the caller's K / lda / ldw are LOGICAL; the kernels see rows of 2K 16-bit words.
@@ -1268,10 +1241,7 @@ template <typename T> static GemmArgs kernel_view(const GemmArgs& g0) {
 template <typename T> static int launch_pp_splitk(const GemmArgs& g, int S, hipStream_t s);
 template <typename T> static int pp_splitk_plan(const GemmArgs& g);
 
-static bool skinny_split_writes_mx(int N) {
-  static const bool off = WSEG_KNOB_SET("WSEG_NO_MX_REDUCE");      // A/B knob (variant builds)
-  return !off && N % 32 == 0;
-}
+static bool skinny_split_writes_mx(int N) { return N % 32 == 0; }
 
 template <int EPI, typename T>
 static int launch_h16(const GemmArgs& g0, hipStream_t s) {
@@ -1281,22 +1251,19 @@ static int launch_h16(const GemmArgs& g0, hipStream_t s) {
   const HT* W = (const HT*)g.W;
   if (g.K % 64 || g.N % 64 || (IsMx<T>::v && g.K % 128)) { set_error("gemm h16: K %d / N %d not tile multiples", g.K, g.N); return WSEG_ERR_INVALID; }
   if (big_tile_path(g)) {
-    static const bool no_swz = WSEG_KNOB_SET("WSEG_NO_XCD_SWIZZLE");
-    static const bool big256 = !WSEG_KNOB_SET("WSEG_GEMM_128");   // 256x256 tiles by default where they fill the chip
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (g_prof.on) {
       std::lock_guard<std::mutex> lk(g_prof.mu);
       e0 = g_prof.get(); e1 = g_prof.get(); g_prof.flops.push_back(2.0 * g0.M * g0.N * g0.K); (void)hipEventRecord(e0, s);
     }
-    static const bool persist = !WSEG_KNOB_SET("WSEG_GEMM_NO_PERSIST");
     // m-tiles per tile group of the persistent order: the 32 tiles in flight on one XCD then span ~4 activation tiles x 8
     // weight tiles, the smallest operand footprint for 32 tiles (a + b = 12 operand tiles; 2-row groups re-stream the
     // whole weight matrix per tile pair: PMC FETCH_SIZE 2-3x the algorithmic bytes, profiles/).  Measured at 256
     // windows: 4 beats 2 by 2-8 % on the K = 1280 shapes, 6 and 8 lose on K = 5120.
 #if defined(WSEG_STAMPS) && WSEG_STAMPS == 4
-    static const int group_m = WSEG_KNOB_INT("WSEG_GEMM_GROUP_M", 4) | (getenv("WSEG_PP_SOLO") ? 0x100 : 0);
+    static const int group_m = 4 | (getenv("WSEG_PP_SOLO") ? 0x100 : 0);
 #else
-    static const int group_m = WSEG_KNOB_INT("WSEG_GEMM_GROUP_M", 4);
+    constexpr int group_m = 4;
 #endif
     const int n_cu = device_cu_count();
     // 256x256 tiles need whole rounds of the chip: with fewer than 4 rounds, a last round that leaves more than a fifth of
@@ -1305,26 +1272,22 @@ static int launch_h16(const GemmArgs& g0, hipStream_t s) {
     const int pm = plan_rows(g);
     const long nt256 = (long)cdiv(pm, 256) * (g.N / 256);
     const long rounds256 = (nt256 + n_cu - 1) / n_cu;
-    static const bool quant_rule = !WSEG_KNOB_SET("WSEG_GEMM_NO_QUANT_RULE");   // tuning knob (variant builds)
     // (split / mixed modes: a K tile pair costs twice the bf16 K tile while the 128x128 kernel's fixed costs do not shrink — since the
     // r04 K-loop work the 256x256 kernel wins down to 3/5 of a last round: decoder fc1 at 4 096 rows, 320 tiles, 152 against 161 us)
-    const bool ragged256 = quant_rule && rounds256 < 4 && nt256 * 5 < rounds256 * n_cu * (IO<T>::split ? 3 : 4);
+    const bool ragged256 = rounds256 < 4 && nt256 * 5 < rounds256 * n_cu * (IO<T>::split ? 3 : 4);
     // (r05: 160 tiles for the GELU epilogue in the split / mixed modes — decoder fc1 at 2 048 rows, one round on 62 % of the CUs: 512 slots 21.3 ->
     // 20.3 ms per decode step; NOT for the q|k|v epilogue: 180 tiles at 3 072 rows lose to two rounds of 128x128 tiles, 28.0 -> 29.0 ms)
-    static const int min_tiles256 = WSEG_KNOB_INT("WSEG_BIG256_MIN_TILES", 0);
-    const long need256 = min_tiles256 ? min_tiles256 : ((IO<T>::split && EPI == EPI_GELU) ? 160 : 192);
-    if (big256 && g.N % 256 == 0 && nt256 >= need256 && !ragged256 && g.K >= 128) {      // (K = 64 words: one K tile, 128x128 kernel)
+    const long need256 = (IO<T>::split && EPI == EPI_GELU) ? 160 : 192;
+    if (g.N % 256 == 0 && nt256 >= need256 && !ragged256 && g.K >= 128) {      // (K = 64 words: one K tile, 128x128 kernel)
       const int ntm = cdiv(g.M, 256), ntiles = ntm * (g.N / 256);
-      constexpr bool pingpong = true;      // (r05: the generic / persistent kernels' 256x256 instantiations — knob-only paths that spilled 200-330 bytes per lane — are gone)
       // WSEG_F16M6, M6-row outputs, between one and two rounds of 256x256 tiles (decoder fc1 at 4 096 rows: 320 tiles on 256 CUs — the
       // second round runs on a quarter of the chip): the columns that fill ONE round go through the kernel as usual; the remaining
       // column tiles are multiplied as split-K copies that fill the chip once more for 1 / S of the K range, and the 8-column
       // reduction writes their M6 rows.
       if constexpr (IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU)) {
-        static const bool tail_split = !WSEG_KNOB_SET("WSEG_NO_TAIL_SPLIT");      // A/B knob (variant builds)
         const int ptm = cdiv(pm, 256);      // planned row tiles: the column split and S must not follow the rows launched
         const int ntn = g.N / 256, full_cols = n_cu / ptm, pairs = g.K / 128;
-        if (tail_split && pingpong && rounds256 == 2 && g.splitk_ws && full_cols >= 1 && full_cols < ntn && g.K >= 256) {
+        if (rounds256 == 2 && g.splitk_ws && full_cols >= 1 && full_cols < ntn && g.K >= 256) {
           const int rem_tiles = (ntn - full_cols) * ptm, n1 = full_cols * 256, n2 = g.N - n1;
           int S = n_cu / rem_tiles;
           while (S >= 2 && ((rem_tiles * S) % 8 || pairs / S < 2 || (size_t)S * pm * n2 * sizeof(float) > g.splitk_ws_bytes)) --S;
@@ -1359,30 +1322,25 @@ static int launch_h16(const GemmArgs& g0, hipStream_t s) {
       }
     } else {
       const int ntm = cdiv(g.M, 128), ntiles = ntm * (g.N / 128);
-      if (persist && !no_swz && cdiv(pm, 128) * (g.N / 128) >= 16) {
+      if (cdiv(pm, 128) * (g.N / 128) >= 16) {
         int grid = ntiles < 2 * n_cu ? ntiles : 2 * n_cu;
         grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
         hipLaunchKernelGGL((gemm_h16_persist_kernel<T, 128, 128, 2, 2, EPI>), dim3(grid), dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N,
                            g.K, g.ep, ntm, group_m);
       } else {
-        dim3 grid(g.N / 128, ntm, 1);
-        if (!no_swz) grid = dim3(ntiles, 1, 1);
-        hipLaunchKernelGGL((gemm_h16_kernel<T, 128, 128, 2, 2, EPI, false>), grid, dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N,
-                           g.K, g.ep, (float*)nullptr, 0, no_swz ? 0 : ntm);
+        hipLaunchKernelGGL((gemm_h16_kernel<T, 128, 128, 2, 2, EPI, false>), dim3(ntiles), dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N,
+                           g.K, g.ep, (float*)nullptr, 0, ntm);
       }
     }
     if (e1) (void)hipEventRecord(e1, s);
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
-#ifndef WSEG_MX_PP_SPLITK
-#define WSEG_MX_PP_SPLITK 1
-#endif
   // WSEG_F16M6, M6-row outputs below the large-tile threshold but with hundreds of rows (decoder fc1 at 112-270 slots; r05): split-K copies
   // of the 256x256 kernel + the M6-writing 8-column reduction, instead of the 128x64 stream kernel (whose 4-column epilogue writes hi | lo
   // rows that a conversion launch turns into M6 rows): 57.5 + 11.8 us -> see profiles/r05_epilogue_ab.txt.  gemm_out_is_mx predicts it.
   if constexpr (IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU)) {
-    const int S = WSEG_MX_PP_SPLITK ? pp_splitk_plan<T>(g) : 0;
+    const int S = pp_splitk_plan<T>(g);
     if (S) {
       WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
       hipLaunchKernelGGL((splitk_reduce8_kernel<EPI, T>), dim3(cdiv(g.M * (g.N / 8), 256)), dim3(256), 0, s, g.splitk_ws, S, g.M, g.M, g.N, g.ep);
@@ -1435,23 +1393,19 @@ static int launch_any(int dtype, const GemmArgs& g, hipStream_t s) {
 template <typename T>
 static int gemm_partial_t(const GemmArgs& g0, PartialInfo* info, bool* ok, hipStream_t s) {
   const GemmArgs g = kernel_view<T>(g0);
-#ifndef WSEG_PARTIAL_PP
-#define WSEG_PARTIAL_PP 1
-#endif
-  static const bool partial_big = !WSEG_KNOB_SET("WSEG_NO_PARTIAL_BIG");
-  // (r05: also ABOVE the large-tile threshold when the 256x256 tiles fill at most half the chip — decoder q|k|v at 2 048 rows, 120 tiles: two split-K
-  // copies + the reduction inside the attention kernel instead of the 128x128 kernel with its own epilogue)
   if (!g.splitk_ws || g.K % 64 || g.N % 64) return WSEG_OK;
-  if (big_tile_path(g) && !(WSEG_PARTIAL_PP && partial_big && pp_splitk_plan<T>(g) >= 2)) return WSEG_OK;
-  if (WSEG_PARTIAL_PP) {      // thousands of rows, too few 256x256 tiles for the chip (the decode step's cross-attention query): the split-K copies
-    const int S = pp_splitk_plan<T>(g);      // of the ping-pong kernel leave the same fp32 planes [z][M][N] as the stream family
-    if (S) {
-      WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
-      info->part = g.splitk_ws; info->splits = S; info->m_pad = g.M; info->n = g.N;
-      *ok = true;
-      return WSEG_OK;
-    }
+  // thousands of rows, too few 256x256 tiles for the chip (the decode step's cross-attention query): the split-K copies of the
+  // ping-pong kernel leave the same fp32 planes [z][M][N] as the stream family.  (r05: also ABOVE the large-tile threshold when the
+  // 256x256 tiles fill at most half the chip — decoder q|k|v at 2 048 rows, 120 tiles: two split-K copies + the reduction inside the
+  // attention kernel instead of the 128x128 kernel with its own epilogue)
+  const int S = pp_splitk_plan<T>(g);
+  if (S) {
+    WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
+    info->part = g.splitk_ws; info->splits = S; info->m_pad = g.M; info->n = g.N;
+    *ok = true;
+    return WSEG_OK;
   }
+  if (big_tile_path(g)) return WSEG_OK;
   SkinnyPlan sp = plan_skinny(g, IsMx<T>::v);
   if ((size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) return WSEG_OK;
   WSEG_TRY_(launch_skinny_partial<T>(g, sp, s));
@@ -1478,29 +1432,25 @@ int launch_gemm_partial(int dtype, const GemmArgs& g, PartialInfo* info, bool* o
 // rows: 16 x 5 = 80 tiles on 256 CUs; the 128x64 stream kernel needs 99 us for it, hipBLASLt 56): S = n_cu / tiles copies of the
 // tile grid, each multiplying 1/S of the K tiles into an fp32 partial plane.  Returns 0 when the shape does not qualify.
 template <typename T> static int pp_splitk_plan(const GemmArgs& g) {
-  // tuning knobs.  Split / mixed modes (twice the K tiles per logical column, r04 K loop): the split-K 256x256 kernel beats the
-  // 128x64 stream kernel from 512 rows up (decode step at 128 / 256 / 384 slots: 9.9 -> 9.3, 15.2 -> 14.5, 18.4 -> 17.7 ms; at 64
-  // slots the stream kernel wins, 6.2 against 6.7 ms)
-  static const int min_rows_env = WSEG_KNOB_INT("WSEG_PP_SPLITK_MIN_ROWS", 0);
-  const int min_rows = min_rows_env ? min_rows_env : (IO<T>::split ? 448 : 2048);      // (r05: 480 rows = the 120 windows of a one-hour recording, 9.39 -> 8.99 ms per step; at 384 rows the stream kernel wins, 7.32 against 7.77)
-  static const int min_kt = WSEG_KNOB_INT("WSEG_PP_SPLITK_MIN_KT", 40);
+  // Split / mixed modes (twice the K tiles per logical column, r04 K loop): the split-K 256x256 kernel beats the 128x64 stream
+  // kernel from 512 rows up (decode step at 128 / 256 / 384 slots: 9.9 -> 9.3, 15.2 -> 14.5, 18.4 -> 17.7 ms; at 64 slots the
+  // stream kernel wins, 6.2 against 6.7 ms)
+  const int min_rows = IO<T>::split ? 448 : 2048;      // (r05: 480 rows = the 120 windows of a one-hour recording, 9.39 -> 8.99 ms per step; at 384 rows the stream kernel wins, 7.32 against 7.77)
   const int pm = plan_rows(g);
-  if (pm < min_rows || g.N % 256 || g.K % 64 || g.K / 64 < min_kt || !g.splitk_ws) return 0;
+  if (pm < min_rows || g.N % 256 || g.K % 64 || g.K / 64 < 40 || !g.splitk_ws) return 0;
   const int nt = cdiv(pm, 256) * (g.N / 256), nk = g.K / 64, n_cu = device_cu_count();
-  static const int max_s = WSEG_KNOB_INT("WSEG_PP_SPLITK_MAX_S", 64), min_kt_per = WSEG_KNOB_INT("WSEG_PP_SPLITK_KT_PER", 4);
   int S = n_cu / nt;
-  if (S > max_s) S = max_s;
-  while (S >= 2 && ((nt * S) % 8 || nk / S < min_kt_per || (size_t)S * pm * g.N * sizeof(float) > g.splitk_ws_bytes)) --S;
+  if (S > 64) S = 64;
+  while (S >= 2 && ((nt * S) % 8 || nk / S < 4 || (size_t)S * pm * g.N * sizeof(float) > g.splitk_ws_bytes)) --S;
   // fewer than 96 workgroups of 5 K tiles each (d x d projections at 448-511 rows) lose to the stream family: 120 windows 8.9-9.1 -> 8.6 ms per
   // decode step, 112 windows 8.73 -> 8.13 (profiles/r05_epilogue_ab.txt)
-  static const int min_wgs = WSEG_KNOB_INT("WSEG_PP_SPLITK_MIN_WGS", 96);
-  if (nt * S < min_wgs) return 0;
+  if (nt * S < 96) return 0;
   return S >= 2 ? S : 0;
 }
 
 template <typename T> static int launch_pp_splitk(const GemmArgs& g, int S, hipStream_t s) {
   typedef typename IO<T>::H HT;
-  static const int group_m = WSEG_KNOB_INT("WSEG_GEMM_GROUP_M", 4);
+  constexpr int group_m = 4;
   const int ntm = cdiv(g.M, 256), ntiles = ntm * (g.N / 256) * S, n_cu = device_cu_count();
   int grid = ntiles < n_cu ? ntiles : n_cu;
   grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
@@ -1532,10 +1482,9 @@ static int gemm_resid_ln_t(const GemmArgs& g0, const void* gamma, const void* be
       g.N % 64)
     return WSEG_OK;
   SkinnyPlan sp = plan_skinny(g, IsMx<T>::v);
-  static const bool fuse_unsplit = !WSEG_KNOB_SET("WSEG_RESID_LN_ALWAYS_PARTIAL");   // tuning knob (variant builds)
   // K not split (enough row tiles to fill the chip, 2048+ rows): the fp32 partial round trip buys nothing; the GEMM adds
   // the residual in its own epilogue and a LayerNorm launch follows (2048 rows: 21.6 + ~6 us against 26.7 + 8.9 us)
-  if (!(sp.splits > 1 || !fuse_unsplit) || (size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) return WSEG_OK;
+  if (sp.splits == 1 || (size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) return WSEG_OK;
   WSEG_TRY_(launch_skinny_partial<T>(g, sp, s));
   hipLaunchKernelGGL(splitk_reduce_resid_ln_kernel<T>, dim3(g.M), dim3(256), 0, s, g.splitk_ws, sp.splits, sp.m_pad, g.M, d,
                      (const PT*)g.ep.bias, (float*)g.ep.out, (const PT*)gamma, (const PT*)beta, y);
@@ -1569,7 +1518,7 @@ bool gemm_out_is_mx(int dtype, int M, int N, int K, size_t splitk_ws_bytes) {
   if (!splitk_ws_bytes || g.K % 128 || N % 64) return false;
   g.splitk_ws = (float*)(uintptr_t)16;      // any non-null value: the plans only ask whether a workspace exists and how large it is
   g.splitk_ws_bytes = splitk_ws_bytes;
-  if (WSEG_MX_PP_SPLITK && pp_splitk_plan<M6>(g)) return true;
+  if (pp_splitk_plan<M6>(g)) return true;
   return plan_skinny(g, true).splits > 1 && skinny_split_writes_mx(N);
 }
 
@@ -1644,11 +1593,6 @@ extern "C" int wseg_profile_end(double* total_flops, double* total_ms, int64_t* 
   return WSEG_OK;
 }
 
-#if defined(WSEG_STAMPS) && WSEG_STAMPS == 6 && defined(WSEG_KNOBS)
-extern "C" int wseg_debug_w4_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(wseg::g_w4_stamps), sizeof(unsigned long long) * (4 * 512 + 32));
-}
-#endif
 #if defined(WSEG_STAMPS) && WSEG_STAMPS == 4
 extern "C" int wseg_debug_pp_stamps(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(wseg::g_pp_stamps), sizeof(unsigned long long) * 132);

@@ -60,11 +60,11 @@ __device__ __forceinline__ void st_bfp16_row(unsigned char* blk, int t_len, int 
 }
 
 // Cross K / V as block floating point with 24-BIT integers (EpiParams::kv24 == 3; r06): the same row agreement, elements as two's-complement
-// 24-bit integers q with max|v| <= 2^23 * 2^s, stored in the two-plane layout of the 24-bit float format — [t_len][64] int16 (q >> 8), then
-// [t_len][64] bytes (q & 0xff) — followed by [t_len] fp32 row scales 2^(s - 8): the reader rebuilds the 32-bit word [q >> 8 | q & 0xff | 0] =
-// 256 q with the v_perm it already has, converts it with v_cvt_f32_i32 and multiplies the finished score / the probability by the stored
-// scale.  Same bytes per row as the 24-bit floats (+ 4), error <= 2^-24 of the ROW maximum instead of 2^-17 of every element: the 24-bit
-// floats were the largest term of f16x3's logit error (2e-5 of 2.5e-5) and cost it one of 4 200 sweep recordings.
+// 24-bit integers q with max|v| <= 2^23 * 2^s, stored in two planes — [t_len][64] int16 (q >> 8), then [t_len][64] bytes (q & 0xff) —
+// followed by [t_len] fp32 row scales 2^(s - 8): the reader rebuilds the 32-bit word [q >> 8 | q & 0xff | 0] = 256 q with one v_perm,
+// converts it with v_cvt_f32_i32 and multiplies the finished score / the probability by the stored scale.  196 bytes per row, error
+// <= 2^-24 of the ROW maximum instead of the 2^-17 of every element that the 24-bit floats stored until mid r06 had: those were the largest
+// term of f16x3's logit error (2e-5 of 2.5e-5) and cost it one of 4 200 sweep recordings.
 template <int NC>
 __device__ __forceinline__ void st_bfp24_row(unsigned char* blk, int t_len, int t, int e, const float (&v)[NC], bool first_lane) {
   static_assert(NC == 4 || NC == 8, "4 or 8 columns per lane");
@@ -173,14 +173,6 @@ __device__ __forceinline__ void epi_apply(const EpiParams& ep, int m, int n0, fl
     } else if (IO<T>::split && ep.kv24 == 3) {
       unsigned char* blk = (unsigned char*)(sec == 0 ? ep.k : ep.v) + ((size_t)bs * ep.n_heads + h) * ep.t_len * 196;
       st_bfp24_row<4>(blk, ep.t_len, t, e, *(const float(*)[4])v, e == 0);
-    } else if (IO<T>::split && ep.kv24) {
-      unsigned char* blk = (unsigned char*)(sec == 0 ? ep.k : ep.v) + ((size_t)bs * ep.n_heads + h) * ep.t_len * 192;
-      unsigned w[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = __float_as_uint(v[i]) + 0x80u;        // round to 24 bits (half up in magnitude)
-      *(uint2*)(blk + (size_t)t * 128 + e * 2) = make_uint2((w[0] >> 16) | (w[1] & 0xffff0000u), (w[2] >> 16) | (w[3] & 0xffff0000u));
-      *(unsigned*)(blk + (size_t)ep.t_len * 128 + (size_t)t * 64 + e) =
-          ((w[0] >> 8) & 0xffu) | (w[1] & 0xff00u) | ((w[2] << 8) & 0xff0000u) | ((w[3] << 16) & 0xff000000u);
     } else {
       PT* dst = (PT*)(sec == 0 ? ep.k : ep.v) + (((size_t)bs * ep.n_heads + h) * ep.t_len + t) * 64 + e;
       Vec4<PT>::st(dst, v);
@@ -303,11 +295,6 @@ __device__ __forceinline__ void epi_apply8(const EpiParams& ep, int m, int n0, f
     } else if (IO<T>::split && ep.kv24 == 3) {
       unsigned char* blk = (unsigned char*)(sec == 0 ? ep.k : ep.v) + ((size_t)bs * ep.n_heads + h) * ep.t_len * 196;
       st_bfp24_row<8>(blk, ep.t_len, t, e, *(const float(*)[8])v, e == 0);
-    } else if (IO<T>::split && ep.kv24) {
-      EpiParams e2 = ep;                        // the bias has been added above
-      e2.bias = nullptr;
-      epi_apply<EPI, T>(e2, m, n0, v);
-      epi_apply<EPI, T>(e2, m, n0 + 4, v + 4);
     } else {
       PT* dst = (PT*)(sec == 0 ? ep.k : ep.v) + (((size_t)bs * ep.n_heads + h) * ep.t_len + t) * 64 + e;
       st8_h<PT>(dst, v);

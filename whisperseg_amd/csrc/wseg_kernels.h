@@ -51,17 +51,17 @@ struct EpiParams {
                                  // table entry names may already belong to another slot)
   const int* slot_map = nullptr; // device [M / t_len]: destination window slot of each window of the batch (EPI_KV_CROSS); null = identity
   float* out_f32 = nullptr;
-  int qkv_mode = 0;              // split-precision modes, EPI_QKV_ENC storage of Q / K / V^T (x3_enc_attention_mode): 0 = IEEE half,
-                                 // 1 = fp32 (fp32 attention kernel), 2 = half hi + lo planes, the lo plane qkv_plane elements behind
+  int qkv_mode = 0;              // EPI_QKV_ENC storage of Q / K / V^T: 0 = one plane in the operand type (16-bit modes); 2 = the split
+                                 // modes' IEEE-half hi + lo planes, the lo plane qkv_plane elements behind (the epilogues also store
+                                 // 1 = fp32 planes, which no launcher selects)
   size_t qkv_plane = 0;
   int vt_tiled = 0;              // EPI_QKV_ENC: V^T in the MFMA operand order of the 16-bit attention kernel (vt_tiled_index, wseg_common.h)
                                  // instead of plain [b][h][64][t_pad] rows (the fp32 attention kernels): enc_attention_vt_tiled(dtype)
   int kv24 = 0;                  // split-precision modes, EPI_KV_CROSS storage of the cross K / V (x3_cross_kv_format): 0 = fp32;
-                                 // 1 = 24-bit FLOATS in two planes per (slot, head): [t_len][64] top halves (16 bits) then [t_len][64]
-                                 // third bytes (knob builds; bf16x3 / f16x3 until mid r06); 2 (f16m6, r05) = block floating point, one block
-                                 // per (position, head) row: [t_len][64] int16 then [t_len] fp32 powers of two, value = int16 * scale (132
-                                 // bytes per row); 3 (bf16x3 / f16x3, r06) = block floating point with 24-bit integers in the two planes
-                                 // of format 1, then [t_len] fp32 powers of two (196 bytes per row)
+                                 // 2 (f16m6, r05) = block floating point, one block per (position, head) row: [t_len][64] int16 then
+                                 // [t_len] fp32 powers of two, value = int16 * scale (132 bytes per row); 3 (bf16x3 / f16x3, r06) = block
+                                 // floating point with 24-bit integers q: [t_len][64] int16 (q >> 8), then [t_len][64] bytes (q & 0xff),
+                                 // then [t_len] fp32 powers of two 2^(s - 8), value = 256 q * scale (196 bytes per row)
 };
 
 struct GemmArgs {
@@ -115,20 +115,16 @@ bool enc_attention_vt_tiled(int dtype);
 int launch_enc_attention(int dtype, const void* q, const void* k, const void* vt, void* out,
                          int B, int H, int T, int Tp, int d, hipStream_t s);
 
-// split-precision modes: arithmetic of the encoder self-attention -> EpiParams::qkv_mode.  2 (default): split precision (half
-// hi + lo operands, three MFMAs per product); 0: plain IEEE half (WSEG_X3_ENC_ATTN=f16); 1: fp32 matrix cores (=f32).
-int x3_enc_attention_mode();
 // Storage format of the cross-attention K / V in the split-precision modes (EpiParams::kv24) and its bytes per (position, head) row.
-// 1 = fp32 words rounded to their top 24 bits (sign, exponent, 15 + 1 mantissa bits — the ">= 16 bits" the precision study asks of the
-// cross K; 3 instead of 4 bytes per element of an HBM-bound stream): bf16x3 / f16x3 until mid r06, now a knob-build format.
-// 2 = per-row block floating point (r05): the 200-recording sweep through the CPU oracle with K and V so quantised is 200 / 200 and the
-// first-step logit error stays at the mixed mode's own 1.5e-4 (24-bit: 1.5e-4; plain half: 7.5e-4, 196 / 200; tools/precision_study.py
-// "ckv=bfp16r", profiles/r05_precision_study.json) for 132 instead of 192 bytes per row of an HBM-bound stream: f16m6 (wseg_dec.hip,
-// x3_cross_kv_format, says why the three-MFMA modes do not take it).
-int x3_cross_kv_format(int dtype, int nb);      // 0 = fp32 (more than 4 beams), 1 = 24-bit (bf16x3 / f16x3), 2 = bfp16 rows (f16m6)
-// 3 (r06: bf16x3 / f16x3) = block floating point with 24-bit integers in the two-plane layout of format 1 + [t_len] fp32 row scales:
-// the bytes of the 24-bit floats (+ 4 per row), ~100x their precision relative to the row maximum (st_bfp24_row, wseg_gemm_epi.h).
-static inline size_t cross_kv_row_bytes(int fmt, size_t es) { return fmt == 3 ? 196 : (fmt == 2 ? 132 : (fmt == 1 ? 192 : 64 * es)); }
+// 0 = fp32 rows (more than 4 beams: no beam-tiled cross-attention kernel).
+// 2 = per-row block floating point with int16 elements (r05, f16m6): the 200-recording sweep through the CPU oracle with K and V so
+// quantised is 200 / 200 and the first-step logit error stays at the mixed mode's own 1.5e-4 (plain half: 7.5e-4, 196 / 200;
+// tools/precision_study.py "ckv=bfp16r", profiles/r05_precision_study.json) for 132 bytes per row of an HBM-bound stream
+// (wseg_dec.hip, x3_cross_kv_format, says why the three-MFMA modes do not take it).
+// 3 = per-row block floating point with 24-bit integer elements (r06, bf16x3 / f16x3): 196 bytes per row, error <= 2^-24 of the row
+// maximum (st_bfp24_row, wseg_gemm_epi.h).
+int x3_cross_kv_format(int dtype, int nb);
+static inline size_t cross_kv_row_bytes(int fmt, size_t es) { return fmt == 3 ? 196 : (fmt == 2 ? 132 : 64 * es); }
 // WSEG_F16M6: hi | lo IEEE-half operand rows [M][2K words] -> M6 rows [M][4K bytes] (wseg_common.h), K % 64 == 0
 int launch_x3_to_m6(const void* x3_rows, void* m6_rows, size_t M, int K, bool weight_order, hipStream_t s);
 // the dtype every NON-GEMM kernel runs in: WSEG_F16M6 is WSEG_F16X3 outside the GEMMs

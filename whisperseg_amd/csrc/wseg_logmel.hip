@@ -466,8 +466,7 @@ extern "C" int wseg_logmel_f32(const wseg_logmel_desc* d, const float* audio, in
   }
   const int nc = d->n_fft / 2;
   const size_t smem = (size_t)nc * 8 + (size_t)a.fpb * nc * 8 + (size_t)a.fpb * (nc + 1) * 4;
-  static const bool generic_only = getenv("WSEG_LOGMEL_GENERIC") != nullptr;       // A/B + test knob
-  bool fast_ok = (d->n_fft == 512 || d->n_fft == 1024) && d->n_mels <= 96 && !generic_only;
+  const bool fast_ok = (d->n_fft == 512 || d->n_fft == 1024) && d->n_mels <= 96;      // other shapes: the generic kernel
   if (a.n_frames > 0 && fast_ok) {
     dim3 grid(cdiv(a.n_frames, LM_FB), n_windows);
     hipLaunchKernelGGL(logmel_items_kernel, dim3(1), dim3(256), 0, stream, *d, (LmTables*)a.tables);

@@ -79,7 +79,6 @@ struct wseg_model {
   bool mx = false;           // WSEG_F16M6: GEMM operands are M6 rows (weights attached converted; activations converted before each GEMM)
   int sdt = 0;               // dtype of every non-GEMM kernel (WSEG_F16M6 -> WSEG_F16X3)
   const void* dec_tok_f32 = nullptr;      // WSEG_F16M6: fp32 copy of the token embedding for the embedding lookup
-  size_t ckv_es = 0;         // bytes per cross-attention K / V element: es, or 3 (24-bit planes) in the split modes with <= 4 beams
   int kp1, vp, tp;           // conv1 K padded, vocab padded, encoder positions padded
   std::map<std::string, Slot> slots;
   const void *conv1_w, *conv1_b, *conv2_w, *conv2_b, *enc_pos, *enc_ln_g, *enc_ln_b;
@@ -105,7 +104,7 @@ void add_slot(wseg_model* m, const std::string& name, const void** field, size_t
 // The encoder (and the cross-K/V GEMMs behind it) runs over at most ENC_CHUNK windows at a time: its activations (FFN hidden:
 // 10 MB per window in the 16-bit modes, 20 MB in the split modes) then stop growing with the slot count, and a pass of 256
 // windows (128 000 rows: the r01 / r02 headline workload) already fills the chip for tens of rounds.
-static const int ENC_CHUNK = std::max(1, WSEG_KNOB_INT("WSEG_ENC_CHUNK", 256));      // (measurement knob, variant builds)
+constexpr int ENC_CHUNK = 256;
 // Default self-K/V pool of wseg_workspace_bytes: positions per slot, or max_length if that is smaller.
 constexpr int KV_DEFAULT_POSITIONS = 64;
 
@@ -145,12 +144,11 @@ void make_plan(const wseg_model* m, int W, int nb, int L, int kv_units, char* ba
   const size_t Ld = c.dec_layers, Tk = c.enc_positions;
   if (m->mx) {
     // scratch for the activation operands that still arrive as hi | lo rows and are converted in front of their GEMM: the conv1
-    // im2col always; conv2's operand, the attention output and the FFN hidden only when their producer is not one that writes
-    // M6 rows directly (4-column epilogues of the skinny GEMM family on small problems; WSEG_X3_ENC_ATTN != split)
+    // im2col always; conv2's operand and the FFN hidden only when their producer is not one that writes M6 rows directly (4-column
+    // epilogues of the skinny GEMM family on small problems; the encoder attention always writes M6 rows)
     const int dtp = c.dtype, R0 = W * nb;
     const size_t Rp0 = align_up((size_t)R0, 256);
     size_t big = M1p * (size_t)m->kp1;
-    if (!enc_attention_writes_mx(dtp)) big = std::max(big, Mp * d);
     for (int n = 1; n <= We; ++n) {      // an encoder pass runs over 1 .. We windows (refills admit a few at a time)
       const size_t mp = align_up((size_t)n * c.enc_positions, 256);
       if (!gemm_out_is_mx(dtp, n * c.spec_cols, (int)d, m->kp1)) big = std::max(big, mp * 3 * d);
@@ -278,7 +276,7 @@ int run_encoder(wseg_model* m, const float* feats, int W, Plan& p, void* enc_out
     WSEG_TRY(launch_layernorm(gdt, (const float*)p.x, L.ln1_g, L.ln1_b, p.y, M, d, s));
     e = EpiParams();
     e.bias = L.qkv_b; e.q = p.q; e.k = p.k; e.v = p.vt; e.d_model = d; e.t_len = T; e.t_pad = Tp; e.n_heads = H; e.scale = 0.125f;
-    if (m->x3) { e.qkv_mode = x3_enc_attention_mode(); e.qkv_plane = (size_t)W * H * Tp * 64; }
+    if (m->x3) { e.qkv_mode = 2; e.qkv_plane = (size_t)W * H * Tp * 64; }
     e.vt_tiled = enc_attention_vt_tiled(gdt) ? 1 : 0;
     WSEG_TRY(gemm(m, EPI_QKV_ENC, p.y, d, L.qkv_w, d, M, 3 * d, d, e, nullptr, s));
     WSEG_TRY(launch_enc_attention(gdt, p.q, p.k, p.vt, p.y, W, H, T, Tp, d, s));
@@ -421,7 +419,6 @@ extern "C" int wseg_model_create(const wseg_model_config* cfg, wseg_model** out)
   m->x3 = cfg->dtype == WSEG_BF16X3 || cfg->dtype == WSEG_F16X3 || cfg->dtype == WSEG_F16M6;
   m->mx = cfg->dtype == WSEG_F16M6;
   m->sdt = storage_dtype(cfg->dtype);
-  m->ckv_es = m->es;
   m->kp1 = (int)align_up((size_t)3 * cfg->n_mels, 64);
   m->vp = (int)align_up((size_t)cfg->vocab, 128);
   m->tp = (int)align_up((size_t)cfg->enc_positions, 128);
