@@ -231,6 +231,31 @@ int wseg_convert_operand(const void* src_x3_rows, void* dst_m6_rows, int64_t n_r
  * wseg_generate call are kept in the workspace; this copies them out (device to device). */
 int wseg_debug_first_logits(wseg_model* m, void* workspace, float* out, int32_t n_rows, void* stream);
 
+/* Debug/parity tap: logits and decode state of CHOSEN decode steps of a wseg_generate call (tests/test_late_step_logits_gpu.py
+ * compares them with a float64 oracle fed the engine's own row histories).  A step is named by the position its slots feed: the
+ * self-attention of that step sees position + 1 keys, the first generated step is prompt_len - 1, the last one max_length - 2.
+ *   arm     positions[n_steps]: ascending, n_steps <= 16 (0 disarms); out: device buffer of n_steps records, filled in the order of
+ *           `positions`.  Holds for the NEXT wseg_generate call on this model only — the parameters struct does not change — and
+ *           `out` must stay valid until that call's stream work has completed.  Steps the call never reaches write nothing.
+ *   record  for S = min(n_slots, n_windows) slots, nb beams, R = S * nb rows (row = slot * nb + beam; window i sits in slot i),
+ *           L = max_length, V = vocab, back to back:
+ *             float   logits[R][V]    as the LM head wrote them: before suppression / log-softmax, like wseg_debug_first_logits
+ *             int32_t run_seq[R][L]   token history of every row; entries 0 .. position are the tokens fed so far
+ *             int32_t pos[S]          position of every slot
+ *             int32_t idle[S]         1 = the slot was idle (its window had finished) and the step skipped it
+ *             uint8_t anc[R][L]       ancestry: the beam whose cache rows hold position p of the row's history (rounded up to 4 bytes)
+ *           all as they were when the step ran (before its beam / greedy bookkeeping).  wseg_debug_step_snapshot_bytes: bytes of one record.
+ *   result  after the call: *n_taken = records written; *qkv_split (may be NULL) = 1 when the snapshot steps' q | k | v GEMM handed
+ *           split-K partials to the self-attention kernel (which finishes the reduction and appends K / V itself), 0 when the GEMM
+ *           epilogue wrote q and the cache rows, -1 when no snapshot step ran in the decode loop.  WSEG_ERR_STATE unless the call
+ *           was armed, all its windows started together (n_slots >= n_windows) and none was preempted.
+ * A snapshot step is launched eagerly, every other step still replays the step graph; the call computes exactly what it computes
+ * without a snapshot (same kernels, same order).  These entry points were added without moving WSEG_ABI_VERSION: the version
+ * moves when an existing declaration changes its layout or meaning (ABI 3 -> 4 -> 5 above), not when a tap is added. */
+size_t wseg_debug_step_snapshot_bytes(const wseg_model* m, int32_t n_slots, int32_t num_beams, int32_t max_length);
+int wseg_debug_step_snapshot_arm(wseg_model* m, const int32_t* positions, int32_t n_steps, void* out, size_t out_bytes);
+int wseg_debug_step_snapshot_result(const wseg_model* m, int32_t* n_taken, int32_t* qkv_split);
+
 /* Per-stage device time (ms) of the last wseg_generate call on this model, measured with HIP events
  * on the call's stream: [0]=encoder passes, [1]=cross-K/V passes, [2]=everything else (the decode steps),
  * [3]=number of decode steps. */

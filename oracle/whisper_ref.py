@@ -116,8 +116,10 @@ def encoder_forward(sd, cfg, feats, return_hidden=False):
 class Decoder:
     """Incremental decoder with self-attention KV cache; cross K/V computed once per row."""
 
-    def __init__(self, sd, cfg, enc_out):
-        self.sd, self.cfg = sd, cfg
+    def __init__(self, sd, cfg, enc_out, keep_dtype=False):
+        """keep_dtype: step() returns the logits in the dtype of `sd` / `enc_out` (float64 weights and encoder output: a float64
+        reference) instead of casting them to fp32."""
+        self.sd, self.cfg, self.keep_dtype = sd, cfg, keep_dtype
         self.p = "model.decoder."
         self.scale = (cfg.d_model // cfg.heads) ** -0.5
         self.cross = []
@@ -134,7 +136,8 @@ class Decoder:
 
     @torch.no_grad()
     def step(self, tokens):
-        """tokens int64 [R, n] (n = prompt length on the first call, then 1) -> logits fp32 [R, V] of the last position."""
+        """tokens int64 [R, n] (n = prompt length on the first call, then 1) -> logits fp32 [R, V] of the last position
+        (keep_dtype: in the dtype of the weights)."""
         sd, cfg, p = self.sd, self.cfg, self.p
         n = tokens.shape[1]
         x = sd[p + "embed_tokens.weight"][tokens] + sd[p + "embed_positions.weight"][self.pos:self.pos + n][None]
@@ -165,7 +168,8 @@ class Decoder:
             x = r + _lin(y, sd, lp + "fc2")
         self.pos += n
         x = _ln(x[:, -1], sd, p + "layer_norm")
-        return F.linear(x, sd[p + "embed_tokens.weight"]).float()
+        logits = F.linear(x, sd[p + "embed_tokens.weight"])
+        return logits if self.keep_dtype else logits.float()
 
 
 def _process(scores, cur_len, gp):
@@ -308,6 +312,35 @@ def score_sequence(sd, cfg, feats, gp, tokens):
         total += float(lp[0, t])
         inp = torch.tensor([[t]], dtype=torch.int64)
     return total / (len(gen) ** gp.length_penalty)
+
+
+class TeacherForcer:
+    """Encoder output and cross-attention K / V of ONE window in `dtype`, kept for any number of teacher_forced_logits-style passes."""
+
+    @torch.no_grad()
+    def __init__(self, sd, cfg, feats, dtype=torch.float64):
+        self.sd = {k: v.to(dtype) for k, v in sd.items()}
+        self.cfg = cfg
+        self.enc = encoder_forward(self.sd, cfg, torch.as_tensor(feats).to(dtype).reshape(1, cfg.n_mels, -1))
+        self.proto = Decoder(self.sd, cfg, self.enc, keep_dtype=True)
+
+    @torch.no_grad()
+    def logits(self, histories):
+        hist = torch.as_tensor(histories, dtype=torch.int64)
+        assert hist.dim() == 2 and 1 <= hist.shape[1] <= self.cfg.max_target_positions
+        dec = Decoder.__new__(Decoder)      # a fresh self-attention cache on the shared cross K / V (they broadcast over the rows)
+        dec.__dict__.update(self.proto.__dict__)
+        dec.self_kv, dec.pos = [None] * self.cfg.decoder_layers, 0
+        return dec.step(hist)
+
+
+def teacher_forced_logits(sd, cfg, feats, histories, dtype=torch.float64):
+    """Logits [rows, V] (in `dtype`, float64 by default) of the LAST position of given row histories of ONE window, teacher-forced
+    through encoder + decoder as one causal pass in `dtype`: no decoding decisions, no cache bookkeeping, no beam reordering.
+    feats [80, 1000] or [1, 80, 1000]; histories: token ids [rows, n], prompt included (the rows are independent).
+    The float64 result is the reference for logits of late decode steps: the fp32 oracle is itself 2e-5 .. 4e-5 away from it on the
+    fixture models, more than the split-precision modes are.  (TeacherForcer keeps the window's encoder output between calls.)"""
+    return TeacherForcer(sd, cfg, feats, dtype).logits(histories)
 
 
 def canonical(tokens, prompt_len, eos_token_id, prompt=None):

@@ -150,3 +150,44 @@ def test_third_fixture_encoder_logits_and_rows(golden_dir):
     for run in sweep[0:4] + sweep[600:604] + sweep6[0:4] + sweep6[700:702] + sweep7[300:302]:
         got = seg.segment(GI.tiny_recording(run["seed"], run["n_windows"], variant="tiny3"), TM.SR, **run["kwargs"])
         assert got == run["expected"], (run["seed"], run["kwargs"])
+
+
+# ---- the float64 teacher-forced reference (tests/test_late_step_logits_gpu.py) ---------------------------------------------------------
+def test_teacher_forced_logits_match_the_incremental_oracle(tiny2):
+    """teacher_forced_logits runs given histories as ONE causal pass; in fp32 it must agree with what the pinned incremental decoder
+    gives where the two overlap: the first-step logits of generate(), and the per-token log-probabilities score_sequence() sums up at
+    later positions.  Bound: two fp32 summation orders of the same network — each is at most 4.0e-5 away from the float64 result on this
+    model (logit scale 19) — so 1e-4; the float64 result itself lies within the same distance of both."""
+    sd, rc, _, _ = tiny2
+    audio = GI.tiny_recording(5000, 3, variant="tiny2")
+    feats = torch.from_numpy(np.stack([s[2] for s in F.sliced_audio_features(audio, TM.SR, 0, TM.STS, 1)]))
+    gp = W.GenParams(prompt=TM.PROMPT, eos_token_id=TM.EOT, pad_token_id=TM.EOT, max_length=24, num_beams=1,
+                     suppress_tokens=TM.SUPPRESS, begin_suppress_tokens=TM.BEGIN_SUPPRESS)
+    seqs, first = W.generate(sd, rc, feats, gp, return_first_logits=True)
+    P = len(TM.PROMPT)
+    for i in range(feats.shape[0]):
+        got32 = W.teacher_forced_logits(sd, rc, feats[i], [TM.PROMPT], dtype=torch.float32)
+        got64 = W.teacher_forced_logits(sd, rc, feats[i], [TM.PROMPT])
+        assert got32.dtype == torch.float32 and got64.dtype == torch.float64 and got64.shape == (1, rc.vocab_size)
+        assert (got32[0] - first[i]).abs().max().item() <= 1e-4
+        assert (got64[0] - first[i].double()).abs().max().item() <= 1e-4
+    # later positions: score_sequence == mean of log_softmax(teacher-forced logits)[next token] over the generated tokens
+    toks = W.canonical(seqs[0].tolist(), P, TM.EOT, TM.PROMPT)
+    full = list(TM.PROMPT) + toks
+    assert len(toks) >= 6
+    want = W.score_sequence(sd, rc, feats[0:1], gp, full)
+    for dtype in (torch.float32, torch.float64):
+        total = 0.0
+        for k in range(len(toks)):
+            # two rows per call: rows are independent, the second one is a shorter history padded by repeating itself
+            lg = W.teacher_forced_logits(sd, rc, feats[0:1], [full[:P + k], full[:P + k]], dtype=dtype)
+            assert torch.equal(lg[0], lg[1])
+            total += float(torch.log_softmax(lg[0].double(), dim=-1)[toks[k]])
+        assert abs(total / len(toks) - want) <= 1e-4, (dtype, total / len(toks), want)
+    # the decoder's fp32 behaviour is unchanged: keep_dtype only matters for non-fp32 weights
+    dec = W.Decoder(sd, rc, W.encoder_forward(sd, rc, feats[0:1]))
+    assert dec.step(torch.tensor([TM.PROMPT])).dtype == torch.float32
+    sd64 = {k: v.double() for k, v in sd.items()}
+    enc64 = W.encoder_forward(sd64, rc, feats[0:1].double())
+    assert W.Decoder(sd64, rc, enc64).step(torch.tensor([TM.PROMPT])).dtype == torch.float32
+    assert W.Decoder(sd64, rc, enc64, keep_dtype=True).step(torch.tensor([TM.PROMPT])).dtype == torch.float64

@@ -70,6 +70,28 @@ struct Sched {
   std::vector<unsigned char> step_graph_key;
 };
 
+// wseg_debug_step_snapshot_arm: the decode steps (by position) whose logits and decode state the next wseg_generate call copies out
+constexpr int MAX_SNAP_STEPS = 16;
+struct StepSnap {
+  int n = 0;
+  int pos[MAX_SNAP_STEPS] = {};
+  char* out = nullptr;
+  size_t bytes = 0;
+};
+// one record (include/wseg.h): logits [R][V] f32 | run_seq [R][L] i32 | pos [S] i32 | idle [S] i32 | anc [R][L] u8, padded to 4 bytes
+struct SnapLayout { size_t logits, seq, pos, idle, anc, total; };
+SnapLayout snap_layout(int S, int nb, int L, int V) {
+  const size_t R = (size_t)S * nb;
+  SnapLayout l;
+  l.logits = 0;
+  l.seq = l.logits + R * V * 4;
+  l.pos = l.seq + R * L * 4;
+  l.idle = l.pos + (size_t)S * 4;
+  l.anc = l.idle + (size_t)S * 4;
+  l.total = l.anc + align_up(R * L, 4);
+  return l;
+}
+
 }  // namespace
 
 struct wseg_model {
@@ -91,6 +113,9 @@ struct wseg_model {
   bool timing_valid = false;
   int last_W = 0, last_nb = 0, last_L = 0, last_units = 0;
   bool first_logits_valid = false;
+  StepSnap snap_req;                 // armed for the next wseg_generate call
+  int snap_taken = -1;               // last call: records written (-1: none were asked for, or its windows did not start together / were preempted)
+  int snap_qkv_split = -1;           // last call's snapshot steps: did the q | k | v GEMM hand split-K partials to the attention kernel?
   wseg_generate_stats stats = {};
 };
 
@@ -347,6 +372,7 @@ int run_decoder_step(wseg_model* m, DecPlan& p, char* mxa, bool want_logits, hip
       g.splitk_ws = (float*)p.splitk; g.splitk_ws_bytes = p.splitk_bytes;
       PartialInfo pi; bool ok = false;
       WSEG_TRY(launch_gemm_partial(gdt, g, &pi, &ok, s));
+      if (!pp) m->snap_qkv_split = ok ? 1 : 0;
       if (pp) {
         if (!ok) {      // the step's plan does not split q | k | v: fp32 rows of an un-split GEMM (bias added by the attention kernel)
           if ((size_t)R * 3 * d > (size_t)p.row_cap * m->vp) { set_error("prompt pass: %d rows of q | k | v do not fit the logits buffer", R); return WSEG_ERR_STATE; }
@@ -655,6 +681,26 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
   bool first_admission = true;
   bool snap_ok = false;                                // did every window of the call start together (first-logits snapshot)?
   m->first_logits_valid = false;
+  // step snapshots (wseg_debug_step_snapshot_arm): armed for this call only
+  const StepSnap sn = m->snap_req;
+  m->snap_req = StepSnap();
+  m->snap_taken = -1;
+  m->snap_qkv_split = -1;
+  const SnapLayout sl_ = snap_layout(S, nb, L, c.vocab);
+  if (sn.n > 0 && sn.bytes < (size_t)sn.n * sl_.total) {
+    set_error("step snapshot: %d records of %zu bytes do not fit the %zu-byte buffer", sn.n, sl_.total, sn.bytes);
+    return WSEG_ERR_INVALID;
+  }
+  int snap_taken = 0;
+  auto snap_index = [&](int pos) -> int { for (int i = 0; i < sn.n; ++i) if (sn.pos[i] == pos) return i; return -1; };
+  // the decode state a step runs on, as it is before the step's bookkeeping kernels rewrite it
+  auto snap_state = [&](char* rec, hipStream_t qs) -> int {
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.seq, st.run_seq, (size_t)S * nb * L * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.pos, st.pos, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.idle, st.done, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.anc, st.anc, (size_t)S * nb * L, hipMemcpyDeviceToDevice, qs));
+    return WSEG_OK;
+  };
 
   // encoder + cross-K/V of the consecutive windows [w0, w0 + n) into the slots listed at q.adm_slots + off (device)
   auto encode_run = [&](int w0, int n, int off) -> int {
@@ -732,6 +778,14 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
               WSEG_HIP_CHECK(hipMemcpy2DAsync(q.first_logits + ((size_t)c0 * nb + j) * m->vp * 4, (size_t)nb * m->vp * 4, q.logits, (size_t)m->vp * 4,
                                               (size_t)m->vp * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
             if (c0 + nc == n) m->first_logits_valid = true;
+            const int si = snap_index(P - 1);
+            if (si >= 0) {      // the same rows as a step snapshot record
+              char* rec = sn.out + (size_t)si * sl_.total;
+              for (int j = 0; j < nb; ++j)
+                WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + sl_.logits + ((size_t)c0 * nb + j) * c.vocab * 4, (size_t)nb * c.vocab * 4, q.logits,
+                                                (size_t)m->vp * 4, (size_t)c.vocab * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
+              if (c0 == 0) { WSEG_TRY(snap_state(rec, s)); ++snap_taken; }
+            }
           }
           WSEG_TRY(launch_row_topk(st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, s, q.adm_slots + c0, nc));
           if (nb == 1) WSEG_TRY(launch_greedy_step(st, s, q.adm_slots + c0, nc));
@@ -790,10 +844,15 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
   };
 
   // One decode step of every active slot: decoder layers, LM head, candidates, bookkeeping (which also advances the slot).
-  auto enqueue_step = [&](bool snapshot_logits, hipStream_t qs) -> int {
+  auto enqueue_step = [&](bool snapshot_logits, hipStream_t qs, char* rec = nullptr) -> int {
     WSEG_TRY(run_decoder_step(m, q, p.mxa, true, qs));
     if (snapshot_logits)
       WSEG_HIP_CHECK(hipMemcpyAsync(q.first_logits, q.logits, (size_t)S * nb * m->vp * 4, hipMemcpyDeviceToDevice, qs));
+    if (rec) {
+      WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + sl_.logits, (size_t)c.vocab * 4, q.logits, (size_t)m->vp * 4, (size_t)c.vocab * 4, (size_t)S * nb,
+                                      hipMemcpyDeviceToDevice, qs));
+      WSEG_TRY(snap_state(rec, qs));
+    }
     WSEG_TRY(launch_row_topk(st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, qs));
     if (nb == 1) WSEG_TRY(launch_greedy_step(st, qs));
     else WSEG_TRY(launch_beam_step(st, qs));
@@ -816,6 +875,9 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
     // (wseg_debug_first_logits); every other step replays the graph
     const bool snap = !merged && t == P - 1 - POS0 && snap_ok && stats.n_preemptions == 0;
     if (snap) m->first_logits_valid = true;
+    // ... and so is a step named by wseg_debug_step_snapshot_arm (every slot is at position t + POS0: they started together)
+    const int si = snap_ok && stats.n_preemptions == 0 ? snap_index(t + POS0) : -1;
+    if (si >= 0) { ++snap_taken; return enqueue_step(snap, s, sn.out + (size_t)si * sl_.total); }
     if (snap || !use_graph) return enqueue_step(snap, s);
     if (!ln.step_graph || ln.step_graph_key != key) {
       if (ln.step_graph) { (void)hipGraphExecDestroy(ln.step_graph); ln.step_graph = nullptr; }
@@ -916,6 +978,7 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
   while (consumed < t) WSEG_TRY(consume_status(consumed++));
   if (in_flight != 0 || !queue.empty()) { set_error("scheduler ended with %d windows in flight, %d queued", in_flight, (int)queue.size()); return WSEG_ERR_STATE; }
   stats.n_steps = t;
+  if (sn.n > 0 && snap_ok && stats.n_preemptions == 0) m->snap_taken = snap_taken;
   return WSEG_OK;
 }
 
@@ -979,6 +1042,34 @@ extern "C" int wseg_debug_first_logits(wseg_model* m, void* workspace, float* ou
   make_plan(m, m->last_W, m->last_nb, m->last_L, m->last_units, aligned_base(workspace), p);
   WSEG_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)m->cfg.vocab * 4, p.dec.first_logits, (size_t)m->vp * 4,
                                   (size_t)m->cfg.vocab * 4, (size_t)n_rows, hipMemcpyDeviceToDevice, s));
+  return WSEG_OK;
+}
+
+extern "C" size_t wseg_debug_step_snapshot_bytes(const wseg_model* m, int32_t n_slots, int32_t num_beams, int32_t max_length) {
+  if (!m || n_slots <= 0 || num_beams < 1 || num_beams > MAX_BEAMS || max_length <= 0) return 0;
+  return snap_layout(n_slots, num_beams, max_length, m->cfg.vocab).total;
+}
+
+extern "C" int wseg_debug_step_snapshot_arm(wseg_model* m, const int32_t* positions, int32_t n_steps, void* out, size_t out_bytes) {
+  if (!m) { set_error("wseg_debug_step_snapshot_arm: bad argument"); return WSEG_ERR_INVALID; }
+  m->snap_req = StepSnap();
+  if (n_steps == 0) return WSEG_OK;      // disarm
+  if (!positions || !out || n_steps < 0 || n_steps > MAX_SNAP_STEPS) { set_error("wseg_debug_step_snapshot_arm: bad argument (1..%d steps)", MAX_SNAP_STEPS); return WSEG_ERR_INVALID; }
+  for (int i = 0; i < n_steps; ++i)
+    if (positions[i] < 0 || (i > 0 && positions[i] <= positions[i - 1])) { set_error("wseg_debug_step_snapshot_arm: positions must be ascending and >= 0"); return WSEG_ERR_INVALID; }
+  StepSnap r;
+  r.n = n_steps;
+  for (int i = 0; i < n_steps; ++i) r.pos[i] = positions[i];
+  r.out = (char*)out; r.bytes = out_bytes;
+  m->snap_req = r;
+  return WSEG_OK;
+}
+
+extern "C" int wseg_debug_step_snapshot_result(const wseg_model* m, int32_t* n_taken, int32_t* qkv_split) {
+  if (!m || !n_taken) { set_error("wseg_debug_step_snapshot_result: bad argument"); return WSEG_ERR_INVALID; }
+  if (m->snap_taken < 0) { set_error("no wseg_generate call with a step snapshot (it must be armed, and all windows must have started together without preemption)"); return WSEG_ERR_STATE; }
+  *n_taken = m->snap_taken;
+  if (qkv_split) *qkv_split = m->snap_qkv_split;
   return WSEG_OK;
 }
 

@@ -407,7 +407,8 @@ class Engine:
 
     def generate(self, feats, prompt, eos_token_id, pad_token_id, max_length=448, num_beams=4, length_penalty=1.0,
                  suppress_tokens=(), begin_suppress_tokens=(), return_first_logits=False, n_slots=None, refill_min=0,
-                 lookahead=0, window_max_length=None, encoder_output=None, top_k=1, top_p=1.0, seed=0, kv_positions=0):
+                 lookahead=0, window_max_length=None, encoder_output=None, top_k=1, top_p=1.0, seed=0, kv_positions=0,
+                 snapshot_steps=None):
         """Greedy / beam-search decode of ALL windows of `feats` [N, 80, 1000] through `n_slots` window slots with
         in-flight refill (a finished window's slot goes to the next queued window; wseg_generate; see pick_slots for the
         default slot count).  `top_k` in 2..16 with
@@ -415,6 +416,11 @@ class Engine:
         `kv_positions`: average self-attention K/V positions per slot to provision in the paged pool (0: min(max_length, 64);
         >= max_length: every slot can reach max_length at once); when the pool runs short the engine preempts and re-decodes
         the youngest window (last_stats()["n_preemptions"]).
+        `snapshot_steps` (debug, wseg_debug_step_snapshot_*): up to 16 positions; the logits and the decode state of the steps that
+        feed them (a step at position p attends to p + 1 keys; the first generated step is len(prompt) - 1) are appended to the result
+        as a dict of device tensors: positions [n], logits [n, rows, vocab], run_seq [n, rows, max_length], pos [n, slots],
+        idle [n, slots], anc [n, rows, max_length] (rows = windows * beams, row = window * beams + beam) and qkv_split (which writer
+        of the self-attention K / V ran, see include/wseg.h).  Needs every window to start together, like return_first_logits.
         Returns (tokens int32 [N, max_length] on device, lengths int32 [N])."""
         feats = feats.to(device=self.device, dtype=torch.float32).contiguous()
         W = feats.shape[0]
@@ -471,17 +477,45 @@ class Engine:
             gp.encoder_output = enc.data_ptr()
         tokens = torch.empty((W, max_length), dtype=torch.int32, device=self.device)
         lengths = torch.empty((W,), dtype=torch.int32, device=self.device)
+        snap_buf = None
+        if snapshot_steps is not None:
+            if W > slots:
+                raise ValueError("snapshot_steps needs every window to start together (n_slots >= windows)")
+            snap_pos = sorted({int(p) for p in snapshot_steps})
+            rec = int(self.lib.wseg_debug_step_snapshot_bytes(self.handle, W, int(num_beams), max_length))
+            snap_buf = torch.zeros((len(snap_pos), rec), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.wseg_debug_step_snapshot_arm(self.handle, (C.c_int32 * len(snap_pos))(*snap_pos), len(snap_pos),
+                                                             snap_buf.data_ptr(), snap_buf.numel()))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.wseg_generate(self.handle, feats.data_ptr(), W, C.byref(gp), ws.data_ptr(), ws.numel(),
                                               tokens.data_ptr(), lengths.data_ptr(), _lib.stream_ptr()))
+            fl = None
             if return_first_logits:
                 if W > slots:
                     raise ValueError("return_first_logits needs every window to start together (n_slots >= windows)")
                 fl = torch.empty((W * num_beams, self.geo["vocab"]), dtype=torch.float32, device=self.device)
                 _lib.check(self.lib.wseg_debug_first_logits(self.handle, ws.data_ptr(), fl.data_ptr(), W * num_beams,
                                                             _lib.stream_ptr()))
-                return tokens, lengths, fl
-        return tokens, lengths
+            out = (tokens, lengths, fl) if return_first_logits else (tokens, lengths)
+            if snap_buf is not None:
+                out = out + (self._read_snapshots(snap_buf, snap_pos, W, int(num_beams), max_length),)
+        return out
+
+    def _read_snapshots(self, buf, positions, S, nb, L):
+        """The records of wseg_debug_step_snapshot_arm (layout: include/wseg.h) as tensors."""
+        taken, split = C.c_int32(0), C.c_int32(0)
+        _lib.check(self.lib.wseg_debug_step_snapshot_result(self.handle, C.byref(taken), C.byref(split)))
+        if taken.value != len(positions):
+            raise _lib.WsegError(f"{taken.value} of {len(positions)} snapshot steps ran (positions {positions}, max_length {L})")
+        n, R, V = len(positions), S * nb, self.geo["vocab"]
+        fields, at = {}, 0
+        for name, count, dt in (("logits", R * V, torch.float32), ("run_seq", R * L, torch.int32), ("pos", S, torch.int32),
+                                ("idle", S, torch.int32), ("anc", R * L, torch.uint8)):
+            nbytes = count * torch.empty((), dtype=dt).element_size()
+            fields[name] = buf[:, at:at + nbytes].contiguous().view(dt)
+            at += nbytes
+        return {"positions": torch.tensor(positions), "logits": fields["logits"].view(n, R, V), "run_seq": fields["run_seq"].view(n, R, L),
+                "pos": fields["pos"], "idle": fields["idle"], "anc": fields["anc"].view(n, R, L), "qkv_split": split.value}
 
     def last_stats(self):
         """Scheduler statistics of the last generate call: dict(n_windows, n_slots, n_steps, n_admissions,
