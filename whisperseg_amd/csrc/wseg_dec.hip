@@ -127,7 +127,7 @@ template <typename T>
 __device__ __forceinline__ float reduce1(const PartialInfo& pi, int row, int col, const T* bias) {
   const float* pp = pi.part + (size_t)row * pi.n + col;
   const size_t zs = (size_t)pi.m_pad * pi.n;
-  float t[16];                                           // plan_skinny: at most 16 splits
+  float t[16];                                           // plan_stream (wseg_gemm.hip): at most 16 splits
 #pragma unroll
   for (int z = 0; z < 16; ++z) t[z] = pp[(size_t)min(z, pi.splits - 1) * zs];
   float v = 0.f;

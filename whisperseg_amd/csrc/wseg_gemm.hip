@@ -10,9 +10,9 @@
 //   gemm_h16_persist_kernel  persistent 128x128 tiles (large GEMMs where the 256x256 tile does not qualify)
 //   gemm_h16_pp_kernel       persistent 256x256 ping-pong tiles (two 4-wave row groups), also as S split-K copies for decoder rows
 //   splitk_reduce*_kernel    sum the split-K planes and apply the epilogue (4 / 8 columns, or residual + LayerNorm)
-// launch_h16 / gemm_partial_t / gemm_resid_ln_t pick among them by shape.
+// WHICH of them a product gets is decided in one place, plan_h16 (H16Plan: family, tile size, split-K range — what fixes the summation
+// order of an output element); launch_gemm / launch_gemm_partial / launch_gemm_resid_ln switch on its answer and gemm_out_is_mx reads it.
 #include <stdlib.h>
-#include <string.h>
 #include <mutex>
 #include <type_traits>
 
@@ -77,12 +77,9 @@ __device__ __forceinline__ MxFrag ld_mx_frag(const void* block16, const MxOff& m
   f.v = (mx_i32x8){(int)p0.x, (int)p0.y, (int)p0.z, (int)p0.w, (int)p1.x, (int)p1.y, (int)p1.z, (int)p1.w};
   return f;
 }
-// The same for the ping-pong kernel, which runs at the 256-register cap: the second read as ds_read_b96 (codes 4, 5 + scale: the
-// chunk's padding dword never takes a register), 7 registers per fragment.  Opaque to the compiler's waitcnt bookkeeping: the
-// caller retires the reads with its own s_waitcnt lgkmcnt(0) (the L part of a phase ends with one anyway).
 // The ping-pong kernel runs at the 256-register cap, and the MFMA builtin wants 8-register operands (two of them dead for fp6):
-// there the fragment is exactly what the instruction reads — a 6-register tuple of codes + one scale register (b128 + b96 LDS
-// reads: the chunk's padding dword never takes a register) — and the instruction is issued through inline assembly.  Its
+// there the fragment is exactly what the instruction reads — a 6-register tuple of codes + one scale register (b128 + b64 + b32 LDS
+// reads, see ld_mx_frag7: the chunk's padding dword never takes a register) — and the instruction is issued through inline assembly.  Its
 // accumulator is written by builtin MFMAs and asm MFMAs alternately, always with a barrier and a round of LDS reads in between.
 typedef unsigned mx_u2 __attribute__((ext_vector_type(2)));
 typedef unsigned mx_u3 __attribute__((ext_vector_type(3)));
@@ -1061,110 +1058,6 @@ __global__ __launch_bounds__(256) void splitk_reduce8_kernel(const float* __rest
   epi_apply8<EPI, T>(ep, m, n0, v);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Live profiler of the dominant kernel (wseg_profile_begin / wseg_profile_end)
-// ------------------------------------------------------------------------------------------------
-// Process-wide and meant for ONE measuring thread (bench.py's roofline leg); a mutex keeps concurrent device threads from
-// corrupting the event pool if a profile is requested while several devices run.
-struct GemmProfiler {
-  std::mutex mu;
-  bool on = false;
-  std::vector<hipEvent_t> pool;
-  size_t used = 0;
-  std::vector<double> flops;
-  hipEvent_t get() {
-    if (used == pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); pool.push_back(e); }
-    return pool[used++];
-  }
-};
-static GemmProfiler g_prof;
-
-// ------------------------------------------------------------------------------------------------
-// Launchers
-// ------------------------------------------------------------------------------------------------
-// CU count of the CURRENT device, cached per device (thread-per-device mode drives several devices from one process).
-int device_cu_count() {
-  static int cached[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cached[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
-#define WSEG_TRY_(expr) do { int _s = (expr); if (_s != WSEG_OK) return _s; } while (0)
-
-// skinny family (decoder steps, small encoders): BN = 64, BM in {32, 64, 128}; K is split across workgroups until
-// ~256+ of them stream the weight matrix.  Partials are reduced (in a fixed order) by a second kernel that
-// applies the epilogue (or the fused residual + LayerNorm).
-struct SkinnyPlan { int bm, bn, mt, m_pad, splits, k_len; };
-
-// The rows a launch is PLANNED for (GemmArgs::plan_m): kernel family, tile size and split-K ranges follow them, the grid follows g.M.
-static inline int plan_rows(const GemmArgs& g) { return g.plan_m > 0 ? g.plan_m : g.M; }
-static inline GemmArgs plan_view(const GemmArgs& g) { GemmArgs p = g; p.M = plan_rows(g); p.plan_m = 0; return p; }
-
-static SkinnyPlan plan_skinny(const GemmArgs& g0, bool pairs = false) {      // pairs: M6 rows — a K range is whole (hi, MX) tile pairs
-  const GemmArgs g = plan_view(g0);
-  SkinnyPlan sp;
-  // largest row tile that still yields >= 160 workgroups without splitting K; otherwise 128 rows + split-K
-  sp.bm = g.M <= 32 ? 32 : (g.M <= 64 ? 64 : 128);
-  if (g.M > 64) {
-    const int nt = g.N / 64;
-    if (nt * cdiv(g.M, 128) < 160 && nt * cdiv(g.M, 64) >= 160) sp.bm = 64;
-  }
-  sp.bn = 64;
-  sp.mt = cdiv(g.M, sp.bm);
-  sp.m_pad = sp.mt * sp.bm;
-  const int blocks = (g.N / sp.bn) * sp.mt;
-  sp.splits = 1;
-  if (g.splitk_ws) {
-    // split K (in whole 64-wide tiles, >= 2 tiles per split) until ~256 workgroups stream the weights
-    const int nk = g.K / 64;
-    for (int cand = 2; cand <= 16 && blocks * sp.splits < 256; ++cand) {
-      if (nk % cand || nk / cand < 2 || (pairs && (nk / cand) % 2)) continue;
-      if ((size_t)cand * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) break;
-      sp.splits = cand;
-    }
-  }
-  sp.k_len = g.K / sp.splits;
-  sp.mt = cdiv(g0.M, sp.bm);      // the grid and the partial planes cover the rows actually launched
-  sp.m_pad = sp.mt * sp.bm;
-  return sp;
-}
-
-// fp32 partial sums [splits][m_pad][N] into g.splitk_ws (valid for splits == 1 too)
-template <typename T>
-static int launch_skinny_partial(const GemmArgs& g, const SkinnyPlan& sp, hipStream_t s) {
-  typedef typename IO<T>::H HT;
-  const HT* A = (const HT*)g.A;
-  const HT* W = (const HT*)g.W;
-  if (!g.splitk_ws || (size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) {
-    set_error("split-K workspace missing or too small");
-    return WSEG_ERR_STATE;
-  }
-  dim3 grid(g.N / sp.bn, sp.mt, sp.splits);
-  // LDS ring depth: 2 stages.  Measured (large, 120 windows): 6-8 K tiles in flight with one workgroup per CU is 1.7x
-  // SLOWER than 3-4 stages at two workgroups per CU, and 2 stages (3-5 workgroups per CU) is another 2-3 % faster at every
-  // batch size — these kernels want co-resident workgroups to cover their barriers, not more bytes in flight each.
-  // Round 2, at 1024 rows (profiles/README.md, "decode GEMM experiments"): 3 / 4 stages 12.8 / 16.7 us against 11.1 us;
-  // 128x128 tiles (split 4) 13.6 us; no split with 128x128 tiles and 3 stages 24 us; register staging (global -> VGPR ->
-  // ds_write, one barrier per K tile) 35.8 us; dropping the loads OR the MFMAs from the loop changes nothing (11.3 / 9.8
-  // us): a K tile costs ~0.6 us of serialised issue -> land -> barrier -> fragment reads -> MFMA -> barrier per workgroup,
-  // while a bare LDS-DMA stream of the same L2-resident data runs at 123 GB/s per CU (tools/probes/l2fill_probe.hip).
-#define WSEG_SKINNY_P(BM_, WM_, WN_)                                                                                     \
-  hipLaunchKernelGGL((gemm_h16_kernel<T, BM_, 64, WM_, WN_, EPI_STORE, true, 2>), grid, dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, \
-                     g.N, sp.k_len, g.ep, g.splitk_ws, sp.m_pad, 0)
-  if (sp.bm == 32) WSEG_SKINNY_P(32, 1, 4);
-  else if (sp.bm == 64) WSEG_SKINNY_P(64, 1, 4);
-  else WSEG_SKINNY_P(128, 2, 2);
-#undef WSEG_SKINNY_P
-  WSEG_LAUNCH_CHECK();
-  return WSEG_OK;
-}
-
 // x[m][:] += bias + sum_z part[z][m][:]  (x is the fp32 residual stream), then y[m][:] = LayerNorm(x[m][:]) in the model dtype.
 // One workgroup per row, one 8-element chunk per thread (d <= 2048), all split partials loaded up front.
 template <typename T>
@@ -1222,6 +1115,81 @@ __global__ __launch_bounds__(256) void splitk_reduce_resid_ln_kernel(const float
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Live profiler of the dominant kernel (wseg_profile_begin / wseg_profile_end)
+// ------------------------------------------------------------------------------------------------
+// Process-wide and meant for ONE measuring thread (bench.py's roofline leg); a mutex keeps concurrent device threads from
+// corrupting the event pool if a profile is requested while several devices run.
+struct GemmProfiler {
+  std::mutex mu;
+  bool on = false;
+  std::vector<hipEvent_t> pool;
+  size_t used = 0;
+  std::vector<double> flops;
+  hipEvent_t get() {
+    if (used == pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); pool.push_back(e); }
+    return pool[used++];
+  }
+};
+static GemmProfiler g_prof;
+
+// ------------------------------------------------------------------------------------------------
+// Launchers
+// ------------------------------------------------------------------------------------------------
+// CU count of the CURRENT device, cached per device (thread-per-device mode drives several devices from one process).
+int device_cu_count() {
+  static int cached[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cached[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
+#define WSEG_TRY_(expr) do { int _s = (expr); if (_s != WSEG_OK) return _s; } while (0)
+
+// ------------------------------------------------------------------------------------------------
+// The launch plan: WHICH kernel family, tile size and split-K range a product gets.  It fixes the summation order of every output
+// element, so it is computed in one place — plan_h16 — from the rows a launch is PLANNED for (GemmArgs::plan_m); only the grid and
+// the partial planes (mt, m_pad) follow the rows actually launched.  The launchers below switch on the plan and decide nothing.
+// ------------------------------------------------------------------------------------------------
+struct H16Plan {
+  enum Family {
+    NONE,                  // not served (USE_EPILOGUE: an error; the other uses: the caller falls back to launch_gemm)
+    PP,                    // persistent 256x256 ping-pong tiles
+    PP_WITH_SPLITK_TAIL,   // one round of them over the first n_main columns, the remaining columns as PP_SPLITK + 8-column reduction
+    PERSIST128,            // persistent 128x128 tiles
+    TILE128,               // one workgroup per 128x128 tile
+    PP_SPLITK,             // `splits` copies of the 256x256 tile grid, each 1 / splits of the K tiles into an fp32 plane [z][M][N]
+    STREAM,                // bm x 64 stream tiles with the epilogue in the kernel
+    STREAM_SPLITK          // bm x 64 stream tiles into fp32 planes [splits][m_pad][N] (splits may be 1), epilogue in the reduction
+  } family = NONE;
+  int bm = 0;              // STREAM*: 32 / 64 / 128
+  int splits = 1;          // PP_SPLITK / the tail / STREAM_SPLITK
+  int k_len = 0;           // STREAM*: K words per split
+  int mt = 0, m_pad = 0;   // STREAM*: row tiles and padded rows of the launch (PP_SPLITK: m_pad = M, the row stride of its planes)
+  int n_main = 0;          // PP_WITH_SPLITK_TAIL: columns of the un-split launch
+  bool out_is_mx = false;  // M6 EPI_STORE / EPI_GELU: the rows leave as M6 rows (else hi | lo rows)
+};
+enum PlanUse { USE_EPILOGUE, USE_PARTIAL, USE_RESID_LN };      // who consumes the product: launch_gemm / launch_gemm_partial / launch_gemm_resid_ln
+
+// The rows a launch is PLANNED for (GemmArgs::plan_m): kernel family, tile size and split-K ranges follow them, the grid follows g.M.
+static inline int plan_rows(const GemmArgs& g) { return g.plan_m > 0 ? g.plan_m : g.M; }
+
+// Split-precision modes: the caller's K / lda / ldw are LOGICAL; the kernels (and the plan) see rows of 2K 16-bit words.
+template <typename T> static GemmArgs kernel_view(const GemmArgs& g0) {
+  GemmArgs g = g0;
+  if (IO<T>::split) { g.K *= 2; g.lda *= 2; g.ldw *= 2; }
+  return g;
+}
+
+template <typename T> static bool h16_tiles_ok(const GemmArgs& g, PlanUse use) {
+  return !(g.K % 64 || g.N % 64 || (use == USE_EPILOGUE && IsMx<T>::v && g.K % 128));
+}
+
 // Large-tile kernels (128x128 / 256x256 output tiles, no split-K) or the weight-stream family (64-column tiles, split-K)?
 // Decoder-step GEMMs sit at the border.  Measured on the whole decode step (large, 4 beams): at 1024 rows fc1 (N = 5120,
 // 320 blocks of 128x128) is better in the stream family (decode step 10.71 -> 10.23 ms); at 1536 rows q|k|v (360 blocks)
@@ -1231,203 +1199,48 @@ static bool big_tile_path(const GemmArgs& g) {
   return pm > 128 && g.N % 128 == 0 && (long)cdiv(pm, 128) * (g.N / 128) >= 340;
 }
 
-// Split-precision modes: the caller's K / lda / ldw are LOGICAL; the kernels see rows of 2K 16-bit words.
-template <typename T> static GemmArgs kernel_view(const GemmArgs& g0) {
-  GemmArgs g = g0;
-  if (IO<T>::split) { g.K *= 2; g.lda *= 2; g.ldw *= 2; }
-  return g;
-}
-
-template <typename T> static int launch_pp_splitk(const GemmArgs& g, int S, hipStream_t s);
-template <typename T> static int pp_splitk_plan(const GemmArgs& g);
-
-static bool skinny_split_writes_mx(int N) { return N % 32 == 0; }
-
-template <int EPI, typename T>
-static int launch_h16(const GemmArgs& g0, hipStream_t s) {
-  typedef typename IO<T>::H HT;
-  const GemmArgs g = kernel_view<T>(g0);
-  const HT* A = (const HT*)g.A;
-  const HT* W = (const HT*)g.W;
-  if (g.K % 64 || g.N % 64 || (IsMx<T>::v && g.K % 128)) { set_error("gemm h16: K %d / N %d not tile multiples", g.K, g.N); return WSEG_ERR_INVALID; }
-  if (big_tile_path(g)) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_prof.on) {
-      std::lock_guard<std::mutex> lk(g_prof.mu);
-      e0 = g_prof.get(); e1 = g_prof.get(); g_prof.flops.push_back(2.0 * g0.M * g0.N * g0.K); (void)hipEventRecord(e0, s);
-    }
-    // m-tiles per tile group of the persistent order: the 32 tiles in flight on one XCD then span ~4 activation tiles x 8
-    // weight tiles, the smallest operand footprint for 32 tiles (a + b = 12 operand tiles; 2-row groups re-stream the
-    // whole weight matrix per tile pair: PMC FETCH_SIZE 2-3x the algorithmic bytes, profiles/).  Measured at 256
-    // windows: 4 beats 2 by 2-8 % on the K = 1280 shapes, 6 and 8 lose on K = 5120.
-#if defined(WSEG_STAMPS) && WSEG_STAMPS == 4
-    static const int group_m = 4 | (getenv("WSEG_PP_SOLO") ? 0x100 : 0);
-#else
-    constexpr int group_m = 4;
-#endif
-    const int n_cu = device_cu_count();
-    // 256x256 tiles need whole rounds of the chip: with fewer than 4 rounds, a last round that leaves more than a fifth of
-    // the CUs idle costs more than the smaller tile's lower arithmetic intensity (decoder fc1 at 4096 rows: 320 tiles =
-    // 1.25 rounds, 118 us against 1280 tiles of 128x128 in 2.5 rounds of 512 workgroups).
-    const int pm = plan_rows(g);
-    const long nt256 = (long)cdiv(pm, 256) * (g.N / 256);
-    const long rounds256 = (nt256 + n_cu - 1) / n_cu;
-    // (split / mixed modes: a K tile pair costs twice the bf16 K tile while the 128x128 kernel's fixed costs do not shrink — since the
-    // r04 K-loop work the 256x256 kernel wins down to 3/5 of a last round: decoder fc1 at 4 096 rows, 320 tiles, 152 against 161 us)
-    const bool ragged256 = rounds256 < 4 && nt256 * 5 < rounds256 * n_cu * (IO<T>::split ? 3 : 4);
-    // (r05: 160 tiles for the GELU epilogue in the split / mixed modes — decoder fc1 at 2 048 rows, one round on 62 % of the CUs: 512 slots 21.3 ->
-    // 20.3 ms per decode step; NOT for the q|k|v epilogue: 180 tiles at 3 072 rows lose to two rounds of 128x128 tiles, 28.0 -> 29.0 ms)
-    const long need256 = (IO<T>::split && EPI == EPI_GELU) ? 160 : 192;
-    if (g.N % 256 == 0 && nt256 >= need256 && !ragged256 && g.K >= 128) {      // (K = 64 words: one K tile, 128x128 kernel)
-      const int ntm = cdiv(g.M, 256), ntiles = ntm * (g.N / 256);
-      // WSEG_F16M6, M6-row outputs, between one and two rounds of 256x256 tiles (decoder fc1 at 4 096 rows: 320 tiles on 256 CUs — the
-      // second round runs on a quarter of the chip): the columns that fill ONE round go through the kernel as usual; the remaining
-      // column tiles are multiplied as split-K copies that fill the chip once more for 1 / S of the K range, and the 8-column
-      // reduction writes their M6 rows.
-      if constexpr (IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU)) {
-        const int ptm = cdiv(pm, 256);      // planned row tiles: the column split and S must not follow the rows launched
-        const int ntn = g.N / 256, full_cols = n_cu / ptm, pairs = g.K / 128;
-        if (rounds256 == 2 && g.splitk_ws && full_cols >= 1 && full_cols < ntn && g.K >= 256) {
-          const int rem_tiles = (ntn - full_cols) * ptm, n1 = full_cols * 256, n2 = g.N - n1;
-          int S = n_cu / rem_tiles;
-          while (S >= 2 && ((rem_tiles * S) % 8 || pairs / S < 2 || (size_t)S * pm * n2 * sizeof(float) > g.splitk_ws_bytes)) --S;
-          if (S >= 2 && rem_tiles * S * 4 >= n_cu * 3) {
-            int grid = ntm * full_cols < n_cu ? ntm * full_cols : n_cu;
-            grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
-            hipLaunchKernelGGL((gemm_h16_pp_kernel<T, EPI>), dim3(grid), dim3(512), 0, s, A, g.lda, W, g.ldw, g.M, n1, g.K, g.ep, ntm, group_m, 1);
-            GemmArgs g2 = g;
-            g2.W = W + (size_t)n1 * g.ldw;
-            g2.N = n2;
-            WSEG_TRY_(launch_pp_splitk<T>(g2, S, s));
-            typedef typename IO<T>::P PT;
-            EpiParams e3 = g.ep;
-            if (e3.bias) e3.bias = (const PT*)g.ep.bias + n1;
-            e3.out = (char*)g.ep.out + (size_t)(n1 >> 6) * 256;      // M6 rows: 256 bytes per 64 logical columns; ldc stays the full row
-            hipLaunchKernelGGL((splitk_reduce8_kernel<EPI, T>), dim3(cdiv(g.M * (n2 / 8), 256)), dim3(256), 0, s, g.splitk_ws, S, g.M, g.M, n2, e3);
-            if (e1) (void)hipEventRecord(e1, s);
-            WSEG_LAUNCH_CHECK();
-            return WSEG_OK;
-          }
-        }
-      }
-      // (Measured and dropped: r04, the generic kernel as 4 waves x 128x128 wave tiles, one wave per SIMD — 640 against 1 080 TFLOP/s on the
-      // encoder shapes; r05, the hand-built one-wave-per-SIMD kernel — tools/experiments/r05_gemm_w4_kernel.hip.txt, profiles/r05_w4_experiments.txt;
-      // r03, a register-resident residual epilogue — all CUs reach their epilogue together and its 1.3 GB of fp32 residual traffic is an
-      // HBM-bound burst either way: staged 540 / 1513 us, direct 590 / 1525 us; r04, hi-only attention projections in f16m6 — 19x the logit
-      // error at 32 layers.)
-      {
-        int grid = ntiles < n_cu ? ntiles : n_cu;
-        grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
-        hipLaunchKernelGGL((gemm_h16_pp_kernel<T, EPI>), dim3(grid), dim3(512), 0, s, A, g.lda, W, g.ldw, g.M, g.N, g.K, g.ep, ntm, group_m, 1);
-      }
-    } else {
-      const int ntm = cdiv(g.M, 128), ntiles = ntm * (g.N / 128);
-      if (cdiv(pm, 128) * (g.N / 128) >= 16) {
-        int grid = ntiles < 2 * n_cu ? ntiles : 2 * n_cu;
-        grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
-        hipLaunchKernelGGL((gemm_h16_persist_kernel<T, 128, 128, 2, 2, EPI>), dim3(grid), dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N,
-                           g.K, g.ep, ntm, group_m);
-      } else {
-        hipLaunchKernelGGL((gemm_h16_kernel<T, 128, 128, 2, 2, EPI, false>), dim3(ntiles), dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N,
-                           g.K, g.ep, (float*)nullptr, 0, ntm);
-      }
-    }
-    if (e1) (void)hipEventRecord(e1, s);
-    WSEG_LAUNCH_CHECK();
-    return WSEG_OK;
+// Which large tile.  mx_rows: M6 EPI_STORE / EPI_GELU (the only product that may take the split-K tail).
+template <typename T> static void plan_large_tiles(EpiKind epi, const GemmArgs& g, bool mx_rows, H16Plan& p) {
+  const int n_cu = device_cu_count(), pm = plan_rows(g);
+  // 256x256 tiles need whole rounds of the chip: with fewer than 4 rounds, a last round that leaves more than a fifth of
+  // the CUs idle costs more than the smaller tile's lower arithmetic intensity (decoder fc1 at 4096 rows: 320 tiles =
+  // 1.25 rounds, 118 us against 1280 tiles of 128x128 in 2.5 rounds of 512 workgroups).
+  const long nt256 = (long)cdiv(pm, 256) * (g.N / 256);
+  const long rounds256 = (nt256 + n_cu - 1) / n_cu;
+  // (split / mixed modes: a K tile pair costs twice the bf16 K tile while the 128x128 kernel's fixed costs do not shrink — since the
+  // r04 K-loop work the 256x256 kernel wins down to 3/5 of a last round: decoder fc1 at 4 096 rows, 320 tiles, 152 against 161 us)
+  const bool ragged256 = rounds256 < 4 && nt256 * 5 < rounds256 * n_cu * (IO<T>::split ? 3 : 4);
+  // (r05: 160 tiles for the GELU epilogue in the split / mixed modes — decoder fc1 at 2 048 rows, one round on 62 % of the CUs: 512 slots 21.3 ->
+  // 20.3 ms per decode step; NOT for the q|k|v epilogue: 180 tiles at 3 072 rows lose to two rounds of 128x128 tiles, 28.0 -> 29.0 ms)
+  const long need256 = (IO<T>::split && epi == EPI_GELU) ? 160 : 192;
+  if (!(g.N % 256 == 0 && nt256 >= need256 && !ragged256 && g.K >= 128)) {      // (K = 64 words: one K tile, 128x128 kernel)
+    p.family = cdiv(pm, 128) * (g.N / 128) >= 16 ? H16Plan::PERSIST128 : H16Plan::TILE128;
+    return;
   }
-  // WSEG_F16M6, M6-row outputs below the large-tile threshold but with hundreds of rows (decoder fc1 at 112-270 slots; r05): split-K copies
-  // of the 256x256 kernel + the M6-writing 8-column reduction, instead of the 128x64 stream kernel (whose 4-column epilogue writes hi | lo
-  // rows that a conversion launch turns into M6 rows): 57.5 + 11.8 us -> see profiles/r05_epilogue_ab.txt.  gemm_out_is_mx predicts it.
-  if constexpr (IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU)) {
-    const int S = pp_splitk_plan<T>(g);
-    if (S) {
-      WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
-      hipLaunchKernelGGL((splitk_reduce8_kernel<EPI, T>), dim3(cdiv(g.M * (g.N / 8), 256)), dim3(256), 0, s, g.splitk_ws, S, g.M, g.M, g.N, g.ep);
-      WSEG_LAUNCH_CHECK();
-      return WSEG_OK;
-    }
-  }
-  SkinnyPlan sp = plan_skinny(g, IsMx<T>::v);
-  // (block-floating-point cross K / V: the row writer needs the lanes of a row side by side, which the 4-column MFMA-layout epilogue of
-  // the stream kernels does not give — an un-split plan goes through the partial plane + reduction kernel as well)
-  const bool coop_kv = EPI == EPI_KV_CROSS && IO<T>::split && g.ep.kv24 >= 2;
-  if (sp.splits == 1 && !(coop_kv && g.splitk_ws && (size_t)sp.m_pad * g.N * sizeof(float) <= g.splitk_ws_bytes)) {
-    if (coop_kv) { set_error("gemm: block-floating-point cross K / V needs the split-K workspace"); return WSEG_ERR_STATE; }
-    dim3 grid(g.N / 64, sp.mt, 1);
-#define WSEG_SKINNY(BM_, WM_, WN_)                                                                                      \
-  hipLaunchKernelGGL((gemm_h16_kernel<T, BM_, 64, WM_, WN_, EPI, false, 2>), grid, dim3(256), 0, s, A, g.lda, W, g.ldw, g.M, g.N, \
-                     g.K, g.ep, (float*)nullptr, sp.m_pad, 0)
-    if (sp.bm == 32) WSEG_SKINNY(32, 1, 4);
-    else if (sp.bm == 64) WSEG_SKINNY(64, 1, 4);
-    else WSEG_SKINNY(128, 2, 2);
-#undef WSEG_SKINNY
-    WSEG_LAUNCH_CHECK();
-    return WSEG_OK;
-  }
-  WSEG_TRY_(launch_skinny_partial<T>(g, sp, s));
-  if constexpr (IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU)) {
-    if (skinny_split_writes_mx(g.N)) {      // M6 rows straight from the reduction (gemm_out_is_mx predicts exactly this)
-      hipLaunchKernelGGL((splitk_reduce8_kernel<EPI, T>), dim3(cdiv(g.M * (g.N / 8), 256)), dim3(256), 0, s, g.splitk_ws, sp.splits, sp.m_pad, g.M,
-                         g.N, g.ep);
-      WSEG_LAUNCH_CHECK();
-      return WSEG_OK;
-    }
-  }
-  const int work = g.M * (g.N / 4);
-  hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T>), dim3(cdiv(work, 256)), dim3(256), 0, s, g.splitk_ws, sp.splits, sp.m_pad, g.M, g.N, g.ep);
-  WSEG_LAUNCH_CHECK();
-  return WSEG_OK;
-}
-
-template <int EPI>
-static int launch_any(int dtype, const GemmArgs& g, hipStream_t s) {
-  if (dtype == WSEG_BF16) return launch_h16<EPI, bf16_t>(g, s);
-  if (dtype == WSEG_F16) return launch_h16<EPI, f16_t>(g, s);
-  if (dtype == WSEG_BF16X3) return launch_h16<EPI, X3<bf16_t>>(g, s);
-  if (dtype == WSEG_F16X3) return launch_h16<EPI, X3<f16_t>>(g, s);
-  if (dtype == WSEG_F16M6) return launch_h16<EPI, M6>(g, s);
-  return launch_gemm_f32((EpiKind)EPI, g, s);      // exact-parity kernels: wseg_gemm_f32.hip
-}
-
-template <typename T>
-static int gemm_partial_t(const GemmArgs& g0, PartialInfo* info, bool* ok, hipStream_t s) {
-  const GemmArgs g = kernel_view<T>(g0);
-  if (!g.splitk_ws || g.K % 64 || g.N % 64) return WSEG_OK;
-  // thousands of rows, too few 256x256 tiles for the chip (the decode step's cross-attention query): the split-K copies of the
-  // ping-pong kernel leave the same fp32 planes [z][M][N] as the stream family.  (r05: also ABOVE the large-tile threshold when the
-  // 256x256 tiles fill at most half the chip — decoder q|k|v at 2 048 rows, 120 tiles: two split-K copies + the reduction inside the
-  // attention kernel instead of the 128x128 kernel with its own epilogue)
-  const int S = pp_splitk_plan<T>(g);
-  if (S) {
-    WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
-    info->part = g.splitk_ws; info->splits = S; info->m_pad = g.M; info->n = g.N;
-    *ok = true;
-    return WSEG_OK;
-  }
-  if (big_tile_path(g)) return WSEG_OK;
-  SkinnyPlan sp = plan_skinny(g, IsMx<T>::v);
-  if ((size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) return WSEG_OK;
-  WSEG_TRY_(launch_skinny_partial<T>(g, sp, s));
-  info->part = g.splitk_ws; info->splits = sp.splits; info->m_pad = sp.m_pad; info->n = g.N;
-  *ok = true;
-  return WSEG_OK;
-}
-
-int launch_gemm_partial(int dtype, const GemmArgs& g, PartialInfo* info, bool* ok, hipStream_t s) {
-  *ok = false;
-  switch (dtype) {
-    case WSEG_BF16: return gemm_partial_t<bf16_t>(g, info, ok, s);
-    case WSEG_F16: return gemm_partial_t<f16_t>(g, info, ok, s);
-    case WSEG_BF16X3: return gemm_partial_t<X3<bf16_t>>(g, info, ok, s);
-    case WSEG_F16X3: return gemm_partial_t<X3<f16_t>>(g, info, ok, s);
-    case WSEG_F16M6: return gemm_partial_t<M6>(g, info, ok, s);
-    default: return WSEG_OK;      // exact-parity mode: no split-K (one k-ordered chain per output)
+  // (Measured and dropped: r04, the generic kernel as 4 waves x 128x128 wave tiles, one wave per SIMD — 640 against 1 080 TFLOP/s on the
+  // encoder shapes; r05, the hand-built one-wave-per-SIMD kernel — tools/experiments/r05_gemm_w4_kernel.hip.txt, profiles/r05_w4_experiments.txt;
+  // r03, a register-resident residual epilogue — all CUs reach their epilogue together and its 1.3 GB of fp32 residual traffic is an
+  // HBM-bound burst either way: staged 540 / 1513 us, direct 590 / 1525 us; r04, hi-only attention projections in f16m6 — 19x the logit
+  // error at 32 layers.)
+  p.family = H16Plan::PP;
+  // WSEG_F16M6, M6-row outputs, between one and two rounds of 256x256 tiles (decoder fc1 at 4 096 rows: 320 tiles on 256 CUs — the
+  // second round runs on a quarter of the chip): the columns that fill ONE round go through the kernel as usual; the remaining
+  // column tiles are multiplied as split-K copies that fill the chip once more for 1 / S of the K range, and the 8-column
+  // reduction writes their M6 rows.
+  if (!mx_rows) return;
+  const int ptm = cdiv(pm, 256);      // planned row tiles: the column split and S must not follow the rows launched
+  const int ntn = g.N / 256, full_cols = n_cu / ptm, pairs = g.K / 128;
+  if (!(rounds256 == 2 && g.splitk_ws && full_cols >= 1 && full_cols < ntn && g.K >= 256)) return;
+  const int rem_tiles = (ntn - full_cols) * ptm, n1 = full_cols * 256, n2 = g.N - n1;
+  int S = n_cu / rem_tiles;
+  while (S >= 2 && ((rem_tiles * S) % 8 || pairs / S < 2 || (size_t)S * pm * n2 * sizeof(float) > g.splitk_ws_bytes)) --S;
+  if (S >= 2 && rem_tiles * S * 4 >= n_cu * 3) {
+    p.family = H16Plan::PP_WITH_SPLITK_TAIL;
+    p.splits = S;
+    p.n_main = n1;
   }
 }
 
-// x = x + (A W^T + bias); y = LayerNorm(x) * gamma + beta.   MFMA decoder rows: split-K partials + ONE fused
-// reduction/residual/LayerNorm kernel; otherwise the generic GEMM (EPI_RESID) followed by launch_layernorm.
 // Split-K on the 256x256 ping-pong kernel for decoder rows with a long K and too few output tiles for the chip (fc2 at 4096
 // rows: 16 x 5 = 80 tiles on 256 CUs; the 128x64 stream kernel needs 99 us for it, hipBLASLt 56): S = n_cu / tiles copies of the
 // tile grid, each multiplying 1/S of the K tiles into an fp32 partial plane.  Returns 0 when the shape does not qualify.
@@ -1448,78 +1261,298 @@ template <typename T> static int pp_splitk_plan(const GemmArgs& g) {
   return S >= 2 ? S : 0;
 }
 
-template <typename T> static int launch_pp_splitk(const GemmArgs& g, int S, hipStream_t s) {
-  typedef typename IO<T>::H HT;
-  constexpr int group_m = 4;
-  const int ntm = cdiv(g.M, 256), ntiles = ntm * (g.N / 256) * S, n_cu = device_cu_count();
-  int grid = ntiles < n_cu ? ntiles : n_cu;
-  grid = (grid + 7) & ~7;      // (a multiple of 8: one share per XCD; workgroups beyond the tile count return at once)
-  EpiParams ep;
-  ep.out_f32 = g.splitk_ws; ep.ldc = g.N;
-  hipLaunchKernelGGL((gemm_h16_pp_kernel<T, EPI_F32, true>), dim3(grid), dim3(512), 0, s, (const HT*)g.A, g.lda, (const HT*)g.W, g.ldw,
-                     g.M, g.N, g.K, ep, ntm, group_m, S);
-  WSEG_LAUNCH_CHECK();
-  return WSEG_OK;
-}
-
-template <typename T>
-static int gemm_resid_ln_t(const GemmArgs& g0, const void* gamma, const void* beta, void* y, bool* done, hipStream_t s) {
-  typedef typename IO<T>::P PT;
-  const GemmArgs g = kernel_view<T>(g0);
-  const int d = g.N;
-  if (d % 8 == 0 && d <= 2048 && g.ep.bias && g.ep.resid == g.ep.out && g.ep.ldc == d && !big_tile_path(g)) {
-    const int S = pp_splitk_plan<T>(g);
-    if (S) {
-      WSEG_TRY_(launch_pp_splitk<T>(g, S, s));
-      hipLaunchKernelGGL(splitk_reduce_resid_ln_kernel<T>, dim3(g.M), dim3(256), 0, s, g.splitk_ws, S, g.M, g.M, d, (const PT*)g.ep.bias,
-                         (float*)g.ep.out, (const PT*)gamma, (const PT*)beta, y);
-      WSEG_LAUNCH_CHECK();
-      *done = true;
-      return WSEG_OK;
+// Stream family (decoder steps, small encoders): 64-column tiles of 32 / 64 / 128 rows; K is split across workgroups until
+// ~256+ of them stream the weight matrix.  Partials are reduced (in a fixed order) by a second kernel that applies the
+// epilogue (or the fused residual + LayerNorm).  pairs: M6 rows — a K range is whole (hi, MX) tile pairs.
+static void plan_stream(const GemmArgs& g, bool pairs, H16Plan& p) {
+  const int pm = plan_rows(g);
+  // largest row tile that still yields >= 160 workgroups without splitting K; otherwise 128 rows + split-K
+  p.bm = pm <= 32 ? 32 : (pm <= 64 ? 64 : 128);
+  if (pm > 64) {
+    const int nt = g.N / 64;
+    if (nt * cdiv(pm, 128) < 160 && nt * cdiv(pm, 64) >= 160) p.bm = 64;
+  }
+  const int plan_pad = cdiv(pm, p.bm) * p.bm, blocks = (g.N / 64) * cdiv(pm, p.bm);
+  p.splits = 1;
+  if (g.splitk_ws) {
+    // split K (in whole 64-wide tiles, >= 2 tiles per split) until ~256 workgroups stream the weights
+    const int nk = g.K / 64;
+    for (int cand = 2; cand <= 16 && blocks * p.splits < 256; ++cand) {
+      if (nk % cand || nk / cand < 2 || (pairs && (nk / cand) % 2)) continue;
+      if ((size_t)cand * plan_pad * g.N * sizeof(float) > g.splitk_ws_bytes) break;
+      p.splits = cand;
     }
   }
-  if (big_tile_path(g) || !g.splitk_ws || d % 8 || d > 2048 || !g.ep.bias || g.ep.resid != g.ep.out || g.ep.ldc != d || g.K % 64 ||
-      g.N % 64)
-    return WSEG_OK;
-  SkinnyPlan sp = plan_skinny(g, IsMx<T>::v);
-  // K not split (enough row tiles to fill the chip, 2048+ rows): the fp32 partial round trip buys nothing; the GEMM adds
-  // the residual in its own epilogue and a LayerNorm launch follows (2048 rows: 21.6 + ~6 us against 26.7 + 8.9 us)
-  if (sp.splits == 1 || (size_t)sp.splits * sp.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) return WSEG_OK;
-  WSEG_TRY_(launch_skinny_partial<T>(g, sp, s));
-  hipLaunchKernelGGL(splitk_reduce_resid_ln_kernel<T>, dim3(g.M), dim3(256), 0, s, g.splitk_ws, sp.splits, sp.m_pad, g.M, d,
-                     (const PT*)g.ep.bias, (float*)g.ep.out, (const PT*)gamma, (const PT*)beta, y);
+  p.k_len = g.K / p.splits;
+  p.mt = cdiv(g.M, p.bm);      // the grid and the partial planes cover the rows actually launched
+  p.m_pad = p.mt * p.bm;
+}
+
+// g: the kernel view of the launch (kernel_view<T>).  `use` carries the three orders of precedence.
+template <typename T> static H16Plan plan_h16(EpiKind epi, const GemmArgs& g, PlanUse use) {
+  H16Plan p;
+  // M6 rows leave the LDS-staged 8-column epilogues (large tiles) and the 8-column reduction; the stream kernel's own epilogue
+  // and the 4-column reduction write hi | lo rows
+  const bool mx_rows = IsMx<T>::v && use == USE_EPILOGUE && (epi == EPI_STORE || epi == EPI_GELU);
+  if (!h16_tiles_ok<T>(g, use) || (use != USE_EPILOGUE && !g.splitk_ws)) return p;
+  auto pp_splitk = [&] {
+    const int S = pp_splitk_plan<T>(g);
+    if (S) { p.family = H16Plan::PP_SPLITK; p.splits = S; p.k_len = g.K; p.m_pad = g.M; p.out_is_mx = mx_rows; }
+    return S != 0;
+  };
+  const bool big = big_tile_path(g);
+  switch (use) {
+    case USE_EPILOGUE:
+      // large tiles first; then, M6-row outputs below the large-tile threshold but with hundreds of rows (decoder fc1 at 112-270 slots;
+      // r05): split-K copies of the 256x256 kernel + the M6-writing 8-column reduction, instead of the 128x64 stream kernel (whose
+      // 4-column epilogue writes hi | lo rows that a conversion launch turns into M6 rows): 57.5 + 11.8 us -> see profiles/r05_epilogue_ab.txt
+      if (big) { plan_large_tiles<T>(epi, g, mx_rows, p); p.out_is_mx = mx_rows; return p; }
+      if (mx_rows && pp_splitk()) return p;
+      break;
+    case USE_PARTIAL:
+      // thousands of rows, too few 256x256 tiles for the chip (the decode step's cross-attention query): the split-K copies of the
+      // ping-pong kernel leave the same fp32 planes [z][M][N] as the stream family.  (r05: also ABOVE the large-tile threshold when the
+      // 256x256 tiles fill at most half the chip — decoder q|k|v at 2 048 rows, 120 tiles: two split-K copies + the reduction inside the
+      // attention kernel instead of the 128x128 kernel with its own epilogue)
+      if (pp_splitk()) return p;
+      if (big) return p;
+      break;
+    case USE_RESID_LN: {
+      // the fused reduction (splitk_reduce_resid_ln_kernel): one 8-column chunk per thread of a 256-thread row, residual stream in place
+      const int d = g.N;
+      if (d % 8 || d > 2048 || !g.ep.bias || g.ep.resid != g.ep.out || g.ep.ldc != d || big) return p;
+      if (pp_splitk()) return p;
+      break;
+    }
+  }
+  plan_stream(g, IsMx<T>::v, p);
+  const bool fits = g.splitk_ws && (size_t)p.splits * p.m_pad * g.N * sizeof(float) <= g.splitk_ws_bytes;
+  p.family = H16Plan::STREAM_SPLITK;
+  if (use == USE_EPILOGUE) {
+    // (block-floating-point cross K / V: the row writer needs the lanes of a row side by side, which the 4-column MFMA-layout epilogue of
+    // the stream kernels does not give — an un-split plan goes through the partial plane + reduction kernel as well, and without the
+    // workspace for it there is no plan)
+    const bool coop_kv = epi == EPI_KV_CROSS && IO<T>::split && g.ep.kv24 >= 2;
+    if (p.splits == 1 && !(coop_kv && fits)) p.family = coop_kv ? H16Plan::NONE : H16Plan::STREAM;
+    p.out_is_mx = mx_rows && p.family == H16Plan::STREAM_SPLITK && g.N % 32 == 0;      // the 8-column reduction: a quad covers a 32-column M6 block
+  } else if (!fits || (use == USE_RESID_LN && p.splits == 1)) {
+    // (USE_RESID_LN, K not split — enough row tiles to fill the chip, 2048+ rows: the fp32 partial round trip buys nothing; the GEMM adds
+    // the residual in its own epilogue and a LayerNorm launch follows: 2048 rows, 21.6 + ~6 us against 26.7 + 8.9 us)
+    p.family = H16Plan::NONE;
+  }
+  return p;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launchers: one per kernel family
+// ------------------------------------------------------------------------------------------------
+// persistent grids: min(tiles, cap) workgroups, rounded up to a multiple of 8 — one share per XCD; workgroups beyond the tile count return at once
+static int xcd_grid(int tiles, int cap) { return ((tiles < cap ? tiles : cap) + 7) & ~7; }
+
+// m-tiles per tile group of the persistent order: the 32 tiles in flight on one XCD then span ~4 activation tiles x 8
+// weight tiles, the smallest operand footprint for 32 tiles (a + b = 12 operand tiles; 2-row groups re-stream the
+// whole weight matrix per tile pair: PMC FETCH_SIZE 2-3x the algorithmic bytes, profiles/).  Measured at 256
+// windows: 4 beats 2 by 2-8 % on the K = 1280 shapes, 6 and 8 lose on K = 5120.
+static int persistent_group_m() {
+#if defined(WSEG_STAMPS) && WSEG_STAMPS == 4
+  static const int group_m = 4 | (getenv("WSEG_PP_SOLO") ? 0x100 : 0);
+  return group_m;
+#else
+  return 4;
+#endif
+}
+
+// columns [0, n_cols) of the product (n_cols < g.N: the un-split part of PP_WITH_SPLITK_TAIL)
+template <int EPI, typename T> static void launch_pp(const GemmArgs& g, int n_cols, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  const int ntm = cdiv(g.M, 256);
+  hipLaunchKernelGGL((gemm_h16_pp_kernel<T, EPI>), dim3(xcd_grid(ntm * (n_cols / 256), device_cu_count())), dim3(512), 0, s, (const HT*)g.A, g.lda,
+                     (const HT*)g.W, g.ldw, g.M, n_cols, g.K, g.ep, ntm, persistent_group_m(), 1);
+}
+
+// fp32 partial planes [S][g.M][g.N] into g.splitk_ws
+template <typename T> static int launch_pp_splitk(const GemmArgs& g, int S, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  const int ntm = cdiv(g.M, 256);
+  EpiParams ep;
+  ep.out_f32 = g.splitk_ws; ep.ldc = g.N;
+  hipLaunchKernelGGL((gemm_h16_pp_kernel<T, EPI_F32, true>), dim3(xcd_grid(ntm * (g.N / 256) * S, device_cu_count())), dim3(512), 0, s, (const HT*)g.A,
+                     g.lda, (const HT*)g.W, g.ldw, g.M, g.N, g.K, ep, ntm, 4, S);
   WSEG_LAUNCH_CHECK();
-  *done = true;
   return WSEG_OK;
 }
 
-int launch_gemm_resid_ln(int dtype, const GemmArgs& g, const void* gamma, const void* beta, void* y, hipStream_t s) {
-  bool done = false;
-  switch (dtype) {
-    case WSEG_BF16: WSEG_TRY_(gemm_resid_ln_t<bf16_t>(g, gamma, beta, y, &done, s)); break;
-    case WSEG_F16: WSEG_TRY_(gemm_resid_ln_t<f16_t>(g, gamma, beta, y, &done, s)); break;
-    case WSEG_BF16X3: WSEG_TRY_(gemm_resid_ln_t<X3<bf16_t>>(g, gamma, beta, y, &done, s)); break;
-    case WSEG_F16X3: WSEG_TRY_(gemm_resid_ln_t<X3<f16_t>>(g, gamma, beta, y, &done, s)); break;
-    case WSEG_F16M6: WSEG_TRY_(gemm_resid_ln_t<M6>(g, gamma, beta, y, &done, s)); break;
-    default: break;
-  }
-  if (done) return WSEG_OK;
-  WSEG_TRY_(launch_gemm(dtype, EPI_RESID, g, s));
-  return launch_layernorm(dtype, (const float*)g.ep.out, gamma, beta, y, g.M, g.N, s);      // (WSEG_F16M6: y as M6 rows, like the fused kernel)
+template <int EPI, typename T> static void launch_persist128(const GemmArgs& g, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  const int ntm = cdiv(g.M, 128);
+  hipLaunchKernelGGL((gemm_h16_persist_kernel<T, 128, 128, 2, 2, EPI>), dim3(xcd_grid(ntm * (g.N / 128), 2 * device_cu_count())), dim3(256), 0, s,
+                     (const HT*)g.A, g.lda, (const HT*)g.W, g.ldw, g.M, g.N, g.K, g.ep, ntm, persistent_group_m());
 }
 
-// WSEG_F16M6: are the operand rows an EPI_STORE / EPI_GELU launch of this shape writes M6 rows (LDS-staged 8-column epilogues of the
-// large-tile kernels: cooperative op_st8) or hi | lo rows (4-column epilogues of the skinny family and its split-K reduction)?
+template <int EPI, typename T> static void launch_tile128(const GemmArgs& g, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  const int ntm = cdiv(g.M, 128);
+  hipLaunchKernelGGL((gemm_h16_kernel<T, 128, 128, 2, 2, EPI, false>), dim3(ntm * (g.N / 128)), dim3(256), 0, s, (const HT*)g.A, g.lda, (const HT*)g.W,
+                     g.ldw, g.M, g.N, g.K, g.ep, (float*)nullptr, 0, ntm);
+}
+
+// LDS ring depth of the stream kernels: 2 stages.  Measured (large, 120 windows): 6-8 K tiles in flight with one workgroup per CU is 1.7x
+// SLOWER than 3-4 stages at two workgroups per CU, and 2 stages (3-5 workgroups per CU) is another 2-3 % faster at every
+// batch size — these kernels want co-resident workgroups to cover their barriers, not more bytes in flight each.
+// Round 2, at 1024 rows (profiles/README.md, "decode GEMM experiments"): 3 / 4 stages 12.8 / 16.7 us against 11.1 us;
+// 128x128 tiles (split 4) 13.6 us; no split with 128x128 tiles and 3 stages 24 us; register staging (global -> VGPR ->
+// ds_write, one barrier per K tile) 35.8 us; dropping the loads OR the MFMAs from the loop changes nothing (11.3 / 9.8
+// us): a K tile costs ~0.6 us of serialised issue -> land -> barrier -> fragment reads -> MFMA -> barrier per workgroup,
+// while a bare LDS-DMA stream of the same L2-resident data runs at 123 GB/s per CU (tools/probes/l2fill_probe.hip).
+template <int EPI, typename T, bool SPLIT> static void launch_stream_kernel(const GemmArgs& g, const H16Plan& p, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  const dim3 grid(g.N / 64, p.mt, SPLIT ? p.splits : 1);
+#define WSEG_STREAM(BM_, WM_, WN_)                                                                                                \
+  hipLaunchKernelGGL((gemm_h16_kernel<T, BM_, 64, WM_, WN_, EPI, SPLIT, 2>), grid, dim3(256), 0, s, (const HT*)g.A, g.lda, (const HT*)g.W, g.ldw, \
+                     g.M, g.N, p.k_len, g.ep, SPLIT ? g.splitk_ws : (float*)nullptr, p.m_pad, 0)
+  if (p.bm == 32) WSEG_STREAM(32, 1, 4);
+  else if (p.bm == 64) WSEG_STREAM(64, 1, 4);
+  else WSEG_STREAM(128, 2, 2);
+#undef WSEG_STREAM
+}
+
+// fp32 partial sums [splits][m_pad][N] into g.splitk_ws (valid for splits == 1 too)
+template <typename T> static int launch_stream_partial(const GemmArgs& g, const H16Plan& p, hipStream_t s) {
+  if (!g.splitk_ws || (size_t)p.splits * p.m_pad * g.N * sizeof(float) > g.splitk_ws_bytes) {
+    set_error("split-K workspace missing or too small");
+    return WSEG_ERR_STATE;
+  }
+  launch_stream_kernel<EPI_STORE, T, true>(g, p, s);
+  WSEG_LAUNCH_CHECK();
+  return WSEG_OK;
+}
+
+// the fp32 planes [p.splits][p.m_pad][g.N] of a split-K plan, whichever family multiplies them
+template <typename T> static int launch_partial_planes(const GemmArgs& g, const H16Plan& p, hipStream_t s) {
+  return p.family == H16Plan::PP_SPLITK ? launch_pp_splitk<T>(g, p.splits, s) : launch_stream_partial<T>(g, p, s);
+}
+
+// sum of the planes + epilogue, 8 columns per thread (M6 rows) / 4 columns per thread
+template <int EPI, typename T> static void launch_reduce8(const float* part, int splits, int m_pad, int M, int N, const EpiParams& ep, hipStream_t s) {
+  hipLaunchKernelGGL((splitk_reduce8_kernel<EPI, T>), dim3(cdiv(M * (N / 8), 256)), dim3(256), 0, s, part, splits, m_pad, M, N, ep);
+}
+template <int EPI, typename T> static void launch_reduce4(const float* part, int splits, int m_pad, int M, int N, const EpiParams& ep, hipStream_t s) {
+  hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T>), dim3(cdiv(M * (N / 4), 256)), dim3(256), 0, s, part, splits, m_pad, M, N, ep);
+}
+
+// f(TypeTag<T>()) with the operand type of a 16-bit-family dtype, otherwise() for any other dtype (the exact-parity fp32 mode)
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F, typename G> static int with_h16_type(int dtype, F&& f, G&& otherwise) {
+  switch (dtype) {
+    case WSEG_BF16: return f(TypeTag<bf16_t>());
+    case WSEG_F16: return f(TypeTag<f16_t>());
+    case WSEG_BF16X3: return f(TypeTag<X3<bf16_t>>());
+    case WSEG_F16X3: return f(TypeTag<X3<f16_t>>());
+    case WSEG_F16M6: return f(TypeTag<M6>());
+    default: return otherwise();
+  }
+}
+
+template <int EPI, typename T>
+static int launch_h16(const GemmArgs& g0, hipStream_t s) {
+  typedef typename IO<T>::H HT;
+  typedef typename IO<T>::P PT;
+  constexpr bool MX_ROWS = IsMx<T>::v && (EPI == EPI_STORE || EPI == EPI_GELU);      // only these instantiate the 8-column reduction
+  const GemmArgs g = kernel_view<T>(g0);
+  const H16Plan p = plan_h16<T>((EpiKind)EPI, g, USE_EPILOGUE);
+  hipEvent_t e0 = nullptr, e1 = nullptr;      // the live profiler times the large-tile launches
+  if (g_prof.on && p.family >= H16Plan::PP && p.family <= H16Plan::TILE128) {
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    e0 = g_prof.get(); e1 = g_prof.get(); g_prof.flops.push_back(2.0 * g0.M * g0.N * g0.K); (void)hipEventRecord(e0, s);
+  }
+  switch (p.family) {
+    case H16Plan::NONE:
+      if (!h16_tiles_ok<T>(g, USE_EPILOGUE)) { set_error("gemm h16: K %d / N %d not tile multiples", g.K, g.N); return WSEG_ERR_INVALID; }
+      set_error("gemm: block-floating-point cross K / V needs the split-K workspace");
+      return WSEG_ERR_STATE;
+    case H16Plan::PP: launch_pp<EPI, T>(g, g.N, s); break;
+    case H16Plan::PP_WITH_SPLITK_TAIL:
+      if constexpr (MX_ROWS) {
+        const int n1 = p.n_main, n2 = g.N - n1;
+        launch_pp<EPI, T>(g, n1, s);
+        GemmArgs g2 = g;
+        g2.W = (const HT*)g.W + (size_t)n1 * g.ldw;
+        g2.N = n2;
+        WSEG_TRY_(launch_pp_splitk<T>(g2, p.splits, s));
+        EpiParams e3 = g.ep;
+        if (e3.bias) e3.bias = (const PT*)g.ep.bias + n1;
+        e3.out = (char*)g.ep.out + (size_t)(n1 >> 6) * 256;      // M6 rows: 256 bytes per 64 logical columns; ldc stays the full row
+        launch_reduce8<EPI, T>(g.splitk_ws, p.splits, g.M, g.M, n2, e3, s);
+      }
+      break;
+    case H16Plan::PERSIST128: launch_persist128<EPI, T>(g, s); break;
+    case H16Plan::TILE128: launch_tile128<EPI, T>(g, s); break;
+    case H16Plan::STREAM: launch_stream_kernel<EPI, T, false>(g, p, s); break;
+    case H16Plan::PP_SPLITK:
+    case H16Plan::STREAM_SPLITK:
+      WSEG_TRY_(launch_partial_planes<T>(g, p, s));
+      if constexpr (MX_ROWS) {
+        if (p.out_is_mx) { launch_reduce8<EPI, T>(g.splitk_ws, p.splits, p.m_pad, g.M, g.N, g.ep, s); break; }
+      }
+      launch_reduce4<EPI, T>(g.splitk_ws, p.splits, p.m_pad, g.M, g.N, g.ep, s);
+      break;
+  }
+  if (e1) (void)hipEventRecord(e1, s);
+  WSEG_LAUNCH_CHECK();
+  return WSEG_OK;
+}
+
+template <int EPI>
+static int launch_any(int dtype, const GemmArgs& g, hipStream_t s) {
+  return with_h16_type(dtype, [&](auto t) -> int { return launch_h16<EPI, typename decltype(t)::type>(g, s); },
+                       [&]() -> int { return launch_gemm_f32((EpiKind)EPI, g, s); });      // exact-parity kernels: wseg_gemm_f32.hip
+}
+
+int launch_gemm_partial(int dtype, const GemmArgs& g0, PartialInfo* info, bool* ok, hipStream_t s) {
+  *ok = false;
+  return with_h16_type(dtype, [&](auto t) -> int {
+    typedef typename decltype(t)::type T;
+    const GemmArgs g = kernel_view<T>(g0);
+    const H16Plan p = plan_h16<T>(EPI_STORE, g, USE_PARTIAL);
+    if (p.family == H16Plan::NONE) return WSEG_OK;
+    WSEG_TRY_(launch_partial_planes<T>(g, p, s));
+    info->part = g.splitk_ws; info->splits = p.splits; info->m_pad = p.m_pad; info->n = g.N;
+    *ok = true;
+    return WSEG_OK;
+  }, []() -> int { return WSEG_OK; });      // exact-parity mode: no split-K (one k-ordered chain per output)
+}
+
+// x = x + (A W^T + bias); y = LayerNorm(x) * gamma + beta.   MFMA decoder rows: split-K partials + ONE fused
+// reduction/residual/LayerNorm kernel; otherwise the generic GEMM (EPI_RESID) followed by launch_layernorm.
+int launch_gemm_resid_ln(int dtype, const GemmArgs& g0, const void* gamma, const void* beta, void* y, hipStream_t s) {
+  bool done = false;
+  WSEG_TRY_(with_h16_type(dtype, [&](auto t) -> int {
+    typedef typename decltype(t)::type T;
+    typedef typename IO<T>::P PT;
+    const GemmArgs g = kernel_view<T>(g0);
+    const H16Plan p = plan_h16<T>(EPI_RESID, g, USE_RESID_LN);
+    if (p.family == H16Plan::NONE) return WSEG_OK;
+    WSEG_TRY_(launch_partial_planes<T>(g, p, s));
+    hipLaunchKernelGGL(splitk_reduce_resid_ln_kernel<T>, dim3(g.M), dim3(256), 0, s, g.splitk_ws, p.splits, p.m_pad, g.M, g.N, (const PT*)g.ep.bias,
+                       (float*)g.ep.out, (const PT*)gamma, (const PT*)beta, y);
+    WSEG_LAUNCH_CHECK();
+    done = true;
+    return WSEG_OK;
+  }, []() -> int { return WSEG_OK; }));
+  if (done) return WSEG_OK;
+  WSEG_TRY_(launch_gemm(dtype, EPI_RESID, g0, s));
+  return launch_layernorm(dtype, (const float*)g0.ep.out, gamma, beta, y, g0.M, g0.N, s);      // (WSEG_F16M6: y as M6 rows, like the fused kernel)
+}
+
+// WSEG_F16M6: does an EPI_STORE / EPI_GELU launch of this shape write M6 rows or hi | lo rows?  The plan's own field: the plan of such a
+// launch does not depend on STORE vs GELU in what it writes (the GELU tile-count rule only moves a launch between two M6-writing families).
 bool gemm_out_is_mx(int dtype, int M, int N, int K, size_t splitk_ws_bytes) {
   if (dtype != WSEG_F16M6) return false;
   GemmArgs g;
-  g.M = M; g.N = N; g.K = 2 * K;
-  if (big_tile_path(g)) return true;
-  if (!splitk_ws_bytes || g.K % 128 || N % 64) return false;
-  g.splitk_ws = (float*)(uintptr_t)16;      // any non-null value: the plans only ask whether a workspace exists and how large it is
+  g.M = M; g.N = N; g.K = 2 * K;      // (the kernel view of an M6 launch)
+  if (splitk_ws_bytes) g.splitk_ws = (float*)(uintptr_t)16;      // any non-null value: the plan only asks whether a workspace exists and how large it is
   g.splitk_ws_bytes = splitk_ws_bytes;
-  if (pp_splitk_plan<M6>(g)) return true;
-  return plan_skinny(g, true).splits > 1 && skinny_split_writes_mx(N);
+  return plan_h16<M6>(EPI_STORE, g, USE_EPILOGUE).out_is_mx;
 }
 
 int launch_gemm(int dtype, EpiKind epi, const GemmArgs& g, hipStream_t s) {

@@ -86,7 +86,8 @@ int launch_gemm(int dtype, EpiKind epi, const GemmArgs& g, hipStream_t s);
 int launch_gemm_f32(EpiKind epi, const GemmArgs& g, hipStream_t s);
 // CU count of the CURRENT device, cached per device
 int device_cu_count();
-// WSEG_F16M6: does an EPI_STORE / EPI_GELU launch of this (logical) shape write M6 rows (true) or hi | lo rows (false)?
+// WSEG_F16M6: does an EPI_STORE / EPI_GELU launch of this (logical) shape write M6 rows (true) or hi | lo rows (false)?  This is the
+// out_is_mx field of the very plan the launch will follow (plan_h16, wseg_gemm.hip), not a separate prediction.
 // splitk_ws_bytes: the split-K workspace the launch will be given (0: none) — the skinny family writes M6 rows when it splits K
 // (M: the rows the PLAN is chosen for — GemmArgs::plan_m when the launch sets it)
 bool gemm_out_is_mx(int dtype, int M, int N, int K, size_t splitk_ws_bytes = 0);
