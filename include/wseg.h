@@ -256,6 +256,23 @@ size_t wseg_debug_step_snapshot_bytes(const wseg_model* m, int32_t n_slots, int3
 int wseg_debug_step_snapshot_arm(wseg_model* m, const int32_t* positions, int32_t n_steps, void* out, size_t out_bytes);
 int wseg_debug_step_snapshot_result(const wseg_model* m, int32_t* n_taken, int32_t* qkv_split);
 
+/* Host-only tap (no model, no workspace, no device; tests/test_scheduler_cpu.py): runs wseg_generate's slot scheduler — the very
+ * object the call drives — against a SCRIPTED device.  Inputs are the scheduler's resolved geometry: window slots, pool units,
+ * max_length, npf = prompt positions the admission's pass covers, pos0 = the position a slot is at when the decode loop first steps
+ * it (wseg_generate uses (0, 0), (P, P) or (min(P - 1, 4), the same)), refill_min / lookahead as in wseg_generate_params, and
+ * done_after[n_windows]: the decode-loop steps after which the window's slot reports done (0: it ended inside the admission's pass).
+ * Writes the statistics such a call would report and a trace of int32 records (kind, a, b, c), in the order the work would be enqueued:
+ *   1 admit    (slot, window, 0)
+ *   2 assign   (slot, page, unit)       after the admission / before the step it belongs to; only pairs that reach the device
+ *   3 preempt  (slot, 0, 0)             before the assignments of its step
+ *   4 step     (t, 0, 0)
+ *   5 retire   (slot, u, 0)             u: the step whose status showed the slot done
+ * *trace_len = int32 entries of the whole trace; trace may be NULL (count only), otherwise trace_cap entries must hold it.
+ * Scheduler errors (WSEG_ERR_STATE) are those of wseg_generate. */
+int wseg_debug_sched_trace(int32_t n_windows, int32_t n_slots, int32_t kv_units, int32_t max_length, int32_t npf, int32_t pos0,
+                           int32_t refill_min, int32_t lookahead, const int32_t* done_after, wseg_generate_stats* stats,
+                           int32_t* trace, int64_t trace_cap, int64_t* trace_len);
+
 /* Per-stage device time (ms) of the last wseg_generate call on this model, measured with HIP events
  * on the call's stream: [0]=encoder passes, [1]=cross-K/V passes, [2]=everything else (the decode steps),
  * [3]=number of decode steps. */

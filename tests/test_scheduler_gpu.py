@@ -432,3 +432,30 @@ def test_first_step_in_the_pass_with_windows_that_end_there(gpu_lib, nb, mode, m
         assert torch.equal(res["merged", key][0], res["step", key][0]) and torch.equal(res["merged", key][1], res["step", key][1]), key
     assert all(int(v) <= c for v, c in zip(res["merged", 17][1].tolist(), caps))
     assert (res["merged", "short"][1] == P + 1).all()
+
+
+def test_scheduler_statistics_equal_the_host_only_tap(gpu_lib):
+    """Ties wseg_debug_sched_trace (the scheduler against a scripted device, tests/test_scheduler_cpu.py) to the device: in greedy
+    mode a slot that enters the decode loop at position POS0 and returns length n reported done after n - 1 - POS0 loop steps
+    (greedy_step_kernel: the step at position p writes token p + 1 and ends the window when that is EOS or the length cap; 0: the
+    admission's pass already ended it).  23 windows through 5 slots with a short pool and the refill running: every field of
+    wseg_last_stats equals what the tap reports for those lengths.  f32 steps through the prompt (NPF = POS0 = 0); f16x3 runs the
+    prompt and the first generated step in the admission's pass (NPF = POS0 = P)."""
+    import ctypes as C
+    from whisperseg_amd import _lib
+    x = tiny_feats(23)
+    P = len(TM.PROMPT)
+    for dtype, (npf, pos0) in (("f32", (0, 0)), ("f16x3", (P, P))):
+        eng = tiny_engine(dtype)
+        _, l = gen(eng, x, 1, 448, n_slots=5, kv_positions=16, refill_min=1)
+        got = _lib.GenerateStats()
+        _lib.check(eng.lib.wseg_last_stats(eng.handle, C.byref(got)))
+        done_after = np.ascontiguousarray(l.numpy().astype(np.int32) - 1 - pos0)
+        assert (done_after >= 0).all() and len(set(done_after.tolist())) > 3
+        want = _lib.GenerateStats()
+        n_trace = C.c_int64(0)
+        _lib.check(eng.lib.wseg_debug_sched_trace(23, 5, got.kv_units_total, 448, npf, pos0, 1, 0, done_after.ctypes.data, C.byref(want),
+                                                  None, 0, C.byref(n_trace)))
+        assert got.kv_units_total == 56 and n_trace.value > 0
+        for name, _ in _lib.GenerateStats._fields_:
+            assert getattr(got, name) == getattr(want, name), (dtype, name, getattr(got, name), getattr(want, name))

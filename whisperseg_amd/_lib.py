@@ -61,6 +61,8 @@ SYMBOLS = {
     "wseg_debug_step_snapshot_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "wseg_debug_step_snapshot_arm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "wseg_debug_step_snapshot_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "wseg_debug_sched_trace": (C.c_int, [C.c_int32] * 8 + [C.c_void_p, C.POINTER(GenerateStats), C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64)]),
     "wseg_last_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 4)]),
     "wseg_last_stats": (C.c_int, [C.c_void_p, C.POINTER(GenerateStats)]),
     "wseg_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

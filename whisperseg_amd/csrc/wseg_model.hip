@@ -3,15 +3,18 @@
 // Replaces HF WhisperForConditionalGeneration as the reference drives it (reference model.py:626-676):
 // encoder (HF modeling_whisper.py:592-646), decoder with KV cache (:690-796), tied LM head (:1080) and
 // greedy / beam-search decoding (HF generation/utils.py:3208-3510).  The host code below only enqueues
-// kernels on the caller's stream; all decoding state lives in the caller-provided workspace.
+// kernels on the caller's stream; all decoding state lives in the caller-provided workspace.  wseg_generate is split in two:
+// the slot scheduler's policy (which window enters which slot, which pool unit backs which K/V page, who is preempted, when a
+// slot retires, when the loop stops) is the host-only SlotScheduler of wseg_sched.h; generate_windows here is its executor.
 #include <algorithm>
-#include <deque>
 #include <map>
 #include <string>
 #include <vector>
 #include "wseg_dec.h"
+#include "wseg_sched.h"
 
 using namespace wseg;
+static_assert(SCHED_KV_PAGE == KV_PAGE, "the scheduler hands out pages of KV_PAGE positions");
 
 namespace {
 
@@ -49,7 +52,7 @@ struct Plan {   // workspace carve-up (all offsets 256-byte aligned)
 // Pinned host staging for the scheduler's small host->device lists and the device->host status mirror.  An entry is
 // re-used only after the event recorded behind its copy has completed.
 struct PinnedRing {
-  static constexpr int N = 8;
+  static constexpr int N = SCHED_RING;
   int* host = nullptr;        // [N][cap]
   int cap = 0;
   hipEvent_t ev[N] = {};
@@ -599,111 +602,50 @@ static int timing_event(Sched& ln, hipStream_t s, int* idx) {
   return WSEG_OK;
 }
 
-// Decode of n_windows windows through S window slots on stream s.
-//
-// The reference decodes batch by batch (model.py:653): a batch runs until its slowest window has finished.  Here a
-// finished window's slot is retired and handed to the next queued window while the other slots keep decoding: every
-// slot has its own position, every per-step kernel skips idle slots (so they cost no K/V traffic), and the captured
-// step graph never changes.  Windows are independent, so the tokens of a window do not depend on which slot it ran in
-// or on what ran beside it (row-independent kernels, fixed row count => fixed tile / split-K plan).
-// The host runs at most `lookahead` steps ahead of the device: the per-step status mirror (done flag of every slot)
-// is read behind an event, which both bounds the wasted steps after the last window finishes and tells the scheduler
-// which slots to retire / refill.
-//
-// Self-attention K / V are PAGED (wseg_kernels.h): the host knows the position every occupied slot feeds at step t (t minus the
-// step it was admitted at), so it hands out a pool unit whenever a slot crosses a page boundary — before the step is launched,
-// through a small page-table update kernel — and takes the slot's units back when it retires.  The pool is sized for the
-// expected length; when it runs short the YOUNGEST slot is preempted (aborted on the device, its window re-queued and later
-// decoded again from scratch: the same tokens), so the oldest window always makes progress, and admissions keep a one-page
-// cushion per window in flight and pause after a preemption until a slot retires.
-static int generate_windows(wseg_model* m, const float* feats, int n_windows, const wseg_generate_params* gp, char* base, int S,
-                            int kv_units, int32_t* out_tokens, int32_t* out_lengths, hipStream_t s) {
-  Sched& ln = m->sched;
-  const wseg_model_config& c = m->cfg;
-  const int nb = gp->num_beams, P = gp->prompt_len, L = gp->max_length;
-  const int G = gp->refill_min > 0 ? gp->refill_min : (S >= 16 ? S / 8 : 1);                // admit once this many slots are free
-  const int K = gp->lookahead > 0 ? (gp->lookahead < PinnedRing::N - 2 ? gp->lookahead : PinnedRing::N - 2) : 1;
+// The two debug taps of a call: the first-step logits (wseg_debug_first_logits) and the step snapshots
+// (wseg_debug_step_snapshot_arm, armed for one call).  Both need the call's windows to start together (window i sits in slot i)
+// and none of them preempted.
+struct SnapTaps {
+  StepSnap req;
+  SnapLayout lay;
+  int taken = 0;
+  int index(int pos) const { for (int i = 0; i < req.n; ++i) if (req.pos[i] == pos) return i; return -1; }
+  char* record(int i) const { return req.out + (size_t)i * lay.total; }
+};
+
+// Device half of one wseg_generate call (the executor of wseg_sched.h's decisions): decode of the windows through S window slots
+// on stream s.  Every method only enqueues work; the order of the calls in generate_windows is the stream order.
+struct GenerateRun {
+  wseg_model* m;
+  const float* feats;
+  const wseg_generate_params* gp;
+  int S, nb, P, L, kv24, NPF, POS0;
+  bool merged;
+  int32_t *out_tokens, *out_lengths;
+  hipStream_t s;
   Plan p;
-  make_plan(m, S, nb, L, kv_units, base, p);
-  DecPlan& q = p.dec;
-  DecodeState& st = q.st;
-  st.P = P; st.eos = gp->eos_token_id; st.pad = gp->pad_token_id; st.max_length = L; st.length_penalty = gp->length_penalty;
-  for (int i = 0; i < 8; ++i) st.prompt[i] = i < P ? gp->prompt[i] : 0;
-  st.win_max_length = gp->window_max_length;
-  st.top_k = (nb == 1 && gp->top_k > 1) ? gp->top_k : 1;
-  st.top_p = gp->top_p;
-  st.seed = (const unsigned long long*)q.seed_dev;
-  WSEG_TRY(ring_prepare(ln.ring_h2d, 2 * S > 2 ? 2 * S : 2));
-  WSEG_TRY(ring_prepare(ln.ring_status, S));
-  wseg_generate_stats& stats = m->stats;
-  stats = wseg_generate_stats();
-  stats.n_windows = n_windows; stats.n_slots = S; stats.kv_units_total = kv_units;
-  {   // the seed lives in device memory (read by the sampling kernel): per-call values do not invalidate the step graph
-    const unsigned long long sd = gp->seed;
-    int words[2];
-    memcpy(words, &sd, 8);
-    WSEG_TRY(h2d_list(ln, words, 2, q.seed_dev, s));
-  }
-  WSEG_TRY(launch_build_suppress_mask((unsigned char*)q.mask, c.vocab, gp->suppress_tokens, gp->n_suppress,
-                                      gp->begin_suppress_tokens, gp->n_begin_suppress, s));
-  WSEG_TRY(launch_decode_reset(st, s));
-  WSEG_HIP_CHECK(hipMemsetAsync(q.zeros, 0, (size_t)S * sizeof(int), s));
+  SnapTaps taps;
+  std::vector<unsigned char> key;      // what the captured step graph takes by value
+  int status_idx[PinnedRing::N];       // status mirror of step u lives in ring entry status_idx[u % N]
 
-  const int d = c.d_model, H = c.n_heads, Tk = c.enc_positions;
-  const int kv24 = m->x3 ? x3_cross_kv_format(c.dtype, nb) : 0;
-  // prompt pass: the first NPF forced positions of every admission run as one pass (run_decoder_step, PromptPass) and the slots start
-  // at position NPF.  Split-precision modes up to 4 beams (24-bit / block-floating-point cross K / V); the f32 and plain 16-bit modes step through the prompt.
-  const bool prompt_pass = getenv("WSEG_NO_PROMPT_PASS") == nullptr;      // test knob (read per call): step through the prompt instead
-  // ... and when the whole prompt fits the pass (P <= 4) and a step follows anyway (L >= P + 2), the pass also runs position P - 1 — the FIRST
-  // GENERATED step, whose beams are still copies: one row per window through the layers and the LM head instead of a full decode step of every
-  // beam row (which would stream the windows' cross K / V once more) — and the admission finishes that step's bookkeeping for its slots
-  // (candidates from the window's one logits row, beam / greedy step on the admitted list).  NPF: positions the pass covers; POS0: the
-  // position the slot is at when the decode loop first steps it.
-  const bool pass_ok = prompt_pass && m->x3 && kv24 != 0;
-  const bool merged = pass_ok && P <= 4 && L >= P + 2 && getenv("WSEG_NO_FIRST_STEP_MERGE") == nullptr;
-  const int NPF = !pass_ok ? 0 : (merged ? P : std::min(P - 1, 4));
-  const int POS0 = merged ? P : NPF;
-  const size_t cross_stride = (size_t)S * H * Tk * cross_kv_row_bytes(kv24, m->es);
-  const size_t feat_stride = (size_t)c.n_mels * c.spec_cols;
-  const int npg = st.npg;
-
-  // host view of the slots
-  std::vector<int> slot_win(S, -1), slot_from(S, 0);   // window in the slot (-1 = free), first step whose status counts for it (at which
-                                                       // the slot is at position NPF)
-  std::vector<std::vector<int>> slot_units(S);         // pool units the slot holds, in page order
-  std::vector<int> free_slots, free_units, tmp_a, tmp_b;
-  for (int i = S - 1; i >= 0; --i) free_slots.push_back(i);   // popped from the back: lowest slot first
-  for (int i = kv_units - 1; i >= 0; --i) free_units.push_back(i);
-  std::deque<int> queue;                               // windows waiting for a slot (preempted windows return to the front)
-  for (int i = 0; i < n_windows; ++i) queue.push_back(i);
-  int in_flight = 0, t = 0, units_in_use = 0;
-  bool hold_admission = false;                         // set by a preemption, cleared by the next retirement
-  bool first_admission = true;
-  bool snap_ok = false;                                // did every window of the call start together (first-logits snapshot)?
-  m->first_logits_valid = false;
-  // step snapshots (wseg_debug_step_snapshot_arm): armed for this call only
-  const StepSnap sn = m->snap_req;
-  m->snap_req = StepSnap();
-  m->snap_taken = -1;
-  m->snap_qkv_split = -1;
-  const SnapLayout sl_ = snap_layout(S, nb, L, c.vocab);
-  if (sn.n > 0 && sn.bytes < (size_t)sn.n * sl_.total) {
-    set_error("step snapshot: %d records of %zu bytes do not fit the %zu-byte buffer", sn.n, sl_.total, sn.bytes);
-    return WSEG_ERR_INVALID;
-  }
-  int snap_taken = 0;
-  auto snap_index = [&](int pos) -> int { for (int i = 0; i < sn.n; ++i) if (sn.pos[i] == pos) return i; return -1; };
   // the decode state a step runs on, as it is before the step's bookkeeping kernels rewrite it
-  auto snap_state = [&](char* rec, hipStream_t qs) -> int {
-    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.seq, st.run_seq, (size_t)S * nb * L * 4, hipMemcpyDeviceToDevice, qs));
-    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.pos, st.pos, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
-    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.idle, st.done, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
-    WSEG_HIP_CHECK(hipMemcpyAsync(rec + sl_.anc, st.anc, (size_t)S * nb * L, hipMemcpyDeviceToDevice, qs));
+  int snap_state(char* rec, hipStream_t qs) const {
+    const DecodeState& st = p.dec.st;
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + taps.lay.seq, st.run_seq, (size_t)S * nb * L * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + taps.lay.pos, st.pos, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + taps.lay.idle, st.done, (size_t)S * 4, hipMemcpyDeviceToDevice, qs));
+    WSEG_HIP_CHECK(hipMemcpyAsync(rec + taps.lay.anc, st.anc, (size_t)S * nb * L, hipMemcpyDeviceToDevice, qs));
     return WSEG_OK;
-  };
+  }
 
-  // encoder + cross-K/V of the consecutive windows [w0, w0 + n) into the slots listed at q.adm_slots + off (device)
-  auto encode_run = [&](int w0, int n, int off) -> int {
+  // encoder + cross-K/V of the consecutive windows [w0, w0 + n) into the slots listed at adm_slots + off (device)
+  int encode_run(int w0, int n, int off) {
+    Sched& ln = m->sched;
+    const wseg_model_config& c = m->cfg;
+    DecPlan& q = p.dec;
+    const int d = c.d_model, H = c.n_heads, Tk = c.enc_positions;
+    const size_t cross_stride = (size_t)S * H * Tk * cross_kv_row_bytes(kv24, m->es);
+    const size_t feat_stride = (size_t)c.n_mels * c.spec_cols;
     for (int c0 = 0; c0 < n; c0 += ENC_CHUNK) {
       const int nc = std::min(ENC_CHUNK, n - c0), wc = w0 + c0;
       int e0, e1, e2;
@@ -733,151 +675,101 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
       ln.ev_enc.push_back(e0); ln.ev_enc.push_back(e1); ln.ev_ckv.push_back(e1); ln.ev_ckv.push_back(e2);
     }
     return WSEG_OK;
-  };
-  // the first n windows of the queue into n free slots; their decode state starts at position 0
-  auto admit = [&](int n) -> int {
-    tmp_a.clear(); tmp_b.clear();
-    for (int i = 0; i < n; ++i) {
-      const int sl = free_slots.back(); free_slots.pop_back();
-      const int w = queue.front(); queue.pop_front();
-      tmp_a.push_back(sl); tmp_b.push_back(w);
-      slot_win[sl] = w; slot_from[sl] = t;
-    }
-    WSEG_TRY(h2d_list(ln, tmp_a.data(), n, q.adm_slots, s));
-    WSEG_TRY(h2d_list(ln, tmp_b.data(), n, q.adm_wins, s));
-    for (int i = 0; i < n;) {                      // runs of consecutive window indices (a re-queued window breaks a run)
-      int j = i + 1;
-      while (j < n && tmp_b[j] == tmp_b[j - 1] + 1) ++j;
-      WSEG_TRY(encode_run(tmp_b[i], j - i, i));
-      i = j;
-    }
-    WSEG_TRY(launch_decode_admit(st, q.adm_slots, q.adm_wins, n, NPF, merged ? P - 1 : NPF, s));
-    if (NPF > 0) {
-      // the first page of every admitted slot now (the refill rule left a pool unit for each), then the prompt pass in chunks that fit
-      // the decode step's row buffers
-      tmp_b.clear();
-      for (int i = 0; i < n; ++i) {
-        const int sl = tmp_a[i];
-        if (free_units.empty()) { set_error("admission without a pool unit per window"); return WSEG_ERR_STATE; }
-        const int u = free_units.back(); free_units.pop_back();
-        slot_units[sl].push_back(u);
-        ++units_in_use;
-        tmp_b.push_back(sl * npg); tmp_b.push_back(u);
-      }
-      if (units_in_use > stats.kv_units_peak) stats.kv_units_peak = units_in_use;
-      WSEG_TRY(h2d_list(ln, tmp_b.data(), (int)tmp_b.size(), q.kv_pairs, s));
-      WSEG_TRY(launch_kv_assign(q.kv_pt, q.kv_pairs, n, s));
-      const int plan_rows = std::max(S * nb, NPF), chunk = std::max(1, std::min(q.row_cap, plan_rows) / NPF);
-      for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int nc = std::min(chunk, n - c0);
-        const PromptPass pp = {q.adm_slots + c0, nc, NPF, merged, plan_rows};
-        WSEG_TRY(run_decoder_step(m, q, p.mxa, false, s, &pp));
-        if (merged) {
-          if (snap_ok && stats.n_admissions == 0) {      // wseg_debug_first_logits (all windows of the call start together: window i sits in slot i): every beam row of
-            for (int j = 0; j < nb; ++j)      // a window gets the window's row
-              WSEG_HIP_CHECK(hipMemcpy2DAsync(q.first_logits + ((size_t)c0 * nb + j) * m->vp * 4, (size_t)nb * m->vp * 4, q.logits, (size_t)m->vp * 4,
-                                              (size_t)m->vp * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
-            if (c0 + nc == n) m->first_logits_valid = true;
-            const int si = snap_index(P - 1);
-            if (si >= 0) {      // the same rows as a step snapshot record
-              char* rec = sn.out + (size_t)si * sl_.total;
-              for (int j = 0; j < nb; ++j)
-                WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + sl_.logits + ((size_t)c0 * nb + j) * c.vocab * 4, (size_t)nb * c.vocab * 4, q.logits,
-                                                (size_t)m->vp * 4, (size_t)c.vocab * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
-              if (c0 == 0) { WSEG_TRY(snap_state(rec, s)); ++snap_taken; }
-            }
-          }
-          WSEG_TRY(launch_row_topk(st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, s, q.adm_slots + c0, nc));
-          if (nb == 1) WSEG_TRY(launch_greedy_step(st, s, q.adm_slots + c0, nc));
-          else WSEG_TRY(launch_beam_step(st, s, q.adm_slots + c0, nc));
+  }
+
+  // the prompt pass of an admission of n windows, in chunks that fit the decode step's row buffers; merged: it also runs the first
+  // generated step, whose bookkeeping (candidates from the window's one logits row, beam / greedy step on the admitted list) follows
+  // each chunk.  tap: this is the one admission of a call whose windows all start together.
+  int prompt_pass(int n, bool tap) {
+    const wseg_model_config& c = m->cfg;
+    DecPlan& q = p.dec;
+    const DecodeState& st = q.st;
+    const int plan_rows = std::max(S * nb, NPF), chunk = std::max(1, std::min(q.row_cap, plan_rows) / NPF);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+      const int nc = std::min(chunk, n - c0);
+      const PromptPass pp = {q.adm_slots + c0, nc, NPF, merged, plan_rows};
+      WSEG_TRY(run_decoder_step(m, q, p.mxa, false, s, &pp));
+      if (!merged) continue;
+      if (tap) {      // wseg_debug_first_logits: every beam row of a window gets the window's row
+        for (int j = 0; j < nb; ++j)
+          WSEG_HIP_CHECK(hipMemcpy2DAsync(q.first_logits + ((size_t)c0 * nb + j) * m->vp * 4, (size_t)nb * m->vp * 4, q.logits, (size_t)m->vp * 4,
+                                          (size_t)m->vp * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
+        if (c0 + nc == n) m->first_logits_valid = true;
+        const int si = taps.index(P - 1);
+        if (si >= 0) {      // the same rows as a step snapshot record
+          char* rec = taps.record(si);
+          for (int j = 0; j < nb; ++j)
+            WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + taps.lay.logits + ((size_t)c0 * nb + j) * c.vocab * 4, (size_t)nb * c.vocab * 4, q.logits,
+                                            (size_t)m->vp * 4, (size_t)c.vocab * 4, (size_t)nc, hipMemcpyDeviceToDevice, s));
+          if (c0 == 0) { WSEG_TRY(snap_state(rec, s)); ++taps.taken; }
         }
       }
-    }
-    in_flight += n;
-    stats.n_admissions += 1;
-    return WSEG_OK;
-  };
-  // take a slot out of flight without output (its window goes back to the head of the queue)
-  auto preempt = [&](int sl) -> int {
-    WSEG_TRY(h2d_list(ln, &sl, 1, q.ret_slots, s));
-    WSEG_TRY(launch_decode_abort(st, q.ret_slots, 1, s));
-    queue.push_front(slot_win[sl]);
-    slot_win[sl] = -1;
-    for (int u : slot_units[sl]) free_units.push_back(u);
-    units_in_use -= (int)slot_units[sl].size();
-    slot_units[sl].clear();
-    free_slots.push_back(sl);
-    std::sort(free_slots.begin(), free_slots.end(), [](int a, int b) { return a > b; });
-    --in_flight;
-    stats.n_preemptions += 1;
-    hold_admission = true;
-    return WSEG_OK;
-  };
-  // pool units for every occupied slot that enters a new page at step t (position t - slot_from: the host's upper bound — a slot
-  // that finished inside the look-ahead window is idle on the device and simply does not use the page)
-  auto assign_pages = [&]() -> int {
-    tmp_a.clear();
-    for (int sl = 0; sl < S; ++sl) {
-      if (slot_win[sl] < 0) continue;
-      const int pos = t - slot_from[sl] + POS0;
-      if (pos >= L || pos % KV_PAGE) continue;
-      while (free_units.empty()) {
-        int victim = -1;                                // youngest slot that holds pages (never the requester)
-        for (int v = 0; v < S; ++v)
-          if (v != sl && slot_win[v] >= 0 && !slot_units[v].empty() && (victim < 0 || slot_from[v] >= slot_from[victim])) victim = v;
-        if (victim < 0) { set_error("self-attention K/V pool exhausted by one window (pool of %d units)", kv_units); return WSEG_ERR_STATE; }
-        // an assignment already queued for the victim in this pass is void: drop it
-        for (size_t i = 0; i + 1 < tmp_a.size();) { if (tmp_a[i] / npg == victim) tmp_a.erase(tmp_a.begin() + i, tmp_a.begin() + i + 2); else i += 2; }
-        WSEG_TRY(preempt(victim));
-      }
-      const int u = free_units.back(); free_units.pop_back();
-      slot_units[sl].push_back(u);
-      ++units_in_use;
-      tmp_a.push_back(sl * npg + pos / KV_PAGE); tmp_a.push_back(u);
-    }
-    if (units_in_use > stats.kv_units_peak) stats.kv_units_peak = units_in_use;
-    if (!tmp_a.empty()) {
-      WSEG_TRY(h2d_list(ln, tmp_a.data(), (int)tmp_a.size(), q.kv_pairs, s));
-      WSEG_TRY(launch_kv_assign(q.kv_pt, q.kv_pairs, (int)tmp_a.size() / 2, s));
+      WSEG_TRY(launch_row_topk(st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, s, q.adm_slots + c0, nc));
+      if (nb == 1) WSEG_TRY(launch_greedy_step(st, s, q.adm_slots + c0, nc));
+      else WSEG_TRY(launch_beam_step(st, s, q.adm_slots + c0, nc));
     }
     return WSEG_OK;
-  };
+  }
+
+  // an admission: two lists, encoder + cross K/V per run of consecutive windows, the admit kernel (decode state at position 0), and
+  // with a prompt pass the slots' first pages and the pass
+  int admit(const SlotScheduler::Admission& a, bool tap) {
+    DecPlan& q = p.dec;
+    const int n = (int)a.slots.size();
+    WSEG_TRY(h2d_list(m->sched, a.slots.data(), n, q.adm_slots, s));
+    WSEG_TRY(h2d_list(m->sched, a.wins.data(), n, q.adm_wins, s));
+    for (size_t i = 0; i < a.runs.size(); i += 2) WSEG_TRY(encode_run(a.wins[a.runs[i]], a.runs[i + 1], a.runs[i]));
+    WSEG_TRY(launch_decode_admit(q.st, q.adm_slots, q.adm_wins, n, NPF, merged ? P - 1 : NPF, s));
+    if (NPF == 0) return WSEG_OK;
+    WSEG_TRY(assign_pages(a.first_pages));
+    return prompt_pass(n, tap);
+  }
+
+  // one page-table update: kv_pt[pairs[2 i]] = pairs[2 i + 1]
+  int assign_pages(const std::vector<int>& pairs) {
+    if (pairs.empty()) return WSEG_OK;
+    WSEG_TRY(h2d_list(m->sched, pairs.data(), (int)pairs.size(), p.dec.kv_pairs, s));
+    return launch_kv_assign(p.dec.kv_pt, p.dec.kv_pairs, (int)pairs.size() / 2, s);
+  }
+
+  // preemption: the slot stops decoding without output
+  int abort(int sl) {
+    WSEG_TRY(h2d_list(m->sched, &sl, 1, p.dec.ret_slots, s));
+    return launch_decode_abort(p.dec.st, p.dec.ret_slots, 1, s);
+  }
 
   // One decode step of every active slot: decoder layers, LM head, candidates, bookkeeping (which also advances the slot).
-  auto enqueue_step = [&](bool snapshot_logits, hipStream_t qs, char* rec = nullptr) -> int {
+  int enqueue_step(bool snapshot_logits, hipStream_t qs, char* rec = nullptr) {
+    DecPlan& q = p.dec;
     WSEG_TRY(run_decoder_step(m, q, p.mxa, true, qs));
     if (snapshot_logits)
       WSEG_HIP_CHECK(hipMemcpyAsync(q.first_logits, q.logits, (size_t)S * nb * m->vp * 4, hipMemcpyDeviceToDevice, qs));
     if (rec) {
-      WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + sl_.logits, (size_t)c.vocab * 4, q.logits, (size_t)m->vp * 4, (size_t)c.vocab * 4, (size_t)S * nb,
-                                      hipMemcpyDeviceToDevice, qs));
+      WSEG_HIP_CHECK(hipMemcpy2DAsync(rec + taps.lay.logits, (size_t)m->cfg.vocab * 4, q.logits, (size_t)m->vp * 4, (size_t)m->cfg.vocab * 4,
+                                      (size_t)S * nb, hipMemcpyDeviceToDevice, qs));
       WSEG_TRY(snap_state(rec, qs));
     }
-    WSEG_TRY(launch_row_topk(st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, qs));
-    if (nb == 1) WSEG_TRY(launch_greedy_step(st, qs));
-    else WSEG_TRY(launch_beam_step(st, qs));
+    WSEG_TRY(launch_row_topk(q.st, (const float*)q.logits, (float*)q.tk_val, (int*)q.tk_idx, (float*)q.tk_stat, qs));
+    if (nb == 1) WSEG_TRY(launch_greedy_step(q.st, qs));
+    else WSEG_TRY(launch_beam_step(q.st, qs));
     return WSEG_OK;
-  };
-  // The step reads every step-dependent value (positions, tokens, ancestry, idle flags, the page table, the sampling seed) from
-  // device memory, so ONE captured graph serves all steps and later calls: replay costs ~1.6 us per kernel instead of ~5 us per
+  }
+
+  // Step t.  The step reads every step-dependent value (positions, tokens, ancestry, idle flags, the page table, the sampling seed)
+  // from device memory, so ONE captured graph serves all steps and later calls: replay costs ~1.6 us per kernel instead of ~5 us per
   // eager launch.  The key holds what the captured kernels take BY VALUE; per-window length caps are applied by the
   // admission kernel (launched outside the graph) and the weight pointers invalidate the key in wseg_model_set_tensor.
-  static const bool use_graph = getenv("WSEG_NO_GRAPH") == nullptr;
-  std::vector<unsigned char> key;
-  {
-    auto put = [&](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; key.insert(key.end(), b, b + n); };
-    put(&base, sizeof(base)); put(&S, 4); put(&nb, 4); put(&L, 4); put(&kv_units, 4);
-    put(&st.P, 4); put(&st.eos, 4); put(&st.pad, 4); put(&st.length_penalty, 4); put(st.prompt, sizeof(st.prompt));
-    put(&st.top_k, 4); put(&st.top_p, 4);
-  }
-  auto launch_step = [&]() -> int {
+  // tap_ok: the call's windows started together and none has been preempted (every slot is at position t + POS0).
+  int launch_step(int t, bool tap_ok) {
+    static const bool use_graph = getenv("WSEG_NO_GRAPH") == nullptr;
+    Sched& ln = m->sched;
     // the first generated step of a call whose windows all start together is launched eagerly with the logits snapshot
     // (wseg_debug_first_logits); every other step replays the graph
-    const bool snap = !merged && t == P - 1 - POS0 && snap_ok && stats.n_preemptions == 0;
+    const bool snap = !merged && t == P - 1 - POS0 && tap_ok;
     if (snap) m->first_logits_valid = true;
-    // ... and so is a step named by wseg_debug_step_snapshot_arm (every slot is at position t + POS0: they started together)
-    const int si = snap_ok && stats.n_preemptions == 0 ? snap_index(t + POS0) : -1;
-    if (si >= 0) { ++snap_taken; return enqueue_step(snap, s, sn.out + (size_t)si * sl_.total); }
+    // ... and so is a step named by wseg_debug_step_snapshot_arm
+    const int si = tap_ok ? taps.index(t + POS0) : -1;
+    if (si >= 0) { ++taps.taken; return enqueue_step(snap, s, taps.record(si)); }
     if (snap || !use_graph) return enqueue_step(snap, s);
     if (!ln.step_graph || ln.step_graph_key != key) {
       if (ln.step_graph) { (void)hipGraphExecDestroy(ln.step_graph); ln.step_graph = nullptr; }
@@ -894,91 +786,122 @@ static int generate_windows(wseg_model* m, const float* feats, int n_windows, co
     }
     WSEG_HIP_CHECK(hipGraphLaunch(ln.step_graph, s));
     return WSEG_OK;
-  };
-
-  // status mirror of step u lives in ring entry status_idx[u % N]
-  int status_idx[PinnedRing::N];
-  bool step_queued[PinnedRing::N];             // were windows still waiting in the queue when the step was launched?
-  auto consume_status = [&](int u) -> int {      // retire every slot that step u left finished
-    const int ri = status_idx[u % PinnedRing::N];
-    WSEG_HIP_CHECK(hipEventSynchronize(ln.ring_status.ev[ri]));
-    ln.ring_status.used[ri] = false;
-    const int* done = ln.ring_status.host + (size_t)ri * ln.ring_status.cap;
-    tmp_a.clear();
-    int active = 0;
-    for (int sl = 0; sl < S; ++sl) {
-      if (slot_win[sl] < 0 || u < slot_from[sl]) continue;
-      if (done[sl]) { tmp_a.push_back(sl); slot_win[sl] = -1; }
-      else ++active;
-    }
-    stats.slot_steps_active += active + (int64_t)tmp_a.size();
-    if (step_queued[u % PinnedRing::N]) {
-      stats.queued_slot_steps_active += active + (int64_t)tmp_a.size();
-      stats.queued_slot_steps_total += S;
-    }
-    if (!tmp_a.empty()) {
-      const int n = (int)tmp_a.size();
-      WSEG_TRY(h2d_list(ln, tmp_a.data(), n, q.ret_slots, s));
-      WSEG_TRY(launch_finalize(st, q.ret_slots, n, out_tokens, out_lengths, s));
-      for (int sl : tmp_a) {
-        free_slots.push_back(sl);
-        for (int v : slot_units[sl]) free_units.push_back(v);
-        units_in_use -= (int)slot_units[sl].size();
-        slot_units[sl].clear();
-      }
-      std::sort(free_slots.begin(), free_slots.end(), [](int a, int b) { return a > b; });
-      in_flight -= n;
-      hold_admission = false;
-    }
-    return WSEG_OK;
-  };
-
-  int consumed = 0;                               // statuses of steps [0, consumed) have been processed
-  while (true) {
-    const int rem = (int)queue.size();
-    if (rem > 0 && !(hold_admission && in_flight > 0)) {
-      // refill rule: enough free slots, or the rest of the queue, or nothing else is running — and a pool unit for every
-      // admitted window on top of one spare unit per window in flight (16+ steps without a preemption)
-      int n_adm = std::min(rem, (int)free_slots.size());
-      const int spare = (int)free_units.size() - in_flight;
-      n_adm = std::min(n_adm, in_flight == 0 ? (int)free_units.size() : std::max(spare, 0));
-      if (n_adm > 0 && (n_adm >= G || n_adm == rem || in_flight == 0)) {
-        if (first_admission) snap_ok = n_adm == n_windows;
-        first_admission = false;
-        WSEG_TRY(admit(n_adm));
-      }
-    }
-    const bool drained = queue.empty();
-    if (in_flight == 0) {
-      if (!drained) { set_error("scheduler stalled with %d windows queued", (int)queue.size()); return WSEG_ERR_STATE; }
-      break;
-    }
-    if (drained) {                // nothing left to admit later: stop launching once every window in flight must have ended
-      bool may_run = false;       // (a window admitted before step f feeds its last position, L - 2, at step f + L - 2 - POS0)
-      for (int sl = 0; sl < S && !may_run; ++sl) may_run = slot_win[sl] >= 0 && t < slot_from[sl] + L - 1 - POS0;
-      if (!may_run) break;
-    }
-    WSEG_TRY(assign_pages());
-    WSEG_TRY(launch_step());
-    {   // mirror the idle flags of this step
-      int ri;
-      WSEG_TRY(ring_acquire(ln.ring_status, &ri));
-      WSEG_HIP_CHECK(hipMemcpyAsync(ln.ring_status.host + (size_t)ri * ln.ring_status.cap, st.done, (size_t)S * sizeof(int),
-                                    hipMemcpyDeviceToHost, s));
-      WSEG_HIP_CHECK(hipEventRecord(ln.ring_status.ev[ri], s));
-      ln.ring_status.used[ri] = true;
-      status_idx[t % PinnedRing::N] = ri;
-      step_queued[t % PinnedRing::N] = !drained;
-    }
-    ++t;
-    stats.slot_steps_total += S;
-    // stay at most K steps ahead of the device
-    while (consumed < t - K) WSEG_TRY(consume_status(consumed++));
   }
-  while (consumed < t) WSEG_TRY(consume_status(consumed++));
-  if (in_flight != 0 || !queue.empty()) { set_error("scheduler ended with %d windows in flight, %d queued", in_flight, (int)queue.size()); return WSEG_ERR_STATE; }
-  stats.n_steps = t;
-  if (sn.n > 0 && snap_ok && stats.n_preemptions == 0) m->snap_taken = snap_taken;
+
+  // mirror the idle flags step t left behind
+  int mirror_status(int t) {
+    PinnedRing& r = m->sched.ring_status;
+    int ri;
+    WSEG_TRY(ring_acquire(r, &ri));
+    WSEG_HIP_CHECK(hipMemcpyAsync(r.host + (size_t)ri * r.cap, p.dec.st.done, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, s));
+    WSEG_HIP_CHECK(hipEventRecord(r.ev[ri], s));
+    r.used[ri] = true;
+    status_idx[t % PinnedRing::N] = ri;
+    return WSEG_OK;
+  }
+
+  // wait for the status of step u, let the scheduler retire, finalize every slot that step left finished
+  int retire_step(SlotScheduler& sch, int u) {
+    PinnedRing& r = m->sched.ring_status;
+    const int ri = status_idx[u % PinnedRing::N];
+    WSEG_HIP_CHECK(hipEventSynchronize(r.ev[ri]));
+    r.used[ri] = false;
+    const std::vector<int>& fin = sch.retire(u, r.host + (size_t)ri * r.cap);
+    if (fin.empty()) return WSEG_OK;
+    WSEG_TRY(h2d_list(m->sched, fin.data(), (int)fin.size(), p.dec.ret_slots, s));
+    return launch_finalize(p.dec.st, p.dec.ret_slots, (int)fin.size(), out_tokens, out_lengths, s);
+  }
+};
+
+static int sched_failed(const SlotScheduler& sch) { set_error("%s", sch.error()); return WSEG_ERR_STATE; }
+static void put_sched_stats(const SchedStats& a, wseg_generate_stats* out) {
+  out->n_steps = a.n_steps; out->n_admissions = a.n_admissions; out->kv_units_peak = a.kv_units_peak; out->n_preemptions = a.n_preemptions;
+  out->slot_steps_active = a.slot_steps_active; out->slot_steps_total = a.slot_steps_total;
+  out->queued_slot_steps_active = a.queued_slot_steps_active; out->queued_slot_steps_total = a.queued_slot_steps_total;
+}
+
+// Decode of n_windows windows through S window slots on stream s: the per-call set-up, then the loop that asks the slot scheduler
+// (wseg_sched.h: the policy, and the long story) what to do and enqueues it.
+static int generate_windows(wseg_model* m, const float* feats, int n_windows, const wseg_generate_params* gp, char* base, int S,
+                            int kv_units, int32_t* out_tokens, int32_t* out_lengths, hipStream_t s) {
+  Sched& ln = m->sched;
+  const wseg_model_config& c = m->cfg;
+  const int nb = gp->num_beams, P = gp->prompt_len, L = gp->max_length;
+  GenerateRun r;
+  r.m = m; r.feats = feats; r.gp = gp; r.S = S; r.nb = nb; r.P = P; r.L = L; r.out_tokens = out_tokens; r.out_lengths = out_lengths; r.s = s;
+  make_plan(m, S, nb, L, kv_units, base, r.p);
+  DecPlan& q = r.p.dec;
+  DecodeState& st = q.st;
+  st.P = P; st.eos = gp->eos_token_id; st.pad = gp->pad_token_id; st.max_length = L; st.length_penalty = gp->length_penalty;
+  for (int i = 0; i < 8; ++i) st.prompt[i] = i < P ? gp->prompt[i] : 0;
+  st.win_max_length = gp->window_max_length;
+  st.top_k = (nb == 1 && gp->top_k > 1) ? gp->top_k : 1;
+  st.top_p = gp->top_p;
+  st.seed = (const unsigned long long*)q.seed_dev;
+  WSEG_TRY(ring_prepare(ln.ring_h2d, 2 * S > 2 ? 2 * S : 2));
+  WSEG_TRY(ring_prepare(ln.ring_status, S));
+  m->stats = wseg_generate_stats();
+  m->stats.n_windows = n_windows; m->stats.n_slots = S; m->stats.kv_units_total = kv_units;
+  {   // the seed lives in device memory (read by the sampling kernel): per-call values do not invalidate the step graph
+    const unsigned long long sd = gp->seed;
+    int words[2];
+    memcpy(words, &sd, 8);
+    WSEG_TRY(h2d_list(ln, words, 2, q.seed_dev, s));
+  }
+  WSEG_TRY(launch_build_suppress_mask((unsigned char*)q.mask, c.vocab, gp->suppress_tokens, gp->n_suppress,
+                                      gp->begin_suppress_tokens, gp->n_begin_suppress, s));
+  WSEG_TRY(launch_decode_reset(st, s));
+  WSEG_HIP_CHECK(hipMemsetAsync(q.zeros, 0, (size_t)S * sizeof(int), s));
+
+  r.kv24 = m->x3 ? x3_cross_kv_format(c.dtype, nb) : 0;
+  // prompt pass: the first NPF forced positions of every admission run as one pass (run_decoder_step, PromptPass) and the slots start
+  // at position NPF.  Split-precision modes up to 4 beams (24-bit / block-floating-point cross K / V); the f32 and plain 16-bit modes step through the prompt.
+  const bool prompt_pass = getenv("WSEG_NO_PROMPT_PASS") == nullptr;      // test knob (read per call): step through the prompt instead
+  // ... and when the whole prompt fits the pass (P <= 4) and a step follows anyway (L >= P + 2), the pass also runs position P - 1 — the FIRST
+  // GENERATED step, whose beams are still copies: one row per window through the layers and the LM head instead of a full decode step of every
+  // beam row (which would stream the windows' cross K / V once more) — and the admission finishes that step's bookkeeping for its slots.
+  // NPF: positions the pass covers; POS0: the position the slot is at when the decode loop first steps it.
+  const bool pass_ok = prompt_pass && m->x3 && r.kv24 != 0;
+  r.merged = pass_ok && P <= 4 && L >= P + 2 && getenv("WSEG_NO_FIRST_STEP_MERGE") == nullptr;
+  r.NPF = !pass_ok ? 0 : (r.merged ? P : std::min(P - 1, 4));
+  r.POS0 = r.merged ? P : r.NPF;
+
+  m->first_logits_valid = false;
+  r.taps.req = m->snap_req;      // armed for this call only
+  m->snap_req = StepSnap();
+  m->snap_taken = -1;
+  m->snap_qkv_split = -1;
+  r.taps.lay = snap_layout(S, nb, L, c.vocab);
+  if (r.taps.req.n > 0 && r.taps.req.bytes < (size_t)r.taps.req.n * r.taps.lay.total) {
+    set_error("step snapshot: %d records of %zu bytes do not fit the %zu-byte buffer", r.taps.req.n, r.taps.lay.total, r.taps.req.bytes);
+    return WSEG_ERR_INVALID;
+  }
+  {
+    auto put = [&r](const void* ptr, size_t n) { const unsigned char* b = (const unsigned char*)ptr; r.key.insert(r.key.end(), b, b + n); };
+    put(&base, sizeof(base)); put(&S, 4); put(&nb, 4); put(&L, 4); put(&kv_units, 4);
+    put(&st.P, 4); put(&st.eos, 4); put(&st.pad, 4); put(&st.length_penalty, 4); put(st.prompt, sizeof(st.prompt));
+    put(&st.top_k, 4); put(&st.top_p, 4);
+  }
+
+  SlotScheduler sch(n_windows, S, kv_units, L, r.NPF, r.POS0, gp->refill_min, gp->lookahead);
+  while (true) {
+    if (const SlotScheduler::Admission* a = sch.plan_admission())
+      WSEG_TRY(r.admit(*a, sch.started_together() && sch.stats().n_admissions == 1));
+    if (!sch.ok() || !sch.more_steps()) break;
+    const SlotScheduler::Pages& pages = sch.plan_pages();
+    if (!sch.ok()) break;
+    for (int sl : pages.preempt) WSEG_TRY(r.abort(sl));
+    WSEG_TRY(r.assign_pages(pages.pairs));
+    WSEG_TRY(r.launch_step(sch.t(), sch.started_together() && sch.stats().n_preemptions == 0));
+    WSEG_TRY(r.mirror_status(sch.t()));
+    sch.step_launched();
+    for (int u; (u = sch.status_due()) >= 0;) WSEG_TRY(r.retire_step(sch, u));
+  }
+  if (!sch.ok()) return sched_failed(sch);
+  for (int u; (u = sch.status_due(true)) >= 0;) WSEG_TRY(r.retire_step(sch, u));
+  if (!sch.finish()) return sched_failed(sch);
+  put_sched_stats(sch.stats(), &m->stats);
+  if (r.taps.req.n > 0 && sch.started_together() && sch.stats().n_preemptions == 0) m->snap_taken = r.taps.taken;
   return WSEG_OK;
 }
 
@@ -1029,6 +952,65 @@ extern "C" int wseg_generate(wseg_model* m, const float* feats, int32_t n_window
   WSEG_TRY(timing_event(sc, s, &m->ev_total[1]));
   m->last_W = S; m->last_nb = nb; m->last_L = L; m->last_units = (int)units;
   m->timing_valid = true;
+  return WSEG_OK;
+}
+
+// Scripted device behind wseg_debug_sched_trace: slot sl still has left[sl] decode-loop steps to run before it reports done.
+namespace {
+struct SchedTrace {
+  int32_t* out; int64_t cap, n;
+  std::vector<int> left, done, status;      // status: the done flags as each of the last SCHED_RING steps left them
+  void ev(int kind, int a, int b, int c) {
+    if (out && n + 4 <= cap) { out[n] = kind; out[n + 1] = a; out[n + 2] = b; out[n + 3] = c; }
+    n += 4;
+  }
+  void pages(const std::vector<int>& pairs, int npg) { for (size_t i = 0; i + 1 < pairs.size(); i += 2) ev(2, pairs[i] / npg, pairs[i] % npg, pairs[i + 1]); }
+  void retire(SlotScheduler& sch, int u) {
+    const size_t S = done.size();
+    for (int sl : sch.retire(u, status.data() + (size_t)(u % SCHED_RING) * S)) ev(5, sl, u, 0);
+  }
+};
+}  // namespace
+
+extern "C" int wseg_debug_sched_trace(int32_t n_windows, int32_t n_slots, int32_t kv_units, int32_t max_length, int32_t npf, int32_t pos0,
+                                      int32_t refill_min, int32_t lookahead, const int32_t* done_after, wseg_generate_stats* stats,
+                                      int32_t* trace, int64_t trace_cap, int64_t* trace_len) {
+  if (n_windows <= 0 || n_slots <= 0 || kv_units < 0 || max_length <= 0 || npf < 0 || pos0 < npf || refill_min < 0 || lookahead < 0 ||
+      !done_after || !stats || !trace_len || trace_cap < 0) {
+    set_error("wseg_debug_sched_trace: bad argument"); return WSEG_ERR_INVALID;
+  }
+  const int S = n_slots, npg = kv_pages(max_length);
+  SlotScheduler sch(n_windows, S, kv_units, max_length, npf, pos0, refill_min, lookahead);
+  SchedTrace tr = {trace, trace_cap, 0, std::vector<int>(S, 0), std::vector<int>(S, 1), std::vector<int>((size_t)SCHED_RING * S, 1)};
+  while (true) {
+    if (const SlotScheduler::Admission* a = sch.plan_admission()) {
+      for (size_t i = 0; i < a->slots.size(); ++i) {
+        const int sl = a->slots[i];
+        tr.ev(1, sl, a->wins[i], 0);
+        tr.left[sl] = done_after[a->wins[i]];
+        tr.done[sl] = tr.left[sl] <= 0;
+      }
+      tr.pages(a->first_pages, npg);
+    }
+    if (!sch.ok() || !sch.more_steps()) break;
+    const SlotScheduler::Pages& pages = sch.plan_pages();
+    if (!sch.ok()) break;
+    for (int sl : pages.preempt) { tr.ev(3, sl, 0, 0); tr.done[sl] = 1; }
+    tr.pages(pages.pairs, npg);
+    tr.ev(4, sch.t(), 0, 0);
+    for (int sl = 0; sl < S; ++sl) if (!tr.done[sl] && --tr.left[sl] <= 0) tr.done[sl] = 1;
+    std::copy(tr.done.begin(), tr.done.end(), tr.status.begin() + (size_t)(sch.t() % SCHED_RING) * S);
+    sch.step_launched();
+    for (int u; (u = sch.status_due()) >= 0;) tr.retire(sch, u);
+  }
+  if (!sch.ok()) return sched_failed(sch);
+  for (int u; (u = sch.status_due(true)) >= 0;) tr.retire(sch, u);
+  if (!sch.finish()) return sched_failed(sch);
+  *stats = wseg_generate_stats();
+  stats->n_windows = n_windows; stats->n_slots = S; stats->kv_units_total = kv_units;
+  put_sched_stats(sch.stats(), stats);
+  *trace_len = tr.n;
+  if (trace && tr.n > trace_cap) { set_error("wseg_debug_sched_trace: the trace needs %lld entries, the buffer holds %lld", (long long)tr.n, (long long)trace_cap); return WSEG_ERR_INVALID; }
   return WSEG_OK;
 }
 
