@@ -159,3 +159,62 @@ def test_the_lint_finds_planted_defects(tmp_path):
     assert kinds == {("_Z4bad1v", "valu"), ("_Z4bad2v", "non-MFMA")}, r["findings"]      # (names demangle only for kernels with metadata)
     k = r["kernels"]["_Z4loopv"]
     assert k["scratch"] == 4 and k["vgpr_spill"] == 1 and k["scratch_in_loop"] == 1
+
+
+BODY_A = """
+_Z1kv:                                  ; @_Z1kv
+\ts_load_dword s2, s[0:1], 0x0
+.LBB7_1:                                ; %loop
+\tv_add_u32_e32 v1, v1, v0                 ; a comment
+\ts_cbranch_scc1 .LBB7_1
+.Ltmp12:
+\ts_endpgm
+.Lfunc_end7:
+_Z1gv:                                  ; @_Z1gv
+\ts_endpgm
+amdhsa.kernels:
+  - .agpr_count:     0
+    .name:           _Z1kv
+    .symbol:         _Z1kv.kd
+    .vgpr_count:     2
+  - .agpr_count:     0
+    .name:           _Z1gv
+    .symbol:         _Z1gv.kd
+    .vgpr_count:     1
+"""
+
+
+def test_the_diff_compares_kernel_bodies(tmp_path):
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import isa_lint
+    finally:
+        sys.path.pop(0)
+    relabelled = BODY_A.replace(".LBB7_1", ".LBB3_4").replace(".Ltmp12", ".Ltmp0").replace("a comment", "another comment")
+    changed = BODY_A.replace("v_add_u32_e32 v1, v1, v0", "v_sub_u32_e32 v1, v1, v0")
+    missing = BODY_A[:BODY_A.index("_Z1gv:")] + BODY_A[BODY_A.index("amdhsa.kernels:"):BODY_A.index("  - .agpr_count:     0\n    .name:           _Z1gv")]
+    dirs = {}
+    for name, text in (("a", BODY_A), ("same", relabelled), ("changed", changed), ("missing", missing)):
+        d = tmp_path / name
+        d.mkdir()
+        (d / "k.s").write_text(text)
+        digest = isa_lint.analyze(str(d / "k.s"))
+        with open(d / "k.lint.json", "w") as f:
+            json.dump(digest, f)
+        dirs[name] = (str(d), digest)
+    h = {n: dg["kernels"]["_Z1kv"]["body_hash"] for n, (_, dg) in dirs.items()}
+    assert h["a"] == h["same"] == h["missing"] and h["a"] != h["changed"]
+    assert h["a"] != dirs["a"][1]["kernels"]["_Z1gv"]["body_hash"]
+    a = dirs["a"][0]
+    assert isa_lint.diff(a, dirs["same"][0])[0] == []
+    rows = isa_lint.diff(a, dirs["changed"][0])[0]
+    assert len(rows) == 1 and rows[0].startswith("differs") and rows[0].endswith(": k"), rows
+    rows = isa_lint.diff(a, dirs["missing"][0])[0]
+    assert len(rows) == 1 and rows[0].startswith("only in A") and rows[0].endswith(": g"), rows
+    rows = isa_lint.diff(dirs["missing"][0], a)[0]
+    assert len(rows) == 1 and rows[0].startswith("only in B"), rows
+    import subprocess
+    tool = os.path.join(ROOT, "tools", "isa_lint.py")
+    assert subprocess.run([sys.executable, tool, "--diff", a, dirs["same"][0]], capture_output=True).returncode == 0
+    assert subprocess.run([sys.executable, tool, "--diff", a, dirs["changed"][0]], capture_output=True).returncode != 0

@@ -2,10 +2,16 @@
 
     python tools/isa_lint.py FILE.s [...]          # prints one line per kernel with scratch, spills or findings
 
+    python tools/isa_lint.py --diff DIR_A DIR_B    # same device code?  compares the *.lint.json digests of two build directories
+
 `analyze(path)` reads the device assembly hipcc leaves behind with -save-temps (whisperseg_amd/build.py keeps a digest of it per
 source file as build/<name>.lint.json) and returns
 
-  kernels : {mangled name: {demangled, vgpr, agpr, sgpr, lds, scratch, vgpr_spill, sgpr_spill}}   from the amdhsa.kernels metadata
+  kernels : {mangled name: {demangled, vgpr, agpr, sgpr, lds, scratch, vgpr_spill, sgpr_spill}}   from the amdhsa.kernels metadata,
+            plus body_hash: SHA-256 of the kernel's labels and instructions with comments dropped and the local labels (.LBB*, .Ltmp*)
+            renumbered in order of appearance — equal for two builds exactly when the compiler emitted the same code for the kernel
+            (`--diff` lists symbols only in A, only in B and with differing bodies, and exits 1 if there is any: the check of a
+            source-only refactor)
   findings: hazards around the inline-assembly MX MFMAs (`v_mfma_scale_f32_16x16x128_f8f6f4`, csrc/wseg_gemm.hip mfma_mx6_asm):
             hipcc treats an asm statement as one opaque instruction and pads none of its hazards (cdna_hip_programming.md §5.7):
               * a compiler-placed VALU write (v_mov, v_accvgpr_*, a conversion ...) of one of the instruction's A / B / scale registers
@@ -15,13 +21,17 @@ source file as build/<name>.lint.json) and returns
 
 tests/test_isa_lint.py asserts on the digest: no scratch and no spills in any kernel of the product's hot path (allow-listed
 exceptions carry a measured reason), register counts under their occupancy steps, no findings."""
+import glob
+import hashlib
 import json
+import os
 import re
 import subprocess
 import sys
 
 _BLOCK = re.compile(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)")      # basic-block label or fall-through block comment
 _FUNC = re.compile(r"^([A-Za-z_$][\w$.]*):")      # function label (hipcc appends "; @name")
+_LOCAL = re.compile(r"\.L(BB|tmp)\d+(?:_\d+)?")      # compiler-numbered local label
 _REG = re.compile(r"\b([vas])(?:(\d+)|\[(\d+):(\d+)\])")
 
 
@@ -61,6 +71,14 @@ def _slots(mn, rest):
         except ValueError:
             return 1
     return 1
+
+
+def _body_hash(body):
+    ids = {}
+    h = hashlib.sha256()
+    for ln in body:
+        h.update((_LOCAL.sub(lambda m: ids.setdefault(m.group(0), ".L%s%d" % (m.group(1), len(ids))), ln) + "\n").encode())
+    return h.hexdigest()
 
 
 def _parse_metadata(lines, start):
@@ -103,6 +121,7 @@ def analyze(path):
         k["demangled"] = dem.get(n, n)
     findings = []
     func, stream, in_asm = None, [], False      # stream: (in_asm, mnemonic, rest, line number)
+    body = []                                   # per function: label and instruction lines without comments (body_hash)
     block_head = False
     in_loop, n_loop_scratch = False, 0          # per function: is the current basic block part of a loop (hipcc annotates every block
                                                 # label with "in Loop: Header=..." / "=>This ... Loop Header"), scratch accesses in such blocks
@@ -112,6 +131,7 @@ def analyze(path):
         # it — the r04 bring-up lost 4x to one such lane offset
         if func is not None and func in kernels:
             kernels[func]["scratch_in_loop"] = n_loop_scratch
+            kernels[func]["body_hash"] = _body_hash(body)
 
     def flush():
         if func is None or not any(a and mn.startswith("v_mfma_scale") for a, mn, _, _ in stream):
@@ -152,7 +172,11 @@ def analyze(path):
             flush_loops()
             func, stream, in_asm = fm.group(1), [], False
             in_loop, n_loop_scratch = False, 0
+            body = []
             continue
+        text = ln.split(";")[0].strip()
+        if text and (text[0] != "." or _LOCAL.match(text)):
+            body.append(text)
         if _BLOCK.match(ln):                     # the annotation sits on the label line or on the comment lines right below it
             in_loop, block_head = "Loop" in ln, True
             continue
@@ -197,7 +221,27 @@ def summarize(res, only_problems=True):
     return rows
 
 
+def diff(dir_a, dir_b):
+    """Lines naming every kernel symbol that only one of two build directories' digests has, or whose body differs."""
+    def load(d):
+        out = {}
+        for f in sorted(glob.glob(os.path.join(d, "*.lint.json"))):
+            with open(f) as fh:
+                out.update({(os.path.basename(f), n): k for n, k in json.load(fh)["kernels"].items()})
+        return out
+    a, b = load(dir_a), load(dir_b)
+    name = lambda key: "%s: %s" % (key[0], (a.get(key) or b[key]).get("demangled", key[1]))
+    rows = ["only in A  " + name(k) for k in sorted(set(a) - set(b))] + ["only in B  " + name(k) for k in sorted(set(b) - set(a))]
+    rows += ["differs    " + name(k) for k in sorted(set(a) & set(b)) if a[k].get("body_hash") is None or a[k].get("body_hash") != b[k].get("body_hash")]
+    return rows, len(a), len(b)
+
+
 if __name__ == "__main__":
+    if "--diff" in sys.argv:
+        i = sys.argv.index("--diff")
+        rows, na, nb = diff(sys.argv[i + 1], sys.argv[i + 2])
+        print("\n".join(rows + ["%d kernel symbols in A, %d in B, %d line(s) of difference" % (na, nb, len(rows))]))
+        sys.exit(1 if rows else 0)
     allk = "--all" in sys.argv
     for p in [a for a in sys.argv[1:] if not a.startswith("--")]:
         r = analyze(p)

@@ -113,6 +113,15 @@ __host__ __device__ __forceinline__ int vt_tiled_index(int hd, int t) {
   const int k = t & 63, gi = (k >> 2) & 3;
   return (t >> 6) * 4096 + hd * 64 + ((2 * (k >> 4) + (gi & 1)) << 3) + ((gi >> 1) << 2) + (k & 3);
 }
+// The other planes of the encoder self-attention, THE definition for the GEMM epilogues that write them and the kernels that read them:
+// Q and K [bh][t_pad][64] (bh = window * heads + head), the row of position t ...
+__host__ __device__ __forceinline__ constexpr size_t enc_qk_index(size_t bh, int t_pad, int t) { return (bh * t_pad + t) * 64; }
+// ... and V^T in plain rows [bh][64 hd][t_pad]: key t of row = bh * 64 + hd (I = size_t), or of row hd inside a (window, head) block
+// (I = int, like vt_tiled_index)
+template <typename I> __host__ __device__ __forceinline__ constexpr I vt_plain_index(I row, int t_pad, int t) { return row * t_pad + t; }
+// start of the (window, head) block of V^T, plain or tiled (vt_tiled_index counts from here)
+__host__ __device__ __forceinline__ constexpr size_t enc_vt_block(size_t bh, int t_pad) { return vt_plain_index(bh * 64, t_pad, 0); }
+static_assert(vt_plain_index<size_t>(7 * 64 + 5, 512, 9) == enc_vt_block(7, 512) + vt_plain_index(5, 512, 9), "row = bh * 64 + hd");
 
 // Element-type traits: T = float (exact-parity mode), bf16_t or f16_t (production modes).
 template <typename T> struct El {      // 16-bit types
@@ -351,6 +360,12 @@ template <typename T> __device__ __forceinline__ void op_st4(void* base, size_t 
   }
 }
 
+// NC = 4 or 8 consecutive columns through the store of their width
+template <typename T, int NC> __device__ __forceinline__ void op_stn(void* base, size_t row, int ld, int c, const float v[NC]) {
+  if constexpr (NC == 8) op_st8<T>(base, row, ld, c, v);
+  else op_st4<T>(base, row, ld, c, v);
+}
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // erf-GELU for the 16-bit paths: Abramowitz & Stegun 7.1.26 rational approximation of erf (|error| <= 1.5e-7, far
@@ -398,6 +413,20 @@ template <typename T> __device__ __forceinline__ void gelu8_for(float* v) {
 template <> __device__ __forceinline__ void gelu8_for<float>(float* v) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
+}
+
+// the GELU of an NC-column epilogue, plus `add` where given: element by element at 4 columns, the paired form at 8 (bit-identical, see above)
+template <typename T, int NC> __device__ __forceinline__ void gelu_n(float* v, const float* add = nullptr) {
+  if constexpr (NC == 8) {
+    gelu8_for<T>(v);
+    if (add) {
+#pragma unroll
+      for (int e = 0; e < NC; ++e) v[e] += add[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < NC; ++e) v[e] = add ? gelu_for<T>(v[e]) + add[e] : gelu_for<T>(v[e]);
+  }
 }
 
 // Value of lane (l ^ M) of a wave64 WITHOUT the LDS crossbar: __shfl_xor compiles to ds_bpermute_b32 + s_waitcnt, ~60-100 cycles

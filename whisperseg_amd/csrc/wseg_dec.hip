@@ -206,18 +206,18 @@ __global__ __launch_bounds__(64, 8) void dec_self_attn_kernel(DecodeState st, co
     sq[lane] = El<T>::rnd(q1 * scale);
     // this step's own page: lane n - 1 holds its unit when n <= 64 (no further round trip)
     const int own_unit = n <= 64 ? __builtin_amdgcn_readlane(pg0, __builtin_amdgcn_readfirstlane(n - 1)) : pt[(n - 1) / KV_PAGE];
-    const size_t at = ((((size_t)own_unit * st.nb + (r - w * st.nb)) * H + h) * KV_PAGE + ((n - 1) % KV_PAGE)) * 64 + lane;
+    const size_t at = ((((size_t)own_unit * st.nb + (r - w * st.nb)) * H + h) * KV_PAGE + ((n - 1) % KV_PAGE)) * 64 + lane;      // kv_page_row, spelled out
     El<T>::st(kc + at, k1);
     El<T>::st(vc + at, v1);
     snk[lane] = k1;
     snv[lane] = v1;
   }
   WSEG_STAMP(1, 2);                                     // q | k | v reduced (fused path), cache rows appended
-  // srow[t]: index of the 64-element cache row of position t = ((unit nb + beam) H + h) KV_PAGE + t % KV_PAGE
+  // srow[t]: index of the 64-element cache row of position t (kv_page_row)
   for (int t = lane; t < n; t += 64) {
     const int beam = t == n - 1 ? (r - w * st.nb) : (t < 64 ? anc0 : (int)anc[t]);
     const int unit = t < 64 ? pg0 : pt[t / KV_PAGE];
-    srow[t] = ((unit * st.nb + beam) * H + h) * KV_PAGE + (t % KV_PAGE);
+    srow[t] = kv_page_row(unit, st.nb, beam, H, h, t);
   }
   __syncthreads();
   WSEG_STAMP(1, 3);
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(64) void prompt_self_attn_kernel(const float* __res
         q[pp] = b[0] + bias[col]; k[pp] = b[d] + bias[d + col]; v[pp] = b[2 * d] + bias[2 * d + col];
       }
       q[pp] *= scale;
-      const size_t at = ((((size_t)unit * nb) * H + h) * KV_PAGE + pp) * 64 + lane;
+      const size_t at = kv_page_row((size_t)unit, nb, 0, H, h, pp) * 64 + lane;
       kc[at] = k[pp];
       vc[at] = v[pp];
     }
@@ -692,9 +692,9 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState s
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16x3 / f16x3: cross-attention over 24-bit block-floating-point K / V (r06, EpiParams::kv24 == 3; st_bfp24_row in wseg_gemm_epi.h):
+// bf16x3 / f16x3: cross-attention over 24-bit block-floating-point K / V (r06, EpiParams::kv24 == 3: CrossKv<3>, written by st_bfp_row in wseg_gemm_epi.h):
 // per (slot, head) a [Tk][64] plane of the 24-bit two's-complement integers' top 16 bits, a [Tk][64] plane of their low bytes and
-// [Tk] fp32 row scales (196 bytes per row of an HBM-bound stream).  fp32 query and arithmetic; same structure as the packed 16-bit
+// [Tk] fp32 row scales (CrossKv<3>::ROW_BYTES per row of an HBM-bound stream).  fp32 query and arithmetic; same structure as the packed 16-bit
 // kernel above: 8 lanes per row, 8 raw rows per lane in flight (16 + 8 bytes each), one v_perm_b32 per element to rebuild the 32-bit
 // word 256 q and one v_cvt_f32_i32 to convert it, two beams per v_pk_fma_f32, DPP row sums.  The row scales are applied where a row
 // is one number — the K scale to the finished score and the V scale to the probability, both in the softmax pass over LDS — so
@@ -721,12 +721,13 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
   const int nb = st.nb;
   const int sub = lane & 7, rowl = lane >> 3;
   const int ws = kv_slot ? kv_slot[w] : w;              // prompt pass: query rows of admitted window w, K / V of its slot
-  const unsigned char* Kb = ck + ((size_t)ws * H + h) * Tk * 196;
-  const unsigned char* Vb = cv + ((size_t)ws * H + h) * Tk * 196;
-  const unsigned char* Kl = Kb + (size_t)Tk * 128;
-  const unsigned char* Vl = Vb + (size_t)Tk * 128;
-  const float* Ks = (const float*)(Kb + (size_t)Tk * 192);      // row scales
-  const float* Vs = (const float*)(Vb + (size_t)Tk * 192);
+  typedef CrossKv<3> KV;
+  const unsigned char* Kb = KV::block(ck, (size_t)ws * H + h, Tk);
+  const unsigned char* Vb = KV::block(cv, (size_t)ws * H + h, Tk);
+  const unsigned char* Kl = KV::low_plane(Kb, Tk);
+  const unsigned char* Vl = KV::low_plane(Vb, Tk);
+  const float* Ks = (const float*)KV::scale_plane(Kb, Tk);      // row scales
+  const float* Vs = (const float*)KV::scale_plane(Vb, Tk);
   // the row scales wait in LDS for the softmax pass (read from global there, each wave's first access paid an HBM round trip with no
   // stream in flight); visible behind the barrier that closes the score pass
   __shared__ float sks[512], svs[512];
@@ -740,8 +741,8 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = min(t0 + u * 32 + wave * 8 + rowl, Tk - 1);      // clamped: out-of-range rows are discarded below
-      kh[u] = __builtin_nontemporal_load((const raw16*)(Kb + (size_t)t * 128 + sub * 16));
-      kl[u] = __builtin_nontemporal_load((const raw8*)(Kl + (size_t)t * 64 + sub * 8));
+      kh[u] = __builtin_nontemporal_load((const raw16*)(Kb + (size_t)t * KV::HI_STRIDE + sub * 16));
+      kl[u] = __builtin_nontemporal_load((const raw8*)(Kl + (size_t)t * KV::LOW_STRIDE + sub * 8));
     }
   };
   if (pi.part != nullptr) {
@@ -818,8 +819,8 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = min(t0 + u * 32 + wave * 8 + rowl, Tk - 1);
-      vh[u] = __builtin_nontemporal_load((const raw16*)(Vb + (size_t)t * 128 + sub * 16));
-      vl[u] = __builtin_nontemporal_load((const raw8*)(Vl + (size_t)t * 64 + sub * 8));
+      vh[u] = __builtin_nontemporal_load((const raw16*)(Vb + (size_t)t * KV::HI_STRIDE + sub * 16));
+      vl[u] = __builtin_nontemporal_load((const raw8*)(Vl + (size_t)t * KV::LOW_STRIDE + sub * 8));
     }
   };
   load_v(0);
@@ -887,8 +888,8 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Split-precision modes, r05: cross-attention over block-floating-point K / V (EpiParams::kv24 == 2: per (slot, head) a [Tk][64] plane
-// of int16 followed by [Tk] fp32 powers of two, value = int16 * scale of its row; 132 bytes per row of an HBM-bound stream).  The
+// Split-precision modes, r05: cross-attention over block-floating-point K / V (EpiParams::kv24 == 2, CrossKv<2>: per (slot, head) a [Tk][64] plane
+// of int16 followed by [Tk] fp32 powers of two, value = int16 * scale of its row; CrossKv<2>::ROW_BYTES per row of an HBM-bound stream).  The
 // structure is the 24-bit kernel's (dec_cross_attn_k24_kernel): 8 lanes per row, 8 raw rows per lane in flight (16 + 4 bytes
 // each), two beams per v_pk_fma_f32, DPP row sums; an element is one v_cvt_f32_i32 (sign-extended half word), the row's scale
 // multiplies the finished score (K) / the probability (V) — powers of two: exact, the sums are those of the dequantised values.
@@ -914,10 +915,11 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_bfp_kernel(DecodeState 
   const int nb = st.nb;
   const int sub = lane & 7, rowl = lane >> 3;
   const int ws = kv_slot ? kv_slot[w] : w;              // prompt pass: query rows of admitted window w, K / V of its slot
-  const unsigned char* Kb = ck + ((size_t)ws * H + h) * Tk * 132;
-  const unsigned char* Vb = cv + ((size_t)ws * H + h) * Tk * 132;
-  const float* Ks = (const float*)(Kb + (size_t)Tk * 128);
-  const float* Vs = (const float*)(Vb + (size_t)Tk * 128);
+  typedef CrossKv<2> KV;
+  const unsigned char* Kb = KV::block(ck, (size_t)ws * H + h, Tk);
+  const unsigned char* Vb = KV::block(cv, (size_t)ws * H + h, Tk);
+  const float* Ks = (const float*)KV::scale_plane(Kb, Tk);
+  const float* Vs = (const float*)KV::scale_plane(Vb, Tk);
   constexpr int NP = (NB + 1) / 2;
   f2 qq[8][NP];
   __shared__ float sq[NB][64];                          // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS
@@ -930,7 +932,7 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_bfp_kernel(DecodeState 
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
       const int t = min(t0 + u * 32 + wave * 8 + rowl, Tk - 1);      // clamped: out-of-range rows are discarded by their consumers
-      r[u] = __builtin_nontemporal_load((const raw16*)(base + (size_t)t * 128 + sub * 16));
+      r[u] = __builtin_nontemporal_load((const raw16*)(base + (size_t)t * KV::HI_STRIDE + sub * 16));
     }
   };
   raw16 kq[U];
@@ -1510,7 +1512,7 @@ static void launch_cross_t(const DecodeState& st, const void* q, const void* ck,
 // wseg_kernels.h.  The three-MFMA modes' GEMMs are exact to ~6e-6 of a logit on the parity sweeps' models; the 24-bit FLOAT rows they
 // stored from r03 to mid r06 added 2e-5 — which cost f16x3 one of 4 200 sweep recordings (a greedy decision with a margin of 2.8e-5;
 // fp32 rows reproduce it) —, 16-bit block-floating-point rows 6e-5: since r06 these modes store 24-bit block floating point (format 3:
-// 196 bytes per row, error <= 2^-24 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven sweeps.  The
+// CrossKv<3>, error <= 2^-24 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven sweeps.  The
 // mixed mode's own fp6 cross terms cost 8e-5: it takes the 31 % smaller 16-bit rows (format 2, 1.3e-4 in all).
 int x3_cross_kv_format(int dtype, int nb) {
   if (nb > 4) return 0;

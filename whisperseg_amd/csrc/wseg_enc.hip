@@ -159,9 +159,9 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 4) void enc_attention_h16_kernel(c
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int q0 = blockIdx.x * 128 + wave * 32;
   const int qi = lane & 31, g2 = lane >> 5;
-  const HT* Qb = Q + (size_t)bh * Tp * 64;
-  const HT* Kb = K + (size_t)bh * Tp * 64;
-  const HT* Vb = Vt + (size_t)bh * 64 * Tp;
+  const HT* Qb = Q + enc_qk_index(bh, Tp, 0);
+  const HT* Kb = K + enc_qk_index(bh, Tp, 0);
+  const HT* Vb = Vt + enc_vt_block(bh, Tp);
 
   bf16x8 qf[4], qfl[SPLIT ? 4 : 1];
 #pragma unroll
@@ -384,14 +384,14 @@ __global__ __launch_bounds__(64) void enc_attention_f32_kernel(const float* __re
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= T) return;
-  const float* qp = Q + ((size_t)bh * Tp + q) * 64;
+  const float* qp = Q + enc_qk_index(bh, Tp, q);
   float qv[64], o[64];
 #pragma unroll
   for (int e = 0; e < 64; ++e) { qv[e] = qp[e]; o[e] = 0.f; }
   // pass 1: row max; pass 2: exp / sum / PV  (same order of operations as softmax(QK^T) V)
   float mx = -3.0e38f;
   for (int t = 0; t < T; ++t) {
-    const float* kp = K + ((size_t)bh * Tp + t) * 64;
+    const float* kp = K + enc_qk_index(bh, Tp, t);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 64; ++e) s = fmaf(qv[e], kp[e], s);
@@ -399,15 +399,15 @@ __global__ __launch_bounds__(64) void enc_attention_f32_kernel(const float* __re
   }
   float l = 0.f;
   for (int t = 0; t < T; ++t) {
-    const float* kp = K + ((size_t)bh * Tp + t) * 64;
+    const float* kp = K + enc_qk_index(bh, Tp, t);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 64; ++e) s = fmaf(qv[e], kp[e], s);
     const float p = expf(s - mx);
     l += p;
-    const float* vp = Vt + (size_t)bh * 64 * Tp + t;
+    const float* vp = Vt + vt_plain_index((size_t)bh * 64, Tp, t);
 #pragma unroll
-    for (int e = 0; e < 64; ++e) o[e] = fmaf(p, vp[(size_t)e * Tp], o[e]);
+    for (int e = 0; e < 64; ++e) o[e] = fmaf(p, vp[vt_plain_index((size_t)e, Tp, 0)], o[e]);
   }
   const float inv = 1.0f / l;
 #pragma unroll
@@ -436,8 +436,8 @@ __global__ __launch_bounds__(256) void enc_attention_f32_mfma_kernel(const float
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fi = lane & 31, fk = lane >> 5;
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int q0 = blockIdx.x * 128 + wave * 32;
-  const float* Qb = Q + (size_t)bh * Tp * 64;
-  const float* Kb = K + (size_t)bh * Tp * 64;
+  const float* Qb = Q + (size_t)bh * Tp * 64;      // enc_qk_index(bh, Tp, 0) | enc_vt_block(bh, Tp), spelled out: the helpers' inlining changes
+  const float* Kb = K + (size_t)bh * Tp * 64;      // this kernel's instruction order
   const float* Vb = Vt + (size_t)bh * 64 * Tp;
   const int qrow = min(q0 + fi, Tp - 1);
   float qf[32];                         // B operand of S^T = K Q^T: Q[q0 + fi][2 kk + fk]

@@ -303,7 +303,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM <= 128 && BN <= 64 && WM * WN == 
         const float4 a = *(const float4*)(strip + r * LDT + cc), b = *(const float4*)(strip + r * LDT + cc + 4);
         float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         const int m = m0 + wm * TM + j * 16 + r;
-        if (m < M) epi_apply8<EPI, T>(ep, m, n0 + wn * TN + cc, v);
+        if (m < M) epi_apply<EPI, T, 8>(ep, m, n0 + wn * TN + cc, v);
       }
     }
   } else {
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM <= 128 && BN <= 64 && WM * WN == 
         if constexpr (SPLIT) {
           *(float4*)(part + ((size_t)blockIdx.z * m_pad + m) * N + n) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
-          if (m < M) epi_apply<EPI, T>(ep, m, n, v);
+          if (m < M) epi_apply<EPI, T, 4>(ep, m, n, v);
         }
       }
     }
@@ -341,7 +341,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
   const int fr = lane & 15, fg = lane >> 4, rr = lane >> 3, cc = (lane & 7) * 8;
   const int nc = nb + cc;
   float bv[8];
-  if (ep.bias) ld8_h<PT>((const PT*)ep.bias + nc, bv);
+  if (ep.bias) VecN<PT, 8>::ld((const PT*)ep.bias + nc, bv);
   else {
 #pragma unroll
     for (int e = 0; e < 8; ++e) bv[e] = 0.f;
@@ -377,7 +377,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
   // position, page-table entry).  Done row by row inside the store loop (r04-r05) every lookup queued behind the previous row's stores
   // (vmcnt retires in order: a load issued after a store waits for it) — 16 serialised round trips per wave tile, ~30 of the 87 us of the
   // 4 096-row launch.  Now all 16 rows of the lane are resolved before the first store (see the rule above).
-  [[maybe_unused]] int dec_kv[EPI == EPI_QKV_DEC ? NROW : 1];      // ((unit * beams + beam) * heads) * KV_PAGE + pos % KV_PAGE, or -1: no store
+  [[maybe_unused]] int dec_kv[EPI == EPI_QKV_DEC ? NROW : 1];      // kv_page_row of head 0 (the head is added at the store), or -1: no store
   [[maybe_unused]] int dec_sec = 0;
   if constexpr (EPI == EPI_QKV_DEC) {
     dec_sec = nb / ep.d_model;      // wave-uniform: a 64-column wave tile lies inside one section and one head
@@ -394,7 +394,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
       for (int t = 0; t < NROW; ++t) {
         const int m = min(mb + t * 8 + rr, M - 1), beam = m - slot_r[t] * ep.pos_div;
         const int unit = ep.kv_pt[(size_t)slot_r[t] * ep.kv_npg + pos_r[t] / KV_PAGE];
-        if (dec_kv[t] == 0) dec_kv[t] = ((unit * ep.pos_div + beam) * ep.n_heads) * KV_PAGE + (pos_r[t] % KV_PAGE);
+        if (dec_kv[t] == 0) dec_kv[t] = kv_page_row(unit, ep.pos_div, beam, ep.n_heads, 0, pos_r[t]);
       }
     }
   }
@@ -426,7 +426,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
         const int m = mb + j * 16 + g4 * 4;                      // first of the lane's 4 rows
         const int b = m / ep.t_len, t = m - b * ep.t_len;
         const int nn = nb - 2 * ep.d_model, h = nn >> 6;
-        AT* vbase = (AT*)ep.v + ((size_t)b * ep.n_heads + h) * 64 * ep.t_pad;
+        AT* vbase = (AT*)ep.v + enc_vt_block((size_t)b * ep.n_heads + h, ep.t_pad);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int hd = q * 16 + hq;
@@ -438,7 +438,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
             for (int r = 0; r < 4; ++r) x[r] = H16<AT>::sat(x[r]);
           }
           const uint2 hi2 = make_uint2(H16<AT>::pack(x[0], x[1]), H16<AT>::pack(x[2], x[3]));
-          AT* dst = vbase + (ep.vt_tiled ? vt_tiled_index(hd, t) : hd * ep.t_pad + t);      // 4 consecutive keys are contiguous either way
+          AT* dst = vbase + (ep.vt_tiled ? vt_tiled_index(hd, t) : vt_plain_index(hd, ep.t_pad, t));      // 4 consecutive keys are contiguous either way
           if (m < M) *(uint2*)dst = hi2;
           if (IO<T>::split && ep.qkv_mode == 2) {               // lo plane: x - rn(x)
             const uint2 lo2 = make_uint2(H16<AT>::pack(H16<AT>::sub_lo(x[0], hi2.x), H16<AT>::sub_hi(x[1], hi2.x)),
@@ -470,16 +470,17 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
       } else if constexpr (EPI == EPI_KV_CROSS) {
         int mm = m;
         if (ep.slot_map) { const int b = m / ep.t_len; mm = (b == kv_b0 ? kv_s0 : kv_s1) * ep.t_len + (m - b * ep.t_len); }
-        if (m < M) epi_apply8<EPI, T>(ep2, mm, nc, v);
+        if (m < M) epi_apply<EPI, T, 8>(ep2, mm, nc, v);
       } else if constexpr (EPI == EPI_QKV_DEC) {
         const int nn = nc - dec_sec * ep.d_model;
         if (dec_sec == 0) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] *= ep.scale;
-          if (m < M) st8_h<PT>((PT*)ep.q + (size_t)m * ep.d_model + nn, v);
+          if (m < M) VecN<PT, 8>::st((PT*)ep.q + (size_t)m * ep.d_model + nn, v);
         } else {
           const int kv = dec_kv[j * 2 + hh];
-          if (kv >= 0) st8_h<PT>((PT*)(dec_sec == 1 ? ep.k : ep.v) + ((size_t)kv + (size_t)(nn >> 6) * KV_PAGE) * 64 + (nn & 63), v);
+          // kv_page_row of head nn >> 6: the row of head 0 + h * KV_PAGE (asserted next to kv_page_row)
+          if (kv >= 0) VecN<PT, 8>::st((PT*)(dec_sec == 1 ? ep.k : ep.v) + ((size_t)kv + (size_t)(nn >> 6) * KV_PAGE) * 64 + (nn & 63), v);
         }
       } else if constexpr (IsMx<T>::v && (EPI == EPI_GELU || EPI == EPI_STORE)) {
         // M6 rows: the quad's word exchange goes through the strip slots the quad has just read (8 floats per lane = its 128 bytes)
@@ -489,7 +490,7 @@ __device__ __forceinline__ void staged_epilogue(const f32x4 (&acc)[NI][MI], floa
         }
         op_st8_m6_lds(ep.out, (size_t)m, ep.ldc, nc, v, (unsigned char*)(strip + rw * LDT + (cc & ~31)), m < M);
       } else {
-        if (m < M) epi_apply8<EPI, T>(ep2, m, nc, v);
+        if (m < M) epi_apply<EPI, T, 8>(ep2, m, nc, v);
       }
     }
   }
@@ -1036,7 +1037,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     const float4 t = *(const float4*)(part + ((size_t)z * m_pad + m) * N + n0);
     v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
   }
-  epi_apply<EPI, T>(ep, m, n0, v);
+  epi_apply<EPI, T, 4>(ep, m, n0, v);
 }
 
 // The same with 8 columns per thread through the 8-column epilogue: in WSEG_F16M6 mode (EPI_STORE / EPI_GELU, N % 32 == 0) the four
@@ -1055,7 +1056,7 @@ __global__ __launch_bounds__(256) void splitk_reduce8_kernel(const float* __rest
     const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
     v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
   }
-  epi_apply8<EPI, T>(ep, m, n0, v);
+  epi_apply<EPI, T, 8>(ep, m, n0, v);
 }
 
 // x[m][:] += bias + sum_z part[z][m][:]  (x is the fp32 residual stream), then y[m][:] = LayerNorm(x[m][:]) in the model dtype.
@@ -1085,7 +1086,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_resid_ln_kernel(const float
     const float4 x0 = *(const float4*)xp, x1 = *(const float4*)(xp + 4);
     const float r[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
     float bb[8];
-    ld8_h<PT>(bias + c, bb);
+    VecN<PT, 8>::ld(bias + c, bb);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { v[j] = r[j] + (a[j] + bb[j]); sum += v[j]; }
     *(float4*)xp = make_float4(v[0], v[1], v[2], v[3]);
@@ -1107,8 +1108,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_resid_ln_kernel(const float
   const float rstd = 1.0f / sqrtf(((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)d + 1e-5f);
   if (act) {
     float gg[8], be[8], o[8];
-    ld8_h<PT>(gam + c, gg);
-    ld8_h<PT>(bet + c, be);
+    VecN<PT, 8>::ld(gam + c, gg);
+    VecN<PT, 8>::ld(bet + c, be);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (v[j] - mean) * rstd * gg[j] + be[j];
     op_st8<T>(y, (size_t)row, d, c, o);

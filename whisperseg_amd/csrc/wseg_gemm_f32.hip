@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + ty * 4 + i;
-    if (m < M) epi_apply<EPI, float>(ep, m, n0 + tx * 4, acc[i]);
+    if (m < M) epi_apply<EPI, float, 4>(ep, m, n0 + tx * 4, acc[i]);
   }
 }
 
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_big_kernel(const float* __res
     if (m < M) {
       float v0[4] = {acc2[i][0][0], acc2[i][0][1], acc2[i][1][0], acc2[i][1][1]};
       float v1[4] = {acc2[i][2][0], acc2[i][2][1], acc2[i][3][0], acc2[i][3][1]};
-      epi_apply<EPI, float>(ep, m, n0 + tx * 4, v0);
-      epi_apply<EPI, float>(ep, m, n0 + 64 + tx * 4, v1);
+      epi_apply<EPI, float, 4>(ep, m, n0 + tx * 4, v0);
+      epi_apply<EPI, float, 4>(ep, m, n0 + 64 + tx * 4, v1);
     }
   }
 }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const float* __restr
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float v[4] = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-        epi_apply<EPI, float>(ep, m, n0 + wn * 32 * TJ + j * 32 + 8 * q + 4 * fk, v);
+        epi_apply<EPI, float, 4>(ep, m, n0 + wn * 32 * TJ + j * 32 + 8 * q + 4 * fk, v);
       }
   }
 }
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma16_kernel(const float* __res
   const int m = m0 + wm * 16 + fi;
   if (m < M) {
     float v[4] = {acc[0], acc[1], acc[2], acc[3]};
-    epi_apply<EPI, float>(ep, m, n0 + wn * 16 + 4 * fk, v);
+    epi_apply<EPI, float, 4>(ep, m, n0 + wn * 16 + 4 * fk, v);
   }
 }
 

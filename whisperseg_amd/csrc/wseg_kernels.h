@@ -10,6 +10,16 @@ namespace wseg {
 // A pool UNIT = one page of every beam row of a slot, in every layer, K and V:  pool[layer][unit][beam][head][KV_PAGE][64].
 // Page table: kv_pt[slot][position / KV_PAGE] -> unit (the beams of a slot advance together, so one entry serves them all).
 constexpr int KV_PAGE = 8;
+// THE definition of that layout: index of the 64-element row of (unit, beam, head h, position pos) inside one layer's K or V pool, in the
+// index type I of the caller (size_t for an address, int for the row tables kept in registers / LDS).  The staged GEMM epilogue resolves
+// the page before it knows the head: it takes the row of head 0 and adds h * KV_PAGE at the store (the assertion below).
+// A few sites spell the same expression out and say so: there the call, although inlined, changed the kernel's instruction order.
+template <typename I> __host__ __device__ __forceinline__ constexpr I kv_page_row(I unit, int beams, int beam, int H, int h, int pos) {
+  return ((unit * beams + beam) * H + h) * KV_PAGE + (pos % KV_PAGE);
+}
+static_assert(kv_page_row(3, 5, 2, 6, 4, 13) == kv_page_row(3, 5, 2, 6, 0, 13) + 4 * KV_PAGE, "head h of a paged K / V row: h * KV_PAGE rows further");
+// rows of `units` units in one layer's K or V pool (host sizing: times 64 elements of the storage type)
+__forceinline__ constexpr size_t kv_pool_rows(size_t units, int beams, int H) { return kv_page_row<size_t>(units, beams, 0, H, 0, 0); }
 
 // ---------------------------------------------------------------------------------------------
 // GEMM:  C[m][n] = sum_k A[m][k] * W[n][k]   (A [M][lda], W [N][ldw]; both K-contiguous, i.e. W is a
@@ -57,11 +67,8 @@ struct EpiParams {
   size_t qkv_plane = 0;
   int vt_tiled = 0;              // EPI_QKV_ENC: V^T in the MFMA operand order of the 16-bit attention kernel (vt_tiled_index, wseg_common.h)
                                  // instead of plain [b][h][64][t_pad] rows (the fp32 attention kernels): enc_attention_vt_tiled(dtype)
-  int kv24 = 0;                  // split-precision modes, EPI_KV_CROSS storage of the cross K / V (x3_cross_kv_format): 0 = fp32;
-                                 // 2 (f16m6, r05) = block floating point, one block per (position, head) row: [t_len][64] int16 then
-                                 // [t_len] fp32 powers of two, value = int16 * scale (132 bytes per row); 3 (bf16x3 / f16x3, r06) = block
-                                 // floating point with 24-bit integers q: [t_len][64] int16 (q >> 8), then [t_len][64] bytes (q & 0xff),
-                                 // then [t_len] fp32 powers of two 2^(s - 8), value = 256 q * scale (196 bytes per row)
+  int kv24 = 0;                  // split-precision modes, EPI_KV_CROSS storage of the cross K / V (x3_cross_kv_format): 0 = fp32 rows;
+                                 // 2, 3 = the packed block-floating-point formats CrossKv<2> / CrossKv<3> (below)
 };
 
 struct GemmArgs {
@@ -116,16 +123,42 @@ bool enc_attention_vt_tiled(int dtype);
 int launch_enc_attention(int dtype, const void* q, const void* k, const void* vt, void* out,
                          int B, int H, int T, int Tp, int d, hipStream_t s);
 
-// Storage format of the cross-attention K / V in the split-precision modes (EpiParams::kv24) and its bytes per (position, head) row.
+// Storage format of the cross-attention K / V in the split-precision modes (EpiParams::kv24).
 // 0 = fp32 rows (more than 4 beams: no beam-tiled cross-attention kernel).
 // 2 = per-row block floating point with int16 elements (r05, f16m6): the 200-recording sweep through the CPU oracle with K and V so
-// quantised is 200 / 200 and the first-step logit error stays at the mixed mode's own 1.5e-4 (plain half: 7.5e-4, 196 / 200;
-// tools/precision_study.py "ckv=bfp16r", profiles/r05_precision_study.json) for 132 bytes per row of an HBM-bound stream
+// quantised is 200 / 200 and the first-step logit error stays at the mixed mode's own 1.5e-4 (plain half: 7.5e-4, 4 of 200 recordings differ;
+// tools/precision_study.py "ckv=bfp16r", profiles/r05_precision_study.json) for two thirds of the bytes of an HBM-bound stream
 // (wseg_dec.hip, x3_cross_kv_format, says why the three-MFMA modes do not take it).
-// 3 = per-row block floating point with 24-bit integer elements (r06, bf16x3 / f16x3): 196 bytes per row, error <= 2^-24 of the row
-// maximum (st_bfp24_row, wseg_gemm_epi.h).
+// 3 = per-row block floating point with 24-bit integer elements (r06, bf16x3 / f16x3): error <= 2^-24 of the row maximum
+// (st_bfp_row, wseg_gemm_epi.h).
 int x3_cross_kv_format(int dtype, int nb);
-static inline size_t cross_kv_row_bytes(int fmt, size_t es) { return fmt == 3 ? 196 : (fmt == 2 ? 132 : 64 * es); }
+// THE definition of the packed formats' bytes (writers st_bfp_row, readers dec_cross_attn_bfp_kernel / dec_cross_attn_k24_kernel, host
+// sizing cross_kv_row_bytes).  One BLOCK per (slot, head), blocks back to back, planes inside a block one after the other:
+//   hi plane    [t_len][64] int16   format 2: the element q; format 3: q >> 8 of the 24-bit element
+//   low plane   [t_len][64] bytes   format 3 only: q & 0xff
+//   scale plane [t_len] fp32        the row's power of two (format 3: 2^(s - 8), value = 256 q * scale)
+// A block starts ROW_BYTES * t_len * (slot * heads + head) bytes into the buffer, and ROW_BYTES is 4 * 33 (format 2) or 4 * 49 (format 3):
+// blocks are 16-byte aligned only when t_len % 4 == 0 (the planes inside a block then are too).  Other lengths rely on the hardware's
+// unaligned global access for the 16-byte row accesses.  (Padding the stride would change the workspace size.)
+template <int FMT> struct CrossKv {
+  static_assert(FMT == 2 || FMT == 3, "the packed formats; format 0 is plain rows of 64 elements");
+  static constexpr int HI_STRIDE = 64 * 2, LOW_STRIDE = FMT == 3 ? 64 : 0, SCALE_STRIDE = 4;      // bytes per position in each plane
+  static constexpr int LOW_AT = HI_STRIDE, SCALE_AT = HI_STRIDE + LOW_STRIDE;                      // start of a plane in its block, per position of t_len
+  static constexpr int ROW_BYTES = HI_STRIDE + LOW_STRIDE + SCALE_STRIDE;
+  static __host__ __device__ __forceinline__ constexpr size_t block_bytes(int t_len) { return (size_t)t_len * ROW_BYTES; }
+  // P: unsigned char / const unsigned char.  The block of (slot * heads + head) — its hi plane starts there — and its other planes; position
+  // t of a plane is t times the plane's stride further
+  template <typename P> static __host__ __device__ __forceinline__ P* block(P* base, size_t slot_head, int t_len) { return base + slot_head * t_len * ROW_BYTES; }
+  template <typename P> static __host__ __device__ __forceinline__ P* low_plane(P* blk, int t_len) { return blk + (size_t)t_len * LOW_AT; }
+  template <typename P> static __host__ __device__ __forceinline__ P* scale_plane(P* blk, int t_len) { return blk + (size_t)t_len * SCALE_AT; }
+};
+static_assert(CrossKv<2>::ROW_BYTES == 132 && CrossKv<2>::ROW_BYTES == 128 + 4 && CrossKv<2>::SCALE_AT == 128, "format 2: int16 plane, scales");
+static_assert(CrossKv<3>::ROW_BYTES == 196 && CrossKv<3>::ROW_BYTES == 128 + 64 + 4 && CrossKv<3>::LOW_AT == 128 && CrossKv<3>::SCALE_AT == 192,
+              "format 3: int16 plane, low-byte plane, scales");
+// bytes per (position, head) row of format fmt (es: element size of the plain rows of format 0)
+static inline size_t cross_kv_row_bytes(int fmt, size_t es) { return fmt == 3 ? CrossKv<3>::ROW_BYTES : (fmt == 2 ? CrossKv<2>::ROW_BYTES : 64 * es); }
+// bytes of one decoder layer's cross K (or V): the blocks of slots * heads (slot, head) pairs
+static inline size_t cross_kv_layer_bytes(int fmt, size_t es, size_t slots, size_t heads, size_t t_len) { return slots * heads * t_len * cross_kv_row_bytes(fmt, es); }
 // WSEG_F16M6: hi | lo IEEE-half operand rows [M][2K words] -> M6 rows [M][4K bytes] (wseg_common.h), K % 64 == 0
 int launch_x3_to_m6(const void* x3_rows, void* m6_rows, size_t M, int K, bool weight_order, hipStream_t s);
 // the dtype every NON-GEMM kernel runs in: WSEG_F16M6 is WSEG_F16X3 outside the GEMMs

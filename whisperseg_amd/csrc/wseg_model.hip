@@ -142,7 +142,7 @@ int kv_pages(int L) { return (L + KV_PAGE - 1) / KV_PAGE; }
 int kv_units_for(int W, int L, int per) { return std::max(W * kv_pages(per < L ? per : L), kv_pages(L)); }
 int kv_default_units(int W, int L) { return kv_units_for(W, L, KV_DEFAULT_POSITIONS); }
 size_t kv_unit_bytes(const wseg_model* m, int nb) {      // one unit: every layer, K and V
-  return (size_t)m->cfg.dec_layers * 2 * nb * m->cfg.n_heads * KV_PAGE * 64 * m->es;
+  return (size_t)m->cfg.dec_layers * 2 * kv_pool_rows(1, nb, m->cfg.n_heads) * 64 * m->es;
 }
 
 // Lay out the workspace for W window slots (encoder passes of up to min(W, ENC_CHUNK) windows), nb beams, capacity L positions,
@@ -165,9 +165,9 @@ void make_plan(const wseg_model* m, int W, int nb, int L, int kv_units, char* ba
   p.hbuf = u;
   p.x = take(Mp * d * 4);                          // the residual stream is fp32 in every mode
   p.y = take(Mp * d * es);
-  p.q = take((size_t)We * H * m->tp * 64 * es);
-  p.k = take((size_t)We * H * m->tp * 64 * es);
-  p.vt = take((size_t)We * H * m->tp * 64 * es);
+  p.q = take(enc_qk_index((size_t)We * H, m->tp, 0) * es);
+  p.k = take(enc_qk_index((size_t)We * H, m->tp, 0) * es);
+  p.vt = take(enc_vt_block((size_t)We * H, m->tp) * es);
   p.enc_out = take(Mp * d * es);
   const size_t Ld = c.dec_layers, Tk = c.enc_positions;
   if (m->mx) {
@@ -191,11 +191,11 @@ void make_plan(const wseg_model* m, int W, int nb, int L, int kv_units, char* ba
   DecPlan& q = p.dec;
   q.W = W;
   const size_t Wc = W, R = Wc * nb, Rp = align_up(R, 256);
-  const size_t crow = cross_kv_row_bytes(m->x3 ? x3_cross_kv_format(c.dtype, nb) : 0, es);      // bytes per (position, head) row (wseg_dec.hip)
-  q.ck = take(Ld * Wc * H * Tk * crow);
-  q.cv = take(Ld * Wc * H * Tk * crow);
+  const size_t cross_stride = cross_kv_layer_bytes(m->x3 ? x3_cross_kv_format(c.dtype, nb) : 0, es, Wc, H, Tk);
+  q.ck = take(Ld * cross_stride);
+  q.cv = take(Ld * cross_stride);
   q.kv_units = kv_units;
-  q.kv_layer_stride = align_up((size_t)kv_units * nb * H * KV_PAGE * 64 * es, 256);
+  q.kv_layer_stride = align_up(kv_pool_rows(kv_units, nb, (int)H) * 64 * es, 256);
   q.sk = take(Ld * q.kv_layer_stride);
   q.sv = take(Ld * q.kv_layer_stride);
   q.kv_pt = (int*)take(Wc * kv_pages(L) * 4);
@@ -284,7 +284,7 @@ int run_encoder(wseg_model* m, const float* feats, int W, Plan& p, void* enc_out
   // the attention and the large-tile GEMM epilogues write M6 rows directly; what still arrives as hi | lo rows is converted, mxa)
   const int dt = m->sdt, gdt = c.dtype, d = c.d_model, H = c.n_heads, ffn = c.ffn, T = c.enc_positions, Tp = m->tp;
   const int M1 = W * c.spec_cols, M = W * T;
-  const size_t qkv_bytes = (size_t)W * H * Tp * 64 * m->es;
+  const size_t qkv_bytes = enc_qk_index((size_t)W * H, Tp, 0) * m->es;
   // pad rows of Q/K and pad columns of V^T must be finite (they are multiplied by exact zeros)
   WSEG_HIP_CHECK(hipMemsetAsync(p.q, 0, qkv_bytes, s));
   WSEG_HIP_CHECK(hipMemsetAsync(p.k, 0, qkv_bytes, s));
@@ -304,7 +304,7 @@ int run_encoder(wseg_model* m, const float* feats, int W, Plan& p, void* enc_out
     WSEG_TRY(launch_layernorm(gdt, (const float*)p.x, L.ln1_g, L.ln1_b, p.y, M, d, s));
     e = EpiParams();
     e.bias = L.qkv_b; e.q = p.q; e.k = p.k; e.v = p.vt; e.d_model = d; e.t_len = T; e.t_pad = Tp; e.n_heads = H; e.scale = 0.125f;
-    if (m->x3) { e.qkv_mode = 2; e.qkv_plane = (size_t)W * H * Tp * 64; }
+    if (m->x3) { e.qkv_mode = 2; e.qkv_plane = enc_qk_index((size_t)W * H, Tp, 0); }
     e.vt_tiled = enc_attention_vt_tiled(gdt) ? 1 : 0;
     WSEG_TRY(gemm(m, EPI_QKV_ENC, p.y, d, L.qkv_w, d, M, 3 * d, d, e, nullptr, s));
     WSEG_TRY(launch_enc_attention(gdt, p.q, p.k, p.vt, p.y, W, H, T, Tp, d, s));
@@ -337,7 +337,7 @@ int run_decoder_step(wseg_model* m, DecPlan& p, char* mxa, bool want_logits, hip
   const wseg_model_config& c = m->cfg;
   const int dt = m->sdt, gdt = c.dtype, d = c.d_model, H = c.n_heads, ffn = c.ffn, Tk = c.enc_positions;
   const size_t self_stride = p.kv_layer_stride;
-  const size_t cross_stride = (size_t)p.st.W * H * Tk * cross_kv_row_bytes(m->x3 ? x3_cross_kv_format(gdt, p.st.nb) : 0, m->es);
+  const size_t cross_stride = cross_kv_layer_bytes(m->x3 ? x3_cross_kv_format(gdt, p.st.nb) : 0, m->es, p.st.W, H, Tk);
   DecodeState view = p.st;      // the prompt pass seen by the cross-attention kernel: n "slots" of np "beams", none idle
   if (pp) { view.W = pp->n; view.nb = pp->np; view.done = p.zeros; }
   const DecodeState& st = pp ? view : p.st;
@@ -644,7 +644,7 @@ struct GenerateRun {
     const wseg_model_config& c = m->cfg;
     DecPlan& q = p.dec;
     const int d = c.d_model, H = c.n_heads, Tk = c.enc_positions;
-    const size_t cross_stride = (size_t)S * H * Tk * cross_kv_row_bytes(kv24, m->es);
+    const size_t cross_stride = cross_kv_layer_bytes(kv24, m->es, S, H, Tk);
     const size_t feat_stride = (size_t)c.n_mels * c.spec_cols;
     for (int c0 = 0; c0 < n; c0 += ENC_CHUNK) {
       const int nc = std::min(ENC_CHUNK, n - c0), wc = w0 + c0;
