@@ -75,7 +75,7 @@ typedef struct {
   int32_t n_fft;            /* 512 | 1024 | 2048 | 4096 | 8192  (reference audio_utils.py:32-43) */
   int32_t hop;              /* int(spec_time_step * sr)          (reference audio_utils.py:48)    */
   int32_t n_mels;           /* 80 */
-  int32_t n_cols;           /* total_spec_columns, 1000          (reference model.py:153)          */
+  int32_t n_cols;           /* total_spec_columns, 256 .. 3000 (default 1000; reference model.py:153) */
   const float* window;      /* device [n_fft]      periodic Hann                                   */
   const float* twiddle;     /* device [n_fft/2][2] (cos, -sin)(2*pi*k/n_fft)                        */
   const int32_t* mel_start; /* device [n_mels]     first non-zero FFT bin of each filter           */
@@ -117,8 +117,8 @@ int wseg_resample_f32(const float* x, int64_t n_in, const float* taps, int32_t n
 typedef struct {
   int32_t d_model, n_heads, enc_layers, dec_layers, ffn, vocab;
   int32_t n_mels;           /* 80   */
-  int32_t spec_cols;        /* 1000 */
-  int32_t enc_positions;    /* 500 = spec_cols / 2 (reference model.py:79) */
+  int32_t spec_cols;        /* total_spec_columns: 2 * enc_positions, 256 .. 3000 (default 1000; reference train.py:72) */
+  int32_t enc_positions;    /* spec_cols / 2 = 128 .. 1500 rows of Whisper's position table (default 500; reference model.py:76-86) */
   int32_t dec_positions;    /* 448  */
   int32_t dtype;            /* wseg_dtype: arithmetic/storage type of weights and activations */
 } wseg_model_config;
@@ -137,7 +137,7 @@ int wseg_model_set_tensor(wseg_model* m, const char* name, const void* dev_ptr, 
 int wseg_model_ready(const wseg_model* m);
 
 /* Workspace (device bytes) for max_windows window slots (= windows decoded concurrently; the encoder runs over at most 256 of
- * them per pass).
+ * them per pass, fewer when enc_positions > 512: about 131 072 / enc_positions, a function of the geometry alone).
  *
  * The decoder's self-attention K / V are PAGED (ABI 5): pages of 8 positions are handed to a slot as its sequence grows and taken
  * back when its window retires, from a pool carved out of the workspace.  wseg_workspace_bytes sizes that pool for the EXPECTED
@@ -152,7 +152,7 @@ size_t wseg_workspace_bytes_kv(const wseg_model* m, int32_t max_windows, int32_t
                                int32_t kv_positions_per_slot);
 
 /*
- * Encoder only: feats device float32 [n_windows][80][1000] -> enc_out device [n_windows][500][d_model]
+ * Encoder only: feats device float32 [n_windows][n_mels][spec_cols] -> enc_out device [n_windows][enc_positions][d_model]
  * in the model dtype.  (HF modeling_whisper.py:592-646 as reached from reference model.py:655.)
  */
 int wseg_encode(wseg_model* m, const float* feats, int32_t n_windows,
@@ -185,7 +185,9 @@ typedef struct {
   uint64_t seed;
   const void* encoder_output;     /* device [n_windows][enc_positions][d_model] in the model dtype: precomputed encoder
                                      states (wseg_encode) used instead of running the encoder on feats (feats may then
-                                     be NULL; rows past the last window must be readable up to a multiple of 256), or NULL */
+                                     be NULL; rows past the last window must be readable up to a multiple of 256 — and, when
+                                     enc_positions > 512, for 256 rows more: the shorter encoder passes of such a geometry
+                                     need not start on a multiple of 256 rows), or NULL */
 } wseg_generate_params;
 
 /*

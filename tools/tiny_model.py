@@ -17,6 +17,7 @@ SOT = 257
 EN = 258
 NOTIMESTAMPS = 259
 TIME0 = 260                      # <|0|> .. <|1000|>  -> 260 .. 1260
+SPEC_COLS = 1000                 # total_spec_columns of the committed fixtures; the functions below take another count (256 .. 3000, even)
 SPECIES = ["<|zebra_finch|>", "<|bengalese_finch|>", "<|mouse|>", "<|marmoset|>", "<|human|>",
            "<|unknown|>", "<|animal|>"]
 SPECIES0 = 1261
@@ -58,12 +59,22 @@ def bytes_to_unicode():
     return dict(zip(bs, [chr(c) for c in cs]))
 
 
-def added_tokens():
+def species0(spec_cols=SPEC_COLS):
+    """First species id: behind the time tokens <|0|> .. <|spec_cols|> (1261 = SPECIES0 at 1000 columns)."""
+    return TIME0 + spec_cols + 1
+
+
+def vocab_size(spec_cols=SPEC_COLS):
+    """The ids in use rounded up to a multiple of 128 (1280 = VOCAB_SIZE at 1000 columns)."""
+    return (species0(spec_cols) + len(SPECIES) + 127) // 128 * 128
+
+
+def added_tokens(spec_cols=SPEC_COLS):
     d = {"<|endoftext|>": EOT, "<|startoftranscript|>": SOT, "<|en|>": EN, "<|notimestamps|>": NOTIMESTAMPS}
-    for i in range(1001):
+    for i in range(spec_cols + 1):
         d["<|%d|>" % i] = TIME0 + i
     for i, s in enumerate(SPECIES):
-        d[s] = SPECIES0 + i
+        d[s] = species0(spec_cols) + i
     return d
 
 
@@ -73,33 +84,38 @@ def base_vocab():
     return {b2u[b]: i for i, b in enumerate(order)}
 
 
-def hf_config_dict(variant="tiny"):
+def hf_config_dict(variant="tiny", spec_cols=SPEC_COLS):
+    """spec_cols: the window length in spectrogram columns, as the reference's `train.py --total_spec_columns` sets it — it drives
+    max_source_positions (= spec_cols / 2 rows of the encoder position table), the time tokens and with them the vocabulary size."""
+    if spec_cols % 2 or not 256 <= spec_cols <= 3000:
+        raise ValueError("spec_cols must be even and in 256 .. 3000")
     v = VARIANTS[variant]
     return dict(
-        model_type="whisper", vocab_size=VOCAB_SIZE, num_mel_bins=80, d_model=v["d_model"],
+        model_type="whisper", vocab_size=vocab_size(spec_cols), num_mel_bins=80, d_model=v["d_model"],
         encoder_layers=v["enc_layers"], decoder_layers=v["dec_layers"], encoder_attention_heads=v["heads"],
         decoder_attention_heads=v["heads"],
-        encoder_ffn_dim=v["ffn"], decoder_ffn_dim=v["ffn"], max_source_positions=500, max_target_positions=448,
+        encoder_ffn_dim=v["ffn"], decoder_ffn_dim=v["ffn"], max_source_positions=spec_cols // 2, max_target_positions=448,
         decoder_start_token_id=SOT, pad_token_id=EOT, eos_token_id=EOT, bos_token_id=EOT,
         activation_function="gelu", scale_embedding=False,
-        total_spec_columns=1000, cluster_codebook=CLUSTER_CODEBOOK,
+        total_spec_columns=spec_cols, cluster_codebook=CLUSTER_CODEBOOK,
         default_segmentation_config={"sr": SR, "spec_time_step": STS, "min_frequency": 0},
     )
 
 
-def write_model_dir(path, state_dict_bf16, variant="tiny"):
-    """HF-style directory: config.json, generation_config.json, vocab.json, added_tokens.json, model.safetensors."""
+def write_model_dir(path, state_dict_bf16, variant="tiny", spec_cols=SPEC_COLS):
+    """HF-style directory: config.json, generation_config.json, vocab.json, added_tokens.json, model.safetensors.
+    The state dict (HF names, any float type) must have the shapes of hf_config_dict(variant, spec_cols)."""
     from safetensors.torch import save_file
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(hf_config_dict(variant), f, indent=1)
+        json.dump(hf_config_dict(variant, spec_cols), f, indent=1)
     with open(os.path.join(path, "generation_config.json"), "w") as f:
         json.dump({"max_length": 448, "suppress_tokens": SUPPRESS, "begin_suppress_tokens": BEGIN_SUPPRESS,
                    "pad_token_id": EOT, "eos_token_id": EOT, "decoder_start_token_id": SOT}, f, indent=1)
     with open(os.path.join(path, "vocab.json"), "w") as f:
         json.dump(base_vocab(), f, ensure_ascii=False)
     with open(os.path.join(path, "added_tokens.json"), "w") as f:
-        json.dump(added_tokens(), f)
+        json.dump(added_tokens(spec_cols), f)
     save_file({k: v.contiguous() for k, v in state_dict_bf16.items()}, os.path.join(path, "model.safetensors"))
 
 

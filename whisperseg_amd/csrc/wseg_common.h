@@ -122,6 +122,10 @@ template <typename I> __host__ __device__ __forceinline__ constexpr I vt_plain_i
 // start of the (window, head) block of V^T, plain or tiled (vt_tiled_index counts from here)
 __host__ __device__ __forceinline__ constexpr size_t enc_vt_block(size_t bh, int t_pad) { return vt_plain_index(bh * 64, t_pad, 0); }
 static_assert(vt_plain_index<size_t>(7 * 64 + 5, 512, 9) == enc_vt_block(7, 512) + vt_plain_index(5, 512, 9), "row = bh * 64 + hd");
+// the longest window: 1500 positions, t_pad 1536.  Offsets inside a (window, head) block stay far inside int (vt_tiled_index, vt_plain_index<int>);
+// everything that counts across windows is size_t (enc_qk_index, enc_vt_block).
+static_assert(vt_plain_index<size_t>(7 * 64 + 5, 1536, 1499) == enc_vt_block(7, 1536) + vt_plain_index(5, 1536, 1499), "row = bh * 64 + hd");
+static_assert(vt_plain_index<int>(63, 1536, 1535) == 64 * 1536 - 1 && enc_qk_index(1, 1536, 0) == enc_vt_block(1, 1536), "Q / K / V^T blocks of a (window, head): 64 * t_pad elements each");
 
 // Element-type traits: T = float (exact-parity mode), bf16_t or f16_t (production modes).
 template <typename T> struct El {      // 16-bit types

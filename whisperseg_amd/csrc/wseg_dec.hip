@@ -368,6 +368,15 @@ __global__ __launch_bounds__(64) void prompt_self_attn_kernel(const float* __res
   }
 }
 
+// Key capacity of the cross-attention kernels: a (slot, head)'s scores and row scales wait in LDS between
+// the K pass and the V pass.  Up to 512 encoder positions every kernel is the instantiation, and the code, it always was; longer windows (up to
+// Whisper's 1500 position rows) run the same body instantiated with a LongKeys<> tag: arrays of CROSS_TK_LONG entries — the two-pass structure, the summation order
+// and one read of every K / V row stay.  LDS per workgroup at 4 beams: 39.5 KB (block-floating-point rows: a quarter of the CU's 160 KB, four
+// workgroups per CU as at 512 keys), 29 KB (packed 16-bit); the general kernel at 8 beams 57 KB, two per CU as its registers allow anyway.
+constexpr int CROSS_TK_LONG = 1504;      // Whisper's 1500 position rows, rounded up to whole 32-row steps of the streaming loops
+template <typename X> struct LongKeys {};      // tag around a kernel's output (packed kernel: element) type: the long-key instantiation
+template <typename X> struct KeyCap { typedef X type; static constexpr int TKM = 512; };
+template <typename X> struct KeyCap<LongKeys<X>> { typedef X type; static constexpr int TKM = CROSS_TK_LONG; };
 // ------------------------------------------------------------------------------------------------
 // Cross-attention, one workgroup per (window, head); all beams of the window in one pass over K and V.
 // HBM-bound (128 KiB of K/V per workgroup).  8 lanes cover one 128-byte K/V row (16 B each), so a wave
@@ -375,11 +384,13 @@ __global__ __launch_bounds__(64) void prompt_self_attn_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------
 // (NB = 8, beams 5..8: 64 query registers per lane — two workgroups per CU instead of four; under the 128-register cap that
 // instantiation spilled 350 bytes per lane)
-template <typename T, typename TO, int NB>
+template <typename T, typename TOK, int NB>
 __global__ __launch_bounds__(256, NB > 4 ? 2 : 4) void dec_cross_attn_kernel(DecodeState st, const T* __restrict__ q, const T* __restrict__ ck,
                                                              const T* __restrict__ cv, void* __restrict__ out, int H, int Tk, int d,
                                                              PartialInfo pi, const T* __restrict__ q_bias, float scale) {
-  __shared__ float sc[NB][512];
+  typedef typename KeyCap<TOK>::type TO;      // (a LongKeys<> tag selects the long-key form)
+  constexpr int TKM = KeyCap<TOK>::TKM;
+  __shared__ float sc[NB][TKM];
   __shared__ float red[4][NB][64];
   __shared__ float sinv[NB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -501,15 +512,17 @@ __global__ __launch_bounds__(256, NB > 4 ? 2 : 4) void dec_cross_attn_kernel(Dec
 // (v_dot2c_f32_bf16 scores are 8 instructions per row shorter still, but sum in another order — one boundary of the
 // tiny-model parity test moved by two mel frames — so the FMA chain stays.)
 // ------------------------------------------------------------------------------------------------
-template <typename HT, int NB>
-__global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState st, const HT* __restrict__ q,
-                                                                   const HT* __restrict__ ck, const HT* __restrict__ cv,
-                                                                   HT* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
-                                                                   const HT* __restrict__ q_bias, float scale) {
+template <typename HTK, int NB>
+__global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState st, const typename KeyCap<HTK>::type* __restrict__ q,
+                                                                   const typename KeyCap<HTK>::type* __restrict__ ck, const typename KeyCap<HTK>::type* __restrict__ cv,
+                                                                   typename KeyCap<HTK>::type* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
+                                                                   const typename KeyCap<HTK>::type* __restrict__ q_bias, float scale) {
+  typedef typename KeyCap<HTK>::type HT;      // (a LongKeys<> tag selects the long-key form)
+  constexpr int TKM = KeyCap<HTK>::TKM;
   typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
   typedef float f2 __attribute__((ext_vector_type(2)));
   constexpr int U = 8;                                  // K/V rows in flight per lane
-  __shared__ float sc[NB][512];
+  __shared__ float sc[NB][TKM];
   __shared__ float red[4][NB][64];
   __shared__ float sinv[NB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -632,6 +645,7 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState s
   __syncthreads();
   WSEG_STAMP(2, 5);                                 // softmax
   static_assert(NB == 1 || NB == 2 || NB == 4, "beam tiles");
+  static_assert(3 * TKM * 4 < 65536, "ds_read offset field");
   const unsigned sc_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)&sc[0][0];
   f2 acc[NB][4];
 #pragma unroll
@@ -655,12 +669,13 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState s
       // other waves issue between these instructions, so an earlier read can land before a later one is issued.
       float pr[NB];
       const unsigned pa = sc_base + (unsigned)tc * 4u;
+      constexpr int BS = TKM * 4;      // bytes between two beams' scores of a position (the 16-bit offset field reaches beam 3 of CROSS_TK_LONG keys)
       if constexpr (NB == 1) asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pr[0]) : "v"(pa) : "memory");
       else if constexpr (NB == 2)
-        asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:2048\n\ts_waitcnt lgkmcnt(0)" : "=&v"(pr[0]), "=&v"(pr[1]) : "v"(pa) : "memory");
+        asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:%3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(pr[0]), "=&v"(pr[1]) : "v"(pa), "n"(BS) : "memory");
       else
-        asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:2048\n\tds_read_b32 %2, %4 offset:4096\n\tds_read_b32 %3, %4 offset:6144\n\t"
-                     "s_waitcnt lgkmcnt(0)" : "=&v"(pr[0]), "=&v"(pr[1]), "=&v"(pr[2]), "=&v"(pr[3]) : "v"(pa) : "memory");
+        asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:%5\n\tds_read_b32 %2, %4 offset:%6\n\tds_read_b32 %3, %4 offset:%7\n\t"
+                     "s_waitcnt lgkmcnt(0)" : "=&v"(pr[0]), "=&v"(pr[1]), "=&v"(pr[2]), "=&v"(pr[3]) : "v"(pa), "n"(BS), "n"(2 * BS), "n"(3 * BS) : "memory");
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         const float p = (ok && j < nb) ? pr[j] : 0.f;
@@ -701,16 +716,18 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_pk_kernel(DecodeState s
 // neither streaming loop carries another register.  (Not done: requesting the first K rows in front of the query reduction — the rows
 // live across reduce1 and spill at 128 registers, r06: 8 rows 8-24 VGPRs, 4 rows 4-31.)
 // ------------------------------------------------------------------------------------------------
-template <typename TO, int NB>
+template <typename TOK, int NB>
 __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState st, const float* __restrict__ q,
                                                                     const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                     void* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
                                                                     const float* __restrict__ q_bias, float scale, const int* __restrict__ kv_slot) {
+  typedef typename KeyCap<TOK>::type TO;      // (a LongKeys<> tag selects the long-key form)
+  constexpr int TKM = KeyCap<TOK>::TKM;
   typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
   typedef unsigned int raw8 __attribute__((ext_vector_type(2)));
   typedef float f2 __attribute__((ext_vector_type(2)));
   constexpr int U = 8;
-  __shared__ __attribute__((aligned(16))) float sc[512][NB];      // [position][beam]: one read per row in the V pass
+  __shared__ __attribute__((aligned(16))) float sc[TKM][NB];      // [position][beam]: one read per row in the V pass
   __shared__ float red[4][NB][64];
   __shared__ float sinv[NB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -730,11 +747,14 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
   const float* Vs = (const float*)KV::scale_plane(Vb, Tk);
   // the row scales wait in LDS for the softmax pass (read from global there, each wave's first access paid an HBM round trip with no
   // stream in flight); visible behind the barrier that closes the score pass
-  __shared__ float sks[512], svs[512];
+  __shared__ float sks[TKM], svs[TKM];
   for (int t = tid; t < Tk; t += 256) { sks[t] = Ks[t]; svs[t] = Vs[t]; }
   constexpr int NP = (NB + 1) / 2;
   f2 qq[8][NP];
-  __shared__ float sq[NB][64];                          // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS
+  // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS.  Long-key form: the slices borrow `red`, which is idle until
+  // the V pass is over (barriers in between) — the 4-beam instantiation then fits four times into the CU's 160 KB like the 512-key one
+  __shared__ float sq_own[TKM > 512 ? 1 : NB][64];
+  float (*sq)[64] = TKM > 512 ? red[0] : sq_own;
   raw16 kh[U];
   raw8 kl[U];
   auto load_k = [&](int t0) {
@@ -896,18 +916,20 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_k24_kernel(DecodeState 
 // ------------------------------------------------------------------------------------------------
 // Occupancy: four workgroups per CU (128 registers).  The 4-beam instantiation fits with 5 instead of 8 V rows per lane in flight and the
 // scores as [position][beam] (one 16-byte LDS read per row instead of four addresses); with 8 it needs 168 registers = three per CU.
-template <typename TO, int NB>
+template <typename TOK, int NB>
 __global__ __launch_bounds__(256, 4) void dec_cross_attn_bfp_kernel(DecodeState st, const float* __restrict__ q,
                                                                     const unsigned char* __restrict__ ck, const unsigned char* __restrict__ cv,
                                                                     void* __restrict__ out, int H, int Tk, int d, PartialInfo pi,
                                                                     const float* __restrict__ q_bias, float scale, const int* __restrict__ kv_slot) {
+  typedef typename KeyCap<TOK>::type TO;      // (a LongKeys<> tag selects the long-key form)
+  constexpr int TKM = KeyCap<TOK>::TKM;
   typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
   typedef float f2 __attribute__((ext_vector_type(2)));
   constexpr int U = 8;
-  __shared__ __attribute__((aligned(16))) float sc[512][NB];      // [position][beam]: one 16-byte read per row in the V pass
+  __shared__ __attribute__((aligned(16))) float sc[TKM][NB];      // [position][beam]: one 16-byte read per row in the V pass
   __shared__ float red[4][NB][64];
   __shared__ float sinv[NB];
-  __shared__ float sks[512], svs[512];                 // the row scales of this (slot, head): 2 x 2 KB, fetched once with coalesced loads (as
+  __shared__ float sks[TKM], svs[TKM];                 // the row scales of this (slot, head): 2 x 2 KB, fetched once with coalesced loads (as
                                                        // 4-byte loads beside the rows they doubled the kernel's VMEM instructions: 5.2 TB/s)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int w = blockIdx.x / H, h = blockIdx.x - w * H;
@@ -922,7 +944,10 @@ __global__ __launch_bounds__(256, 4) void dec_cross_attn_bfp_kernel(DecodeState 
   const float* Vs = (const float*)KV::scale_plane(Vb, Tk);
   constexpr int NP = (NB + 1) / 2;
   f2 qq[8][NP];
-  __shared__ float sq[NB][64];                          // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS
+  // thread (j, e) finishes dim e of beam j (reduce1), slices come back from LDS.  Long-key form: the slices borrow `red`, which is idle until
+  // the V pass is over (barriers in between) — the 4-beam instantiation then fits four times into the CU's 160 KB like the 512-key one
+  __shared__ float sq_own[TKM > 512 ? 1 : NB][64];
+  float (*sq)[64] = TKM > 512 ? red[0] : sq_own;
   // The first batch of K rows is requested BEFORE the query is assembled (reduce1: a chain of dependent split-K loads) and the first
   // batch of V rows before the softmax: neither depends on what it overtakes, and the kernel's fixed costs (~170 us of a 464-us launch at
   // 1 024 slots by a two-point fit against the 24-bit format) are exactly these serial sections.
@@ -1498,15 +1523,18 @@ int launch_dec_self_attn(int dtype, const DecodeState& st, const void* q, void* 
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }
+#define WSEG_KEYS_512(X_) X_
+#define WSEG_KEYS_LONG(X_) LongKeys<X_>
+#define WSEG_BY_TK(LAUNCH_, ...) do { if (Tk <= 512) LAUNCH_(WSEG_KEYS_512, __VA_ARGS__); else LAUNCH_(WSEG_KEYS_LONG, __VA_ARGS__); } while (0)
 template <typename T, typename TO>
 static void launch_cross_t(const DecodeState& st, const void* q, const void* ck, const void* cv, void* out, int H, int Tk, int d,
                            const PartialInfo& pi, const void* qb, float scale, hipStream_t s) {
   dim3 grid(st.W * H), block(256);
-#define WSEG_CA(NB_) hipLaunchKernelGGL((dec_cross_attn_kernel<T, TO, NB_>), grid, block, 0, s, st, (const T*)q, (const T*)ck, (const T*)cv, out, H, Tk, d, pi, (const T*)qb, scale)
-  if (st.nb <= 1) WSEG_CA(1);
-  else if (st.nb <= 2) WSEG_CA(2);
-  else if (st.nb <= 4) WSEG_CA(4);
-  else WSEG_CA(8);
+#define WSEG_CA(K_, NB_) hipLaunchKernelGGL((dec_cross_attn_kernel<T, K_(TO), NB_>), grid, block, 0, s, st, (const T*)q, (const T*)ck, (const T*)cv, out, H, Tk, d, pi, (const T*)qb, scale)
+  if (st.nb <= 1) WSEG_BY_TK(WSEG_CA, 1);
+  else if (st.nb <= 2) WSEG_BY_TK(WSEG_CA, 2);
+  else if (st.nb <= 4) WSEG_BY_TK(WSEG_CA, 4);
+  else WSEG_BY_TK(WSEG_CA, 8);
 #undef WSEG_CA
 }
 // wseg_kernels.h.  The three-MFMA modes' GEMMs are exact to ~6e-6 of a logit on the parity sweeps' models; the 24-bit FLOAT rows they
@@ -1524,35 +1552,35 @@ bool dec_cross_attn_writes_mx(int dtype, int nb) { return dtype == WSEG_F16M6 &&
 
 int launch_dec_cross_attn(int dtype, const DecodeState& st, const void* q, const void* ck, const void* cv, void* out, int H, int Tk, int d,
                           const PartialInfo* q_part, const void* q_bias, float scale, hipStream_t s, const int* kv_slot) {
-  if (Tk > 512) { set_error("cross-attention: %d encoder positions > 512", Tk); return WSEG_ERR_INVALID; }
+  if (Tk > CROSS_TK_LONG) { set_error("cross-attention: %d encoder positions > %d", Tk, CROSS_TK_LONG); return WSEG_ERR_INVALID; }
   PartialInfo pi;
   if (q_part) pi = *q_part;
   const bool m6 = dtype == WSEG_F16M6;      // M6-row output from the block-floating-point K / V kernel only (dec_cross_attn_writes_mx)
   const int kvf = (dtype == WSEG_BF16X3 || dtype == WSEG_F16X3 || m6) ? x3_cross_kv_format(dtype, st.nb) : 0;
   if (kvf == 2) {      // f16m6
     dim3 grid(st.W * H), block(256);
-#define WSEG_BFP(NB_) hipLaunchKernelGGL((dec_cross_attn_bfp_kernel<M6, NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
-    if (st.nb <= 1) WSEG_BFP(1); else if (st.nb <= 2) WSEG_BFP(2); else WSEG_BFP(4);
+#define WSEG_BFP(K_, NB_) hipLaunchKernelGGL((dec_cross_attn_bfp_kernel<K_(M6), NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
+    if (st.nb <= 1) WSEG_BY_TK(WSEG_BFP, 1); else if (st.nb <= 2) WSEG_BY_TK(WSEG_BFP, 2); else WSEG_BY_TK(WSEG_BFP, 4);
 #undef WSEG_BFP
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
   if (kvf == 3) {      // bf16x3 / f16x3
     dim3 grid(st.W * H), block(256);
-#define WSEG_K24(TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_k24_kernel<TO_, NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
-    if (dtype == WSEG_BF16X3) { if (st.nb <= 1) WSEG_K24(X3<bf16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<bf16_t>, 2); else WSEG_K24(X3<bf16_t>, 4); }
-    else { if (st.nb <= 1) WSEG_K24(X3<f16_t>, 1); else if (st.nb <= 2) WSEG_K24(X3<f16_t>, 2); else WSEG_K24(X3<f16_t>, 4); }
+#define WSEG_K24(K_, TO_, NB_) hipLaunchKernelGGL((dec_cross_attn_k24_kernel<K_(TO_), NB_>), grid, block, 0, s, st, (const float*)q, (const unsigned char*)ck, (const unsigned char*)cv, out, H, Tk, d, pi, (const float*)q_bias, scale, kv_slot)
+    if (dtype == WSEG_BF16X3) { if (st.nb <= 1) WSEG_BY_TK(WSEG_K24, X3<bf16_t>, 1); else if (st.nb <= 2) WSEG_BY_TK(WSEG_K24, X3<bf16_t>, 2); else WSEG_BY_TK(WSEG_K24, X3<bf16_t>, 4); }
+    else { if (st.nb <= 1) WSEG_BY_TK(WSEG_K24, X3<f16_t>, 1); else if (st.nb <= 2) WSEG_BY_TK(WSEG_K24, X3<f16_t>, 2); else WSEG_BY_TK(WSEG_K24, X3<f16_t>, 4); }
 #undef WSEG_K24
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
   if (kv_slot) { set_error("cross-attention: the slot map exists for the block-floating-point K / V kernels only"); return WSEG_ERR_INVALID; }
   static const bool deep = getenv("WSEG_CROSS_NO_PK") == nullptr;         // tuning knob: fp32-FMA kernel
-  if ((dtype == WSEG_BF16 || dtype == WSEG_F16) && deep && Tk <= 512 && st.nb <= 4) {
+  if ((dtype == WSEG_BF16 || dtype == WSEG_F16) && deep && st.nb <= 4) {
     dim3 grid(st.W * H), block(256);
-#define WSEG_PK(HT_, NB_) hipLaunchKernelGGL((dec_cross_attn_pk_kernel<HT_, NB_>), grid, block, 0, s, st, (const HT_*)q, (const HT_*)ck, (const HT_*)cv, (HT_*)out, H, Tk, d, pi, (const HT_*)q_bias, scale)
-    if (dtype == WSEG_BF16) { if (st.nb <= 1) WSEG_PK(bf16_t, 1); else if (st.nb <= 2) WSEG_PK(bf16_t, 2); else WSEG_PK(bf16_t, 4); }
-    else { if (st.nb <= 1) WSEG_PK(f16_t, 1); else if (st.nb <= 2) WSEG_PK(f16_t, 2); else WSEG_PK(f16_t, 4); }
+#define WSEG_PK(K_, HT_, NB_) hipLaunchKernelGGL((dec_cross_attn_pk_kernel<K_(HT_), NB_>), grid, block, 0, s, st, (const HT_*)q, (const HT_*)ck, (const HT_*)cv, (HT_*)out, H, Tk, d, pi, (const HT_*)q_bias, scale)
+    if (dtype == WSEG_BF16) { if (st.nb <= 1) WSEG_BY_TK(WSEG_PK, bf16_t, 1); else if (st.nb <= 2) WSEG_BY_TK(WSEG_PK, bf16_t, 2); else WSEG_BY_TK(WSEG_PK, bf16_t, 4); }
+    else { if (st.nb <= 1) WSEG_BY_TK(WSEG_PK, f16_t, 1); else if (st.nb <= 2) WSEG_BY_TK(WSEG_PK, f16_t, 2); else WSEG_BY_TK(WSEG_PK, f16_t, 4); }
 #undef WSEG_PK
   } else if (dtype == WSEG_BF16) launch_cross_t<bf16_t, bf16_t>(st, q, ck, cv, out, H, Tk, d, pi, q_bias, scale, s);
   else if (dtype == WSEG_F16) launch_cross_t<f16_t, f16_t>(st, q, ck, cv, out, H, Tk, d, pi, q_bias, scale, s);

@@ -50,8 +50,8 @@ struct EpiParams {
   void* k = nullptr;
   void* v = nullptr;
   int d_model = 0;
-  int t_len = 1;               // rows per window (500)
-  int t_pad = 1;               // padded rows per (b,h) slab (512)
+  int t_len = 1;               // rows per window (128 .. 1500, default 500)
+  int t_pad = 1;               // padded rows per (b,h) slab (t_len rounded up to 128: 512 .. 1536)
   int n_heads = 1;
   const int* pos_ptr = nullptr;  // device [rows / pos_div]: current decode position of each window slot (EPI_QKV_DEC)
   int pos_div = 1;               // rows (beams) per slot
@@ -139,7 +139,8 @@ int x3_cross_kv_format(int dtype, int nb);
 //   scale plane [t_len] fp32        the row's power of two (format 3: 2^(s - 8), value = 256 q * scale)
 // A block starts ROW_BYTES * t_len * (slot * heads + head) bytes into the buffer, and ROW_BYTES is 4 * 33 (format 2) or 4 * 49 (format 3):
 // blocks are 16-byte aligned only when t_len % 4 == 0 (the planes inside a block then are too).  Other lengths rely on the hardware's
-// unaligned global access for the 16-byte row accesses.  (Padding the stride would change the workspace size.)
+// unaligned global access for the 16-byte row accesses, at every length — 251 positions as much as the 750 of a 1500-column checkpoint, in the
+// long-key instantiations of the readers like in the others.  (Padding the stride would change the workspace size.)
 template <int FMT> struct CrossKv {
   static_assert(FMT == 2 || FMT == 3, "the packed formats; format 0 is plain rows of 64 elements");
   static constexpr int HI_STRIDE = 64 * 2, LOW_STRIDE = FMT == 3 ? 64 : 0, SCALE_STRIDE = 4;      // bytes per position in each plane

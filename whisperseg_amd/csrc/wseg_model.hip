@@ -133,6 +133,13 @@ void add_slot(wseg_model* m, const std::string& name, const void** field, size_t
 // 10 MB per window in the 16-bit modes, 20 MB in the split modes) then stop growing with the slot count, and a pass of 256
 // windows (128 000 rows: the r01 / r02 headline workload) already fills the chip for tens of rounds.
 constexpr int ENC_CHUNK = 256;
+// Windows of more than 512 encoder positions (up to Whisper's 1500): a pass keeps about the 131 072 rows of 256 windows of 512, so the
+// activation buffers and the pass's fixed GEMM plan stay the size they are at 500 positions — 224 windows at 576 positions, 160 at 750,
+// 80 at 1500.  A function of the geometry alone: a window's tokens must not depend on how many windows were admitted with it.
+int enc_chunk(const wseg_model_config& c) {
+  if (c.enc_positions <= 512) return ENC_CHUNK;
+  return std::max(16, (ENC_CHUNK * 512 / c.enc_positions) & ~15);
+}
 // Default self-K/V pool of wseg_workspace_bytes: positions per slot, or max_length if that is smaller.
 constexpr int KV_DEFAULT_POSITIONS = 64;
 
@@ -145,23 +152,24 @@ size_t kv_unit_bytes(const wseg_model* m, int nb) {      // one unit: every laye
   return (size_t)m->cfg.dec_layers * 2 * kv_pool_rows(1, nb, m->cfg.n_heads) * 64 * m->es;
 }
 
-// Lay out the workspace for W window slots (encoder passes of up to min(W, ENC_CHUNK) windows), nb beams, capacity L positions,
+// Lay out the workspace for W window slots (encoder passes of up to min(W, enc_chunk) windows), nb beams, capacity L positions,
 // kv_units pool units of self-attention K / V.  base may be null (size query).
 void make_plan(const wseg_model* m, int W, int nb, int L, int kv_units, char* base, Plan& p) {
   const wseg_model_config& c = m->cfg;
   const size_t es = m->es;
   const size_t d = c.d_model, H = c.n_heads, ffn = c.ffn;
-  const int We = W < ENC_CHUNK ? W : ENC_CHUNK;
+  const int We = std::min(W, enc_chunk(c));
   const size_t M1p = align_up((size_t)We * c.spec_cols, 256), Mp = align_up((size_t)We * c.enc_positions, 256);
-  char* cur = base;
-  auto take = [&](size_t bytes) { char* q = cur; cur += align_up(bytes, 256); return q; };
+  size_t used = 0;      // (offsets, not pointers: a size query has no base to step from)
+  auto at = [&](char* from, size_t bytes) -> char* { return from ? from + bytes : nullptr; };
+  auto take = [&](size_t bytes) { char* q = at(base, used); used += align_up(bytes, 256); return q; };
   // encoder: a1 | h1 | a2 are dead once conv2 has run; hbuf reuses their space.
   const size_t conv_bytes = align_up(M1p * m->kp1 * es, 256) + align_up(M1p * d * es, 256) + align_up(Mp * 3 * d * es, 256);
   const size_t hbuf_bytes = align_up(Mp * ffn * es, 256);
   char* u = take(conv_bytes > hbuf_bytes ? conv_bytes : hbuf_bytes);
   p.a1 = u;
-  p.h1 = p.a1 + align_up(M1p * m->kp1 * es, 256);
-  p.a2 = p.h1 + align_up(M1p * d * es, 256);
+  p.h1 = at(p.a1, align_up(M1p * m->kp1 * es, 256));
+  p.a2 = at(p.h1, align_up(M1p * d * es, 256));
   p.hbuf = u;
   p.x = take(Mp * d * 4);                          // the residual stream is fp32 in every mode
   p.y = take(Mp * d * es);
@@ -242,13 +250,13 @@ void make_plan(const wseg_model* m, int W, int nb, int L, int kv_units, char* ba
   st.cand_val = (float*)take(R * MAX_CAND * 4);
   st.cand_tok = (int*)take(R * MAX_CAND * 4);
   st.sup_mask = (const unsigned char*)q.mask;
-  p.total = (size_t)(cur - base);
+  p.total = used;
 }
 
 int check_geometry(const wseg_model_config& c) {
   if (c.d_model <= 0 || c.n_heads <= 0 || c.d_model != c.n_heads * 64) { set_error("d_model %d must be n_heads %d * 64", c.d_model, c.n_heads); return WSEG_ERR_INVALID; }
   if (c.d_model % 128 || c.ffn % 128) { set_error("d_model/ffn must be multiples of 128"); return WSEG_ERR_INVALID; }
-  if (c.spec_cols != 2 * c.enc_positions || c.enc_positions > 512 || c.enc_positions < 128) { set_error("spec_cols %d / enc_positions %d unsupported", c.spec_cols, c.enc_positions); return WSEG_ERR_INVALID; }
+  if (c.spec_cols != 2 * c.enc_positions || c.enc_positions > 1500 || c.enc_positions < 128) { set_error("spec_cols %d / enc_positions %d unsupported", c.spec_cols, c.enc_positions); return WSEG_ERR_INVALID; }
   if (c.n_mels <= 0 || c.n_mels > 96) { set_error("n_mels %d unsupported", c.n_mels); return WSEG_ERR_INVALID; }
   if (c.dec_positions <= 0 || c.dec_positions > 512) { set_error("dec_positions %d unsupported", c.dec_positions); return WSEG_ERR_INVALID; }
   if (c.dtype < WSEG_F32 || c.dtype > WSEG_F16M6) { set_error("dtype %d unsupported", c.dtype); return WSEG_ERR_INVALID; }
@@ -555,8 +563,9 @@ extern "C" int wseg_encode(wseg_model* m, const float* feats, int32_t n_windows,
   make_plan(m, n_windows, 1, 8, kv_default_units(n_windows, 8), aligned_base(workspace), p);
   if (p.total + 256 > workspace_bytes) { set_error("workspace too small: need %zu, have %zu", p.total + 256, workspace_bytes); return WSEG_ERR_STATE; }
   const size_t feat_stride = (size_t)m->cfg.n_mels * m->cfg.spec_cols;
-  for (int w0 = 0; w0 < n_windows; w0 += ENC_CHUNK) {      // passes of at most ENC_CHUNK windows (the encoder buffers' size)
-    const int n = std::min(ENC_CHUNK, n_windows - w0);
+  const int chunk = enc_chunk(m->cfg);
+  for (int w0 = 0; w0 < n_windows; w0 += chunk) {      // passes of at most enc_chunk windows (the encoder buffers' size)
+    const int n = std::min(chunk, n_windows - w0);
     WSEG_TRY(run_encoder(m, feats + (size_t)w0 * feat_stride, n, p, p.enc_out, s));
     const size_t rows = (size_t)n * m->cfg.enc_positions, row0 = (size_t)w0 * m->cfg.enc_positions;
     if (m->x3) WSEG_TRY(launch_operand_to_f32(m->sdt, p.enc_out, (float*)enc_out + row0 * m->cfg.d_model, rows, m->cfg.d_model, s));
@@ -646,8 +655,9 @@ struct GenerateRun {
     const int d = c.d_model, H = c.n_heads, Tk = c.enc_positions;
     const size_t cross_stride = cross_kv_layer_bytes(kv24, m->es, S, H, Tk);
     const size_t feat_stride = (size_t)c.n_mels * c.spec_cols;
-    for (int c0 = 0; c0 < n; c0 += ENC_CHUNK) {
-      const int nc = std::min(ENC_CHUNK, n - c0), wc = w0 + c0;
+    const int chunk = enc_chunk(c);
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+      const int nc = std::min(chunk, n - c0), wc = w0 + c0;
       int e0, e1, e2;
       WSEG_TRY(timing_event(ln, s, &e0));
       const char* enc_rows = p.enc_out;
@@ -669,7 +679,7 @@ struct GenerateRun {
         // family with a split-K count that follows the row count — a window's cross K / V (and through their block-floating-point
         // rounding its tokens on a near-tie) would depend on how many windows were admitted with it.  The un-split large-tile
         // families compute every output element as the same K-ordered MFMA chain (r06, with GemmArgs::plan_m for the pass).
-        WSEG_TRY(gemm(m, EPI_KV_CROSS, enc_rows, d, m->dec[l].ckv_w, d, nc * Tk, 2 * d, d, e, &q, s, nullptr, ENC_CHUNK * Tk));
+        WSEG_TRY(gemm(m, EPI_KV_CROSS, enc_rows, d, m->dec[l].ckv_w, d, nc * Tk, 2 * d, d, e, &q, s, nullptr, chunk * Tk));
       }
       WSEG_TRY(timing_event(ln, s, &e2));
       ln.ev_enc.push_back(e0); ln.ev_enc.push_back(e1); ln.ev_ckv.push_back(e1); ln.ev_ckv.push_back(e2);

@@ -395,7 +395,8 @@ class Engine:
         return s
 
     def encode(self, feats):
-        """feats float32 device tensor [W, 80, 1000] -> [W, 500, d] in the model dtype (float32 in the split-precision modes)."""
+        """feats float32 device tensor [W, 80, spec_cols] -> [W, enc_positions, d] (1000 -> 500 by default; up to 3000 -> 1500) in the
+        model dtype (float32 in the split-precision modes)."""
         feats = feats.to(device=self.device, dtype=torch.float32).contiguous()
         W = feats.shape[0]
         ws = self._workspace(W, 1, 8, may_shrink=False)
@@ -409,7 +410,7 @@ class Engine:
                  suppress_tokens=(), begin_suppress_tokens=(), return_first_logits=False, n_slots=None, refill_min=0,
                  lookahead=0, window_max_length=None, encoder_output=None, top_k=1, top_p=1.0, seed=0, kv_positions=0,
                  snapshot_steps=None):
-        """Greedy / beam-search decode of ALL windows of `feats` [N, 80, 1000] through `n_slots` window slots with
+        """Greedy / beam-search decode of ALL windows of `feats` [N, 80, spec_cols] through `n_slots` window slots with
         in-flight refill (a finished window's slot goes to the next queued window; wseg_generate; see pick_slots for the
         default slot count).  `top_k` in 2..16 with
         num_beams == 1 samples (top-k, then nucleus `top_p`) with a counter-based generator keyed by `seed`.
@@ -470,9 +471,10 @@ class Engine:
                 raise ValueError("window_max_length needs one entry per window")
             gp.window_max_length = wml.data_ptr()
         enc = None
-        if encoder_output is not None:         # precomputed encoder states [W, 500, d] (padded to the GEMM's 256-row granularity)
+        if encoder_output is not None:         # precomputed encoder states [W, enc_positions, d] (padded to the GEMM's 256-row granularity,
+            # and by 256 rows more for windows of more than 512 positions, whose encoder passes may start off that granularity: include/wseg.h)
             enc = encoder_output.to(device=self.device, dtype=self.torch_dtype).reshape(W * self.geo["enc_positions"], self.geo["d_model"])
-            pad = _round_up(enc.shape[0], 256) - enc.shape[0]
+            pad = _round_up(enc.shape[0], 256) - enc.shape[0] + (256 if self.geo["enc_positions"] > 512 else 0)
             enc = torch.nn.functional.pad(enc, (0, 0, 0, pad)).contiguous()
             gp.encoder_output = enc.data_ptr()
         tokens = torch.empty((W, max_length), dtype=torch.int32, device=self.device)
