@@ -109,6 +109,22 @@ int wseg_resample_f32(const float* x, int64_t n_in, const float* taps, int32_t n
                       int32_t pre_pad, int32_t pre_remove, float* y, int64_t n_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * WAVE sample decode (audio ingest).
+ * Replaces the decoding half of `librosa.load(path, sr=None)` at reference scripts/segment.py:48,61 and evaluate.py:58:
+ * sample formats widened to float32 in [-1, 1) and channels averaged to mono, with the float32 bits
+ * whisperseg_amd/wavio.py::load_wav produces on the host (u8 (x - 128) / 128, s16 x / 2^15, s24 sign-extended / 2^23,
+ * s32 one int -> float32 rounding then the exact scale 2^-31, f32 copied, f64 one round-to-nearest-even conversion; channels:
+ * numpy's float32 mean(axis=1), i.e. a sum from +0 in numpy's order — left to right below 8 channels, pairwise from 8 on — and
+ * one division by float(channels)).  Added without moving WSEG_ABI_VERSION (an addition, see wseg_debug_step_snapshot_*).
+ * ---------------------------------------------------------------------------------------------- */
+typedef enum { WSEG_PCM_U8 = 0, WSEG_PCM_S16 = 1, WSEG_PCM_S24 = 2, WSEG_PCM_S32 = 3,
+               WSEG_PCM_F32 = 4, WSEG_PCM_F64 = 5 } wseg_pcm_format;
+/* raw: device, interleaved little-endian frames exactly as they sit in a WAVE data chunk, 16-byte aligned, readable up to
+ * the next multiple of 16 bytes behind n_frames * channels * bytes_per_sample.  out: device float32 [n_frames], mono (any
+ * float alignment; 16-byte aligned for 16-byte stores).  channels 1..64.  n_frames == 0 launches nothing.  Stream-ordered. */
+int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

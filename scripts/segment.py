@@ -15,7 +15,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
-from whisperseg_amd.wavio import load_wav  # noqa: E402
+from whisperseg_amd.wavio import load_wav, load_wav_device  # noqa: E402
 
 
 def build_parser():
@@ -56,13 +56,14 @@ def main(argv=None):
         columns, rows = ["filename", "onset", "offset", "cluster"], []
         paths = glob.glob(args.audio_folder + "/*.wav") + glob.glob(args.audio_folder + "/*.WAV")
         # same rows as the reference's serial loop, but the windows of many files share the engine's decode slots; files
-        # are read lazily, group by group, so a large folder needs no more memory than a small one
-        results = segmenter.segment_batch((load_wav(path) for path in paths), **kwargs)
+        # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
+        # a large folder needs no more memory than a small one
+        results = segmenter.segment_files(paths, **kwargs)
         for path, res in zip(paths, results):
             name = os.path.basename(path)
             rows += [(name, on, off, c) for on, off, c in zip(res["onset"], res["offset"], res["cluster"])]
     else:
-        audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read())) if args.audio_path == "-" else load_wav(args.audio_path)
+        audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read())) if args.audio_path == "-" else load_wav_device(args.audio_path)
         res = segmenter.segment(audio, sr, **kwargs)
         columns = ["onset", "offset", "cluster"]
         rows = list(zip(res["onset"], res["offset"], res["cluster"]))

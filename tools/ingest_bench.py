@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""A/B of the audio ingest on one MI355X: host decode (wavio.load_wav, numpy, one thread) against the device decode
+(wseg_pcm_to_mono_f32) and the folder pipeline on top of it (SegmenterBase.segment_files).
+
+    python tools/ingest_bench.py [--files 64] [--seconds 60] [--out profiles/ingest_ab.txt]
+
+For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
+`--seconds` seconds into a temporary directory and reports
+  * load_wav: frames/s of the host decode (file read from the page cache included, as the folder mode pays it),
+  * the kernel alone: GB/s (bytes read + bytes written) from HIP events, warm, median of 20, on one file's samples and on the
+    samples of the whole folder in one launch,
+  * wall time of the folder through segment_batch((load_wav(p) for p in paths)) and through segment_files(paths): the same
+    engine, the same results (checked), one process.
+The engine is bench.py's: whisperseg-large geometry with seeded random weights in the default mode, spec_time_step 0.01 (10 s
+windows), decode length capped at --max-length (random weights emit no meaningful EOS, so every window runs that long)."""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+CASES = (("s16", 1, 16000), ("s16", 2, 48000), ("s24", 2, 96000))
+
+
+def write_folder(d, fmt, channels, sr, files, seconds):
+    import wav_cases as WC
+    rng = np.random.default_rng(1)
+    n = seconds * sr
+    t = np.arange(n) / sr
+    blobs = []
+    for k in range(4):                       # four distinct signals, cycled
+        x = 0.3 * np.sin(2 * np.pi * (700 + 300 * k) * t) + 0.05 * rng.standard_normal(n)
+        full = 1 << (WC.TAG_BITS[fmt][1] - 1)
+        q = np.clip(np.round(x * full), -full, full - 1).astype(np.int64)
+        inter = np.stack([q] + [q // (c + 2) for c in range(channels - 1)], axis=1).reshape(-1)
+        blobs.append(WC.wav_bytes(fmt, channels, sr, WC.sample_bytes(fmt, inter)))
+    paths = []
+    for i in range(files):
+        paths.append(os.path.join(d, "rec%03d.wav" % i))
+        with open(paths[-1], "wb") as f:
+            f.write(blobs[i % 4])
+    return paths
+
+
+def kernel_gbps(lib, raw_bytes, n_frames, channels, fmt_code):
+    import torch
+    from whisperseg_amd import _lib
+    raw = torch.zeros(-(-len(raw_bytes) // 16) * 16, dtype=torch.uint8, device="cuda")
+    raw[:len(raw_bytes)] = torch.from_numpy(np.frombuffer(raw_bytes, np.uint8).copy()).cuda()
+    out = torch.empty(n_frames, dtype=torch.float32, device="cuda")
+    call = lambda: _lib.check(lib.wseg_pcm_to_mono_f32(raw.data_ptr(), n_frames, channels, fmt_code, out.data_ptr(), _lib.stream_ptr()))
+    for _ in range(3):
+        call()
+    ms = []
+    for _ in range(20):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        call()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    med = statistics.median(ms)
+    return (len(raw_bytes) + 4 * n_frames) / (med * 1e-3) / 1e9, med
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=64)
+    ap.add_argument("--seconds", type=int, default=60)
+    ap.add_argument("--max-length", type=int, default=32)
+    ap.add_argument("--model", default="large")
+    ap.add_argument("--dtype", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    import torch
+    import bench
+    from whisperseg_amd import _lib
+    from whisperseg_amd.engine import Engine
+    from whisperseg_amd.model import DEFAULT_DTYPE
+    from whisperseg_amd.wavio import load_wav, read_wav_raw
+    lib = _lib.load(require_device=True)
+    args.dtype = args.dtype or DEFAULT_DTYPE
+    seg = bench.make_segmenter(args, Engine.random(bench.hf_config(args.model), "cuda:0", args.dtype, seed=0))
+    kw = dict(spec_time_step=0.01, max_length=args.max_length)
+    lines = ["ingest A/B: %d files x %d s per format, whisperseg-%s %s (seeded random weights), spec_time_step 0.01, max_length %d, %s"
+             % (args.files, args.seconds, args.model, args.dtype, args.max_length, torch.cuda.get_device_name(0))]
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    for fmt, channels, sr in CASES:
+        with tempfile.TemporaryDirectory() as d:
+            paths = write_folder(d, fmt, channels, sr, args.files, args.seconds)
+            name = "%s x%d %d Hz" % (fmt, channels, sr)
+            t0 = time.perf_counter()
+            frames = sum(len(load_wav(p)[0]) for p in paths)
+            host_s = time.perf_counter() - t0
+            emit("%-18s load_wav (host)      %8.1f M frames/s  (%.2f s for the folder)" % (name, frames / host_s / 1e6, host_s))
+            raw = read_wav_raw(paths[0])
+            one = bytes(raw.data)
+            for label, data, n in (("one file", one, raw.n_frames), ("folder, one launch", one * min(args.files, 16), raw.n_frames * min(args.files, 16))):
+                gbps, ms = kernel_gbps(lib, data, n, raw.channels, raw.format)
+                emit("%-18s kernel, %-18s %8.1f GB/s  %8.1f M frames/s  (%.3f ms, median of 20)" % (name, label, gbps, n / ms / 1e3, ms))
+            seg.segment_files(paths[:4], **kw)                         # warm: workspace, pinned buffers, filterbanks
+            seg.segment_batch((load_wav(p) for p in paths[:4]), **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a = seg.segment_batch((load_wav(p) for p in paths), **kw)
+            torch.cuda.synchronize()
+            t_host = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            b = seg.segment_files(paths, **kw)
+            torch.cuda.synchronize()
+            t_dev = time.perf_counter() - t0
+            emit("%-18s folder wall time     segment_batch(load_wav) %.2f s | segment_files %.2f s  (x%.2f; results equal: %s; %.0f audio-s)"
+                 % (name, t_host, t_dev, t_host / t_dev, a == b, args.files * args.seconds))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,188 @@
+// WAVE sample decode (audio ingest): interleaved little-endian PCM frames exactly as they sit in a RIFF data
+// chunk -> float32 mono.  Replaces the decoding half of `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61;
+// evaluate.py:58), i.e. what whisperseg_amd/wavio.py::load_wav does with numpy on the host, and produces the same float32 bits:
+//   u8 (x - 128) / 128 | s16 x / 2^15 | s24 sign-extended / 2^23 | s32 one int -> float32 rounding, then the exact scale 2^-31
+//   f32 copied | f64 one round-to-nearest-even conversion (beyond the float32 range: +-inf)
+//   channels > 1: numpy's mean(axis=1) of the float32 samples of a frame — the sum starts from +0 (so a frame of -0.0 samples
+//   gives +0.0), runs left to right for fewer than 8 channels and in numpy's pairwise order from 8 channels on (eight strided
+//   partial sums, combined as a tree, the last channels % 8 samples added one by one), then ONE division by float(channels).
+// A pure stream (HBM-bound: 1..8 bytes in per sample, 4 bytes out per frame).  The unit of work is a GROUP of four output frames:
+// one lane, one 16-byte store.  A group's bytes start on a dword for every frame size, so a lane reads the aligned dwords that
+// cover its group (16-byte loads where the group is a multiple of 16 bytes) and takes samples apart in registers; the last
+// n_frames % 4 frames are read byte by byte by one lane.  No LDS, no scratch; all indexing is 64-bit.
+#include "wseg_common.h"
+
+namespace wseg {
+
+constexpr int kBytes[6] = {1, 2, 3, 4, 4, 8};      // bytes per sample of wseg_pcm_format
+
+// Sample at byte `b` (a multiple of the sample size for u8 / s16, of 4 for s32 / f32 / f64, any for s24) of the dword array `w`.
+// With a register array and a compile-time `b` this is shifts only.
+template <int FMT, class W>
+__device__ __forceinline__ float sample_at(const W& w, long long b) {
+  const long long d = b >> 2;
+  const int sh = (int)(b & 3) * 8;
+  if constexpr (FMT == WSEG_PCM_U8) {
+    return ((float)((w[d] >> sh) & 0xffu) - 128.0f) / 128.0f;
+  } else if constexpr (FMT == WSEG_PCM_S16) {
+    return (float)(int16_t)(w[d] >> sh) / 32768.0f;
+  } else if constexpr (FMT == WSEG_PCM_S24) {
+    uint32_t v = w[d] >> sh;
+    if (sh > 8) v |= w[d + 1] << (32 - sh);        // the sample ends in the next dword (which exists: it holds the sample's last byte)
+    return (float)((int32_t)(v << 8) >> 8) / 8388608.0f;
+  } else if constexpr (FMT == WSEG_PCM_S32) {
+    return (float)(int32_t)w[d] * 4.656612873077393e-10f;      // 2^-31: exact, no result is subnormal
+  } else if constexpr (FMT == WSEG_PCM_F32) {
+    return __uint_as_float(w[d]);
+  } else {
+    return (float)__longlong_as_double((long long)(((unsigned long long)w[d + 1] << 32) | w[d]));
+  }
+}
+
+// The tail's view of raw: dword d assembled from byte loads, never touching a byte the sample does not own.
+template <int FMT>
+__device__ __forceinline__ float sample_bytes(const uint8_t* __restrict__ raw, long long b) {
+  constexpr int B = kBytes[FMT];
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int i = 0; i < B; ++i) {
+    const uint32_t v = raw[b + i];
+    if (i < 4) lo |= v << (8 * i); else hi |= v << (8 * (i - 4));
+  }
+  const uint32_t w[2] = {lo, hi};
+  return sample_at<FMT>(w, 0);
+}
+
+// numpy's add.reduce over the channels of one frame, then the mean.  get(c): float32 sample of channel c.
+template <int CH, class Get>
+__device__ __forceinline__ float frame_mean(int ch, Get get) {
+  if constexpr (CH == 1) {
+    return get(0);
+  } else if constexpr (CH == 2) {
+    return (0.0f + (get(0) + get(1))) / 2.0f;
+  } else {
+    float s;
+    if (ch < 8) {
+      s = get(0);
+      for (int c = 1; c < ch; ++c) s += get(c);
+    } else {
+      float r[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = get(j);
+      int c = 8;
+      for (; c < ch - (ch & 7); c += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] += get(c + j);
+      }
+      s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+      for (; c < ch; ++c) s += get(c);
+    }
+    return (0.0f + s) / (float)ch;
+  }
+}
+
+template <int N>
+struct Dwords {
+  uint32_t v[N];
+  __device__ __forceinline__ uint32_t operator[](long long i) const { return v[i]; }
+};
+
+// The N dwords of a group at p (a multiple of 4 N bytes behind a 16-byte aligned base): the widest loads that alignment allows.
+template <int N>
+__device__ __forceinline__ Dwords<N> load_group(const uint32_t* __restrict__ p) {
+  Dwords<N> r;
+  if constexpr (N % 4 == 0) {
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i) {
+      const uint4 q = reinterpret_cast<const uint4*>(p)[i];
+      r.v[4 * i] = q.x; r.v[4 * i + 1] = q.y; r.v[4 * i + 2] = q.z; r.v[4 * i + 3] = q.w;
+    }
+  } else if constexpr (N % 2 == 0) {
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+      const uint2 q = reinterpret_cast<const uint2*>(p)[i];
+      r.v[2 * i] = q.x; r.v[2 * i + 1] = q.y;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.v[i] = p[i];
+  }
+  return r;
+}
+
+// CH = 1 / 2: unrolled bodies over a register copy of the group; CH = 0: any channel count, dwords fetched sample by sample.
+template <int FMT, int CH>
+__global__ __launch_bounds__(256) void pcm_to_mono_kernel(const void* __restrict__ raw_, long long n_frames, int ch,
+                                                          float* __restrict__ out, int out_aligned) {
+  constexpr int B = kBytes[FMT];
+  const uint32_t* __restrict__ raw = static_cast<const uint32_t*>(raw_);
+  const long long n_groups = n_frames >> 2;
+  const long long frame_bytes = (long long)(CH ? CH : ch) * B;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += stride) {
+    float y[4];
+    if constexpr (CH != 0) {
+      constexpr int N = CH * B;                    // dwords of a group = bytes of a frame
+      const Dwords<N> w = load_group<N>(raw + g * N);
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+        y[f] = frame_mean<CH>(CH, [&](int c) { return sample_at<FMT>(w, (long long)((f * CH + c) * B)); });
+    } else {
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const long long b0 = (4 * g + f) * frame_bytes;
+        y[f] = frame_mean<0>(ch, [&](int c) { return sample_at<FMT>(raw, b0 + (long long)c * B); });
+      }
+    }
+    if (out_aligned) {
+      *reinterpret_cast<float4*>(out + 4 * g) = make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+#pragma unroll
+      for (int f = 0; f < 4; ++f) out[4 * g + f] = y[f];
+    }
+  }
+  // the last n_frames % 4 frames: one lane, byte loads
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint8_t* __restrict__ bytes = static_cast<const uint8_t*>(raw_);
+    for (long long fr = n_groups << 2; fr < n_frames; ++fr) {
+      const long long b0 = fr * frame_bytes;
+      out[fr] = frame_mean<CH>(CH ? CH : ch, [&](int c) { return sample_bytes<FMT>(bytes, b0 + (long long)c * B); });
+    }
+  }
+}
+
+template <int FMT>
+static void launch_pcm(int ch, dim3 grid, hipStream_t s, const void* raw, long long n_frames, float* out, int out_aligned) {
+  if (ch == 1) hipLaunchKernelGGL((pcm_to_mono_kernel<FMT, 1>), grid, dim3(256), 0, s, raw, n_frames, ch, out, out_aligned);
+  else if (ch == 2) hipLaunchKernelGGL((pcm_to_mono_kernel<FMT, 2>), grid, dim3(256), 0, s, raw, n_frames, ch, out, out_aligned);
+  else hipLaunchKernelGGL((pcm_to_mono_kernel<FMT, 0>), grid, dim3(256), 0, s, raw, n_frames, ch, out, out_aligned);
+}
+
+}  // namespace wseg
+
+using namespace wseg;
+
+extern "C" int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (!raw || ((uintptr_t)raw & 15)) { set_error("wseg_pcm_to_mono_f32: raw must be a 16-byte aligned device pointer"); return WSEG_ERR_INVALID; }
+  if (!out || ((uintptr_t)out & 3)) { set_error("wseg_pcm_to_mono_f32: out must be a float32 device pointer"); return WSEG_ERR_INVALID; }
+  if (channels < 1 || channels > 64) { set_error("wseg_pcm_to_mono_f32: channels must be 1..64 (got %d)", channels); return WSEG_ERR_INVALID; }
+  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_mono_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  if (n_frames < 0) { set_error("wseg_pcm_to_mono_f32: n_frames is negative"); return WSEG_ERR_INVALID; }
+  if (n_frames == 0) return WSEG_OK;
+  long long blocks = ((n_frames >> 2) + 255) / 256;
+  if (blocks < 1) blocks = 1;                      // fewer than four frames: the tail lane alone
+  if (blocks > 8192) blocks = 8192;                // 32 workgroups per CU; longer streams take the grid stride
+  const dim3 grid((unsigned)blocks);
+  const int out_aligned = ((uintptr_t)out & 15) == 0;
+  switch (format) {
+    case WSEG_PCM_U8: launch_pcm<WSEG_PCM_U8>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+    case WSEG_PCM_S16: launch_pcm<WSEG_PCM_S16>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+    case WSEG_PCM_S24: launch_pcm<WSEG_PCM_S24>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+    case WSEG_PCM_S32: launch_pcm<WSEG_PCM_S32>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+    case WSEG_PCM_F32: launch_pcm<WSEG_PCM_F32>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+    default: launch_pcm<WSEG_PCM_F64>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+  }
+  WSEG_LAUNCH_CHECK();
+  return WSEG_OK;
+}

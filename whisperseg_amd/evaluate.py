@@ -5,7 +5,7 @@ import csv
 import json
 import os
 
-from .wavio import load_wav
+from .wavio import load_wav_device
 
 
 def read_label(label_path, default_config={}, ignore_cluster=False):
@@ -79,7 +79,9 @@ def evaluate(audio_list, label_list, segmenter, batch_size, max_length, num_tria
     if distributed is None:
         distributed = os.environ.get("WSEG_EVAL_DISTRIBUTED") == "1"
     if distributed and ours and not wdist._single() and hasattr(segmenter, "decode_shard_tokens"):
-        predictions = wdist.segment_batch_distributed(segmenter, audio_list, srs, **kw)
+        # the hand-over between ranks starts from host arrays (rank 0's; the other ranks may pass None)
+        host = audio_list and [a.cpu().numpy() if hasattr(a, "cpu") else a for a in audio_list]
+        predictions = wdist.segment_batch_distributed(segmenter, host, srs, **kw)
     elif ours and hasattr(segmenter, "segment_batch"):
         predictions = segmenter.segment_batch(audio_list, srs, **kw)
     else:
@@ -103,7 +105,7 @@ def evaluate_dataset(dataset_folder, model_path, num_trials, max_length=448, num
     audio_paths, label_paths = get_audio_and_label_paths(dataset_folder)
     for audio_path, label_path in zip(audio_paths, label_paths):
         label = read_label(label_path)
-        audio, sr = load_wav(audio_path)
+        audio, sr = load_wav_device(audio_path)      # load_wav's samples, decoded on the GPU
         want = label.get("sr", None)
         if want is not None and int(want) != sr:      # librosa.load(path, sr=label sr) upstream: resample on the GPU
             from .resample import resample

@@ -16,7 +16,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, postprocess, scoring
+from . import _lib, postprocess, scoring, wavio
 from .audio_utils import get_feature_extractor, get_n_fft_given_sr
 from .checkpoint import checkpoint_files
 from .engine import DEFAULT_BEGIN_SUPPRESS_TOKENS, DEFAULT_SUPPRESS_TOKENS, Engine
@@ -94,6 +94,9 @@ class SegmenterBase:
         # fits 80 % of the free device memory).  The reference bounds memory with `batch_size`; here `batch_size` no longer
         # caps the concurrency, this attribute does.
         self.max_slots = None
+        # segment_files: bytes of each of the two pinned buffers the reader thread fills (a longer file goes through in pieces)
+        self.ingest_buffer_bytes = wavio.STAGING_BYTES
+        self._ingest = None
 
     # ---- slicing + features (reference model.py:127-166), batched on the first device ------------
     def get_sliced_audios_features(self, audio, sr, min_frequency, spec_time_step, num_trials):
@@ -335,6 +338,28 @@ class SegmenterBase:
         if group:
             flush()
         return out
+
+    # ---- a folder of wav files: reads overlapped with the device work ----------------------------------
+    def ingest_backend(self):
+        """The device half of segment_files (wavio.DeviceIngest on the first device, kept: its pinned buffers are re-used)."""
+        if self._ingest is None:
+            self._ingest = wavio.DeviceIngest(self.device_list[0])
+        return self._ingest
+
+    def segment_files(self, paths, **segment_batch_kwargs):
+        """segment_batch((load_wav(p) for p in paths), ...) element for element, without the host decode and without the
+        serial file reads: one reader thread fills a pool of two pinned buffers (self.ingest_buffer_bytes each at most; larger
+        files go through in pieces) while this thread copies filled buffers to the device, decodes the samples there
+        (wseg_pcm_to_mono_f32: load_wav's float32 bits) and runs the front-end and the pooled decode of segment_batch on the
+        resident PCM.  Errors of the reader are raised here with the file's name; the thread is joined on every way out."""
+        paths = list(paths)
+        if not paths:
+            return []
+        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes)
+        try:
+            return self.segment_batch(iter(pipeline), **segment_batch_kwargs)
+        finally:
+            pipeline.close()
 
     # ---- scoring helpers (reference model.py:474-569) --------------------------------------------
     def segment_score(self, prediction, label, target_cluster=None, tolerance=None):

@@ -1,8 +1,12 @@
 """Minimal RIFF/WAVE reader standing in for `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61;
 librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono.
 PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled; no resampling here."""
+import collections
 import io
+import os
+import queue
 import struct
+import threading
 
 import numpy as np
 
@@ -64,3 +68,321 @@ def load_wav(path_or_file):
     if ch > 1:
         x = x[: len(x) // ch * ch].reshape(-1, ch).mean(axis=1).astype(np.float32)
     return np.ascontiguousarray(x, dtype=np.float32), int(sr)
+
+
+# ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
+# load_wav above is the arithmetic's definition; what follows moves it to the device: read_wav_raw hands out the data chunk's
+# bytes untouched, libwseg's wseg_pcm_to_mono_f32 widens and averages them with load_wav's float32 bits.
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)        # wseg_pcm_format (include/wseg.h)
+BYTES_PER_SAMPLE = (1, 2, 3, 4, 4, 8)
+MAX_CHANNELS = 64
+STAGING_BYTES = 256 << 20        # one pinned staging buffer; a longer data chunk goes through in pieces
+
+WavRaw = collections.namedtuple("WavRaw", "data format channels sr n_frames")
+WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames frame_bytes offset")
+
+
+def _pcm_format(tag, bits):
+    """load_wav's dispatch on (format tag, width), with its errors."""
+    if tag == 1:
+        if bits not in (8, 16, 24, 32):
+            raise ValueError(f"unsupported PCM width {bits}")
+        return {8: PCM_U8, 16: PCM_S16, 24: PCM_S24, 32: PCM_S32}[bits]
+    if tag == 3:
+        return PCM_F32 if bits == 32 else PCM_F64
+    raise ValueError(f"unsupported WAVE format tag {tag}")
+
+
+def scan_wav(f):
+    """load_wav's chunk walk over a seekable file without reading the samples -> WavInfo (offset: where the data chunk's bytes
+    start).  As in load_wav the last `fmt ` / `data` chunk counts, a chunk cut short by the end of the file is taken as far as it
+    goes, and the samples are cut to whole frames."""
+    header = f.read(12)
+    if len(header) < 12 or header[:4] not in (b"RIFF", b"RF64") or header[8:12] != b"WAVE":
+        raise ValueError("not a RIFF/WAVE file")
+    end = f.seek(0, 2)
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= end:
+        f.seek(pos)
+        head = f.read(8)
+        cid, size = head[:4], struct.unpack("<I", head[4:])[0]
+        pos += 8
+        if cid == b"fmt ":
+            body = f.read(size)
+            tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+            if tag == 0xFFFE and len(body) >= 26:
+                tag = struct.unpack("<H", body[24:26])[0]
+            fmt = (tag, ch, sr, bits)
+        elif cid == b"data":
+            data = (pos, min(size, end - pos))
+        pos += size + size % 2
+    if fmt is None or data is None:
+        raise ValueError("missing fmt or data chunk")
+    tag, ch, sr, bits = fmt
+    code = _pcm_format(tag, bits)
+    ch = max(int(ch), 1)
+    frame_bytes = ch * BYTES_PER_SAMPLE[code]
+    return WavInfo(code, ch, int(sr), data[1] // frame_bytes, frame_bytes, data[0])
+
+
+def _opened(path_or_file):
+    """-> (seekable binary file, whether it is ours to close)."""
+    if isinstance(path_or_file, (str, bytes, os.PathLike)):
+        return open(path_or_file, "rb"), True
+    return (path_or_file if hasattr(path_or_file, "read") else io.BytesIO(path_or_file)), False
+
+
+def _read_exact(f, view):
+    got = 0
+    while got < len(view):
+        n = f.readinto(view[got:])
+        if not n:
+            raise ValueError("the file ended inside its data chunk")
+        got += n
+
+
+def read_wav_raw(path_or_file, into=None):
+    """-> WavRaw(data, format, channels, sr, n_frames): the sample bytes of whole frames exactly as they sit in the data chunk
+    (a uint8 memoryview of n_frames * channels * bytes-per-sample bytes), `format` a wseg_pcm_format code.  With `into` — a
+    caller's writable buffer, e.g. pinned memory — the bytes are read straight into it and `data` is a view of its front."""
+    f, ours = _opened(path_or_file)
+    try:
+        info = scan_wav(f)
+        nbytes = info.n_frames * info.frame_bytes
+        if into is None:
+            into = bytearray(nbytes)
+        view = memoryview(into).cast("B")
+        if len(view) < nbytes:
+            raise ValueError(f"the data chunk holds {nbytes} bytes, the buffer {len(view)}")
+        view = view[:nbytes]
+        f.seek(info.offset)
+        _read_exact(f, view)
+    finally:
+        if ours:
+            f.close()
+    return WavRaw(view, info.format, info.channels, info.sr, info.n_frames)
+
+
+class DeviceIngest:
+    """The device half of the ingest: pinned staging buffers, and `submit` = copy a filled buffer to the device and decode it
+    there (wseg_pcm_to_mono_f32), stream-ordered on the current stream.  Every call belongs to the thread that owns the
+    device; a reader thread only ever writes into the arrays `acquire` handed out."""
+
+    def __init__(self, device="cuda"):
+        import torch
+        from . import _lib
+        self.torch, self._lib = torch, _lib
+        self.lib = _lib.load(require_device=True)
+        self.device = torch.device(device)
+        self.buffers, self._pinned = [], {}
+
+    def acquire(self, count, nbytes):
+        """`count` pinned buffers of at least `nbytes` bytes (kept and re-used from call to call) -> writable uint8 arrays."""
+        nbytes = -(-max(int(nbytes), 1) // 4096) * 4096
+        if len(self.buffers) < count or self.buffers[0].numel() < nbytes:
+            self.buffers = []        # let go of the old ones first
+            self.buffers = [self.torch.empty(nbytes, dtype=self.torch.uint8, pin_memory=True) for _ in range(count)]
+        views = [b.numpy()[:nbytes] for b in self.buffers[:count]]      # (a kept buffer may be longer than asked for)
+        self._pinned = {v.ctypes.data: b for v, b in zip(views, self.buffers)}
+        return views
+
+    def new_output(self, n_frames):
+        return self.torch.empty(int(n_frames), dtype=self.torch.float32, device=self.device)
+
+    def submit(self, view, nbytes, info, out, frame0, n_frames):
+        """Decode `n_frames` frames whose `nbytes` bytes sit at the front of buffer `view` into out[frame0 : frame0 + n_frames]
+        -> an event that has completed once the copy out of the buffer has, i.e. once the buffer may be written again."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            event = torch.cuda.Event()
+            if n_frames:
+                # the kernel may read up to the next multiple of 16 bytes: the device copy is that long (and 16-byte aligned: torch
+                # aligns its allocations to 512 bytes)
+                raw = torch.empty(-(-nbytes // 16) * 16, dtype=torch.uint8, device=self.device)
+                raw[:nbytes].copy_(self._pinned[view.ctypes.data][:nbytes], non_blocking=True)
+                event.record()
+                dst = out[frame0:frame0 + n_frames]
+                self._lib.check(self.lib.wseg_pcm_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format),
+                                                              dst.data_ptr(), self._lib.stream_ptr()))
+            else:
+                event.record()
+        return event
+
+    @staticmethod
+    def done(event, wait):
+        if wait:
+            event.synchronize()
+        return event.query()
+
+
+def chunk_plan(info, buffer_bytes, chunk_frames=None):
+    """Frames per piece of a data chunk that goes through buffers of `buffer_bytes`: a multiple of 16 frames, so that every
+    piece starts on a multiple of 16 bytes (and of 16 output floats) whatever the frame size."""
+    fit = buffer_bytes // info.frame_bytes // 16 * 16
+    if fit < 16:
+        raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 frames of {info.frame_bytes} bytes")
+    if chunk_frames is not None:
+        if chunk_frames <= 0 or chunk_frames % 16:
+            raise ValueError("chunk_frames must be a positive multiple of 16")
+        fit = min(fit, int(chunk_frames))
+    return fit
+
+
+def check_channels(info, name="wav"):
+    if info.channels > MAX_CHANNELS:
+        raise ValueError(f"{name}: {info.channels} channels (the device decode takes up to {MAX_CHANNELS})")
+
+
+_INGEST = {}
+
+
+def load_wav_device(path_or_file, device="cuda", chunk_frames=None):
+    """load_wav on the GPU -> (float32 device tensor [n_frames], sampling_rate), the same samples bit for bit: sample bytes ->
+    pinned staging -> non_blocking copy -> wseg_pcm_to_mono_f32 on the current stream.  A data chunk larger than the staging
+    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces."""
+    import torch
+    key = str(torch.device(device))
+    if key not in _INGEST:
+        _INGEST[key] = DeviceIngest(device)
+    ingest = _INGEST[key]
+    f, ours = _opened(path_or_file)
+    try:
+        info = scan_wav(f)
+        check_channels(info)
+        total = info.n_frames * info.frame_bytes
+        views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * info.frame_bytes)))
+        step = chunk_plan(info, len(views[0]), chunk_frames)
+        out = ingest.new_output(info.n_frames)
+        events = [None, None]        # the next piece is read while the copy of the one before is in flight
+        f.seek(info.offset)
+        for i, frame0 in enumerate(range(0, info.n_frames, step)):
+            n = min(step, info.n_frames - frame0)
+            if events[i % 2] is not None:
+                ingest.done(events[i % 2], wait=True)
+            _read_exact(f, views[i % 2][:n * info.frame_bytes])
+            events[i % 2] = ingest.submit(views[i % 2], n * info.frame_bytes, info, out, frame0, n)
+        for event in events:         # the buffers belong to the next call
+            if event is not None:
+                ingest.done(event, wait=True)
+    finally:
+        if ours:
+            f.close()
+    return out, info.sr
+
+
+def _named(exc, path):
+    """`exc` again with the file's name in front (same type where the type takes a plain message)."""
+    msg = f"{path}: {exc}"
+    if isinstance(exc, OSError):
+        return OSError(msg)
+    try:
+        return type(exc)(msg)
+    except Exception:
+        return RuntimeError(msg)
+
+
+class FilePipeline:
+    """Iterator over (float32 mono device tensor, sampling_rate) of `paths`, in order, with the file reads overlapped with
+    whatever the consumer does between two items: ONE reader thread opens, parses and `readinto`s the buffers of a small pool
+    (`n_buffers` x at most `buffer_bytes`; larger files go through in pieces), the consuming thread submits filled buffers to
+    `ingest` (DeviceIngest, or anything with its acquire / new_output / submit / done) and gives a buffer back to the reader once
+    the event of its submit has completed.  The reader makes no device call.  A reader error is raised by the consumer with the
+    file's name; close() — also called when the iteration ends, fails or is abandoned — stops and joins the thread."""
+
+    def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2):
+        self.paths, self.ingest = list(paths), ingest
+        sizes = [os.path.getsize(p) for p in self.paths if os.path.exists(p)]
+        self.views = ingest.acquire(n_buffers, min(int(buffer_bytes), max(sizes + [16 * MAX_CHANNELS * 8]))) if self.paths else []
+        self.free, self.filled = queue.Queue(), queue.Queue()
+        for v in self.views:
+            self.free.put(v)
+        self.pending = collections.deque()       # (view, event) of submitted buffers, oldest first
+        self.stop = threading.Event()
+        self.thread = None
+        if self.paths:
+            self.thread = threading.Thread(target=self._read, name="wseg-wav-reader", daemon=True)
+            self.thread.start()
+
+    # ---- reader thread: host work only --------------------------------------------------------------------------------
+    def _take_free(self):
+        while not self.stop.is_set():
+            try:
+                return self.free.get(timeout=0.05)
+            except queue.Empty:
+                pass
+        return None
+
+    def _read(self):
+        for index, path in enumerate(self.paths):
+            try:
+                with open(path, "rb") as f:
+                    info = scan_wav(f)
+                    check_channels(info, os.path.basename(path))
+                    step = chunk_plan(info, len(self.views[0]))
+                    f.seek(info.offset)
+                    for frame0 in range(0, max(info.n_frames, 1), step):
+                        n = min(step, info.n_frames - frame0)
+                        view = self._take_free()
+                        if view is None:
+                            return
+                        try:
+                            _read_exact(f, view[:n * info.frame_bytes])
+                        except BaseException:
+                            self.free.put(view)
+                            raise
+                        self.filled.put((index, info, view, frame0, n))
+            except BaseException as exc:
+                self.filled.put((index, exc, None, 0, 0))
+                return
+        self.filled.put(None)
+
+    # ---- consumer ---------------------------------------------------------------------------------------------------------
+    def _reap(self, wait):
+        """Give the reader back every submitted buffer whose copy has completed (wait: block for the oldest)."""
+        while self.pending and self.ingest.done(self.pending[0][1], wait):
+            self.free.put(self.pending.popleft()[0])
+            wait = False
+
+    def _next_item(self):
+        while True:
+            self._reap(False)
+            try:
+                return self.filled.get_nowait()
+            except queue.Empty:
+                pass
+            if self.pending:
+                self._reap(True)
+            else:
+                try:
+                    return self.filled.get(timeout=0.05)
+                except queue.Empty:
+                    if not self.thread.is_alive() and self.filled.empty():
+                        raise RuntimeError("the wav reader thread ended without a result")
+
+    def __iter__(self):
+        try:
+            out = None
+            while self.thread is not None:
+                item = self._next_item()
+                if item is None:
+                    break
+                index, info, view, frame0, n = item
+                if isinstance(info, BaseException):
+                    raise _named(info, self.paths[index]) from info
+                if frame0 == 0:
+                    out = self.ingest.new_output(info.n_frames)
+                self.pending.append((view, self.ingest.submit(view, n * info.frame_bytes, info, out, frame0, n)))
+                if frame0 + n >= info.n_frames:
+                    yield out, info.sr
+                    out = None
+        finally:
+            self.close()
+
+    def close(self):
+        self.stop.set()
+        if self.thread is not None:
+            self.thread.join()
+            self.thread = None
+        self._reap(bool(self.pending))
+        while self.pending:
+            self._reap(True)
