@@ -123,6 +123,17 @@ typedef enum { WSEG_PCM_U8 = 0, WSEG_PCM_S16 = 1, WSEG_PCM_S24 = 2, WSEG_PCM_S32
  * the next multiple of 16 bytes behind n_frames * channels * bytes_per_sample.  out: device float32 [n_frames], mono (any
  * float alignment; 16-byte aligned for 16-byte stores).  channels 1..64.  n_frames == 0 launches nothing.  Stream-ordered. */
 int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream);
+/* The channels of a multi-channel recording kept apart (the reference's `librosa.load(..., mono=False)` and `audio[channel_id]`:
+ * segment_service.py:73-80, scripts/backend.py:279-282, demo.py:76-78), what wavio.load_wav(mono=False) gives on the host.
+ * out[(c - first_channel) * plane_stride + f] = float32 sample of channel c in frame f, for
+ * first_channel <= c < first_channel + n_out_channels and 0 <= f < n_frames; same per-sample conversions as
+ * wseg_pcm_to_mono_f32, no averaging.  raw: as for wseg_pcm_to_mono_f32 (16-byte aligned, readable to the next
+ * multiple of 16 bytes).  out: any float alignment; plane_stride in floats, >= n_frames (ignored when
+ * n_out_channels == 1).  Writes nothing outside the n_out_channels * n_frames addressed floats.
+ * channels 1..64.  n_frames == 0 launches nothing.  Stream-ordered.  Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format,
+                           int32_t first_channel, int32_t n_out_channels,
+                           float* out, int64_t plane_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.

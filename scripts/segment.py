@@ -4,6 +4,11 @@
     python scripts/segment.py --model_path DIR --audio_path a.wav --csv_save_path out.csv
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --csv_save_path out.csv
     cat a.wav | python scripts/segment.py --model_path DIR --audio_path - --csv_save_path buffer
+    python scripts/segment.py --model_path DIR --audio_folder wavs/ --channel_id all --csv_save_path out.csv
+
+--channel_id (the `channel_id` of the reference's interactive entry points: segment_service.py:73-80, scripts/backend.py:279-282,
+demo.py:76-78) segments one channel of multi-channel recordings instead of their mono mix — an integer: the same columns, rows
+of that channel (a one-channel file gives its samples) — or `all`: every channel, with a `channel` column behind `filename`.
 """
 import argparse
 import csv
@@ -18,6 +23,10 @@ from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-le
 from whisperseg_amd.wavio import load_wav, load_wav_device  # noqa: E402
 
 
+def channel_id_arg(text):
+    return "all" if text == "all" else int(text)
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--model_path")
@@ -30,6 +39,9 @@ def build_parser():
     p.add_argument("--min_frequency", default=None, type=int)
     p.add_argument("--spec_time_step", default=None, type=float)
     p.add_argument("--num_trials", default=1, type=int)
+    p.add_argument("--channel_id", default=None, type=channel_id_arg,
+                   help="segment this channel of multi-channel recordings (an integer, negative from the end), or 'all' of them; "
+                        "absent: the mono mix")
     return p
 
 
@@ -39,6 +51,19 @@ def write_csv(columns, rows, dest):
     w.writerow(columns)
     for row in rows:
         w.writerow([repr(v) if isinstance(v, float) else v for v in row])
+
+
+def table(results, names=None, all_channels=False):
+    """-> (columns, rows) of the CSV.  `results`: one prediction dict per recording, or with all_channels one LIST of dicts (one
+    per channel) per recording, which adds the `channel` column; `names`: the recordings' file names for the `filename` column
+    (folder mode).  Rows run in file, channel, row order."""
+    columns = (["filename"] if names is not None else []) + (["channel"] if all_channels else []) + ["onset", "offset", "cluster"]
+    rows = []
+    for i, res in enumerate(results):
+        for channel, r in enumerate(res if all_channels else [res]):
+            head = ((names[i],) if names is not None else ()) + ((channel,) if all_channels else ())
+            rows += [head + (on, off, c) for on, off, c in zip(r["onset"], r["offset"], r["cluster"])]
+    return columns, rows
 
 
 def main(argv=None):
@@ -53,20 +78,29 @@ def main(argv=None):
                   batch_size=args.batch_size)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
-        columns, rows = ["filename", "onset", "offset", "cluster"], []
         paths = glob.glob(args.audio_folder + "/*.wav") + glob.glob(args.audio_folder + "/*.WAV")
         # same rows as the reference's serial loop, but the windows of many files share the engine's decode slots; files
         # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
         # a large folder needs no more memory than a small one
-        results = segmenter.segment_files(paths, **kwargs)
-        for path, res in zip(paths, results):
-            name = os.path.basename(path)
-            rows += [(name, on, off, c) for on, off, c in zip(res["onset"], res["offset"], res["cluster"])]
-    else:
+        results = segmenter.segment_files(paths, **kwargs) if args.channel_id is None \
+            else segmenter.segment_files(paths, channel_id=args.channel_id, **kwargs)
+        columns, rows = table(results, [os.path.basename(p) for p in paths], args.channel_id == "all")
+    elif args.channel_id is None:
         audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read())) if args.audio_path == "-" else load_wav_device(args.audio_path)
-        res = segmenter.segment(audio, sr, **kwargs)
-        columns = ["onset", "offset", "cluster"]
-        rows = list(zip(res["onset"], res["offset"], res["cluster"]))
+        columns, rows = table([segmenter.segment(audio, sr, **kwargs)])
+    else:
+        if args.audio_path == "-":       # the channels kept apart on the host, and the reference's selection (`audio[channel_id]` of a 2-D array)
+            audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read()), mono=False)
+            if audio.ndim == 2 and args.channel_id != "all":
+                audio = audio[args.channel_id]
+        elif args.channel_id == "all":
+            audio, sr = load_wav_device(args.audio_path, mono=False)
+        else:
+            audio, sr = load_wav_device(args.audio_path, channel_id=args.channel_id)
+        if args.channel_id == "all":
+            columns, rows = table([segmenter.segment_channels(audio, sr, **kwargs)], all_channels=True)
+        else:
+            columns, rows = table([segmenter.segment(audio, sr, **kwargs)])
     if args.csv_save_path == "buffer":
         buf = io.StringIO()
         write_csv(columns, rows, buf)

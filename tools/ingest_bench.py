@@ -3,6 +3,7 @@
 (wseg_pcm_to_mono_f32) and the folder pipeline on top of it (SegmenterBase.segment_files).
 
     python tools/ingest_bench.py [--files 64] [--seconds 60] [--out profiles/ingest_ab.txt]
+    python tools/ingest_bench.py --planar [--out profiles/ingest_planar_ab.txt]
 
 For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
 `--seconds` seconds into a temporary directory and reports
@@ -12,7 +13,13 @@ For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 s
   * wall time of the folder through segment_batch((load_wav(p) for p in paths)) and through segment_files(paths): the same
     engine, the same results (checked), one process.
 The engine is bench.py's: whisperseg-large geometry with seeded random weights in the default mode, spec_time_step 0.01 (10 s
-windows), decode length capped at --max-length (random weights emit no meaningful EOS, so every window runs that long)."""
+windows), decode length capped at --max-length (random weights emit no meaningful EOS, so every window runs that long).
+
+--planar measures the two decode kernels alone, no engine: wseg_pcm_to_planar_f32 with all channels beside wseg_pcm_to_mono_f32 on
+the same bytes (random, generated on the device), for PLANAR_CASES x 60 s and 600 s of audio.  GB/s = (input bytes + output
+bytes) over HIP-event time — the planar kernel writes `channels` times the mono kernel's output, so rates compare, times do not.
+A repetition is a train of back-to-back launches (as many as move about 2 GB, at least one) between two events; one warm-up
+train, then three repetitions of each kernel, alternating; all three rates are printed, the median is the figure."""
 import argparse
 import os
 import statistics
@@ -27,6 +34,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 CASES = (("s16", 1, 16000), ("s16", 2, 48000), ("s24", 2, 96000))
+PLANAR_CASES = CASES + (("s16", 8, 48000), ("s24", 5, 96000))
 
 
 def write_folder(d, fmt, channels, sr, files, seconds):
@@ -70,6 +78,58 @@ def kernel_gbps(lib, raw_bytes, n_frames, channels, fmt_code):
     return (len(raw_bytes) + 4 * n_frames) / (med * 1e-3) / 1e9, med
 
 
+def planar_section(lib, emit):
+    import torch
+    import wav_cases as WC
+    from whisperseg_amd import _lib
+    stream = lambda: _lib.stream_ptr()
+    ratios = {}
+    for fmt, channels, sr in PLANAR_CASES:
+        code = WC.FORMATS.index(fmt)
+        for seconds in (60, 600):
+            n = seconds * sr
+            nbytes = n * channels * WC.BYTES[code]
+            raw = torch.randint(0, 256, (-(-nbytes // 16) * 16,), dtype=torch.uint8, device="cuda")
+            planes = torch.empty((channels, n), dtype=torch.float32, device="cuda")
+            mono = torch.empty(n, dtype=torch.float32, device="cuda")
+            kernels = {
+                "planar": (nbytes + 4 * n * channels, lambda: _lib.check(lib.wseg_pcm_to_planar_f32(
+                    raw.data_ptr(), n, channels, code, 0, channels, planes.data_ptr(), n, stream()))),
+                "mono": (nbytes + 4 * n, lambda: _lib.check(lib.wseg_pcm_to_mono_f32(raw.data_ptr(), n, channels, code, mono.data_ptr(), stream()))),
+            }
+
+            launches = {k: max(1, int(2e9 // moved)) for k, (moved, _) in kernels.items()}
+
+            def train(name):
+                moved, call = kernels[name]
+                iters = launches[name]
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    call()
+                b.record()
+                b.synchronize()
+                return moved * iters / (a.elapsed_time(b) * 1e-3) / 1e9
+
+            rates = {"planar": [], "mono": []}
+            for name in kernels:
+                train(name)
+            for _ in range(3):
+                for name in kernels:
+                    rates[name].append(train(name))
+            med = {k: statistics.median(v) for k, v in rates.items()}
+            ratios[(fmt, channels, seconds)] = med["planar"] / med["mono"]
+            for name in ("planar", "mono"):
+                emit("%-3s x%d %6d Hz %4d s  %-6s %8.1f GB/s  (%s; %d launches per repetition, %.1f MB in + %.1f MB out per launch)"
+                     % (fmt, channels, sr, seconds, name, med[name], " ".join("%.1f" % r for r in rates[name]), launches[name],
+                        nbytes / 1e6, (kernels[name][0] - nbytes) / 1e6))
+            spread = max(max(v) - min(v) for v in rates.values())
+            emit("%-3s x%d %6d Hz %4d s  planar / mono GB/s = %.2f  (largest spread of three repetitions: %.1f GB/s)"
+                 % (fmt, channels, sr, seconds, ratios[(fmt, channels, seconds)], spread))
+            del raw, planes, mono
+    return ratios
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -78,10 +138,27 @@ def main(argv=None):
     ap.add_argument("--model", default="large")
     ap.add_argument("--dtype", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--planar", action="store_true", help="only the kernels: wseg_pcm_to_planar_f32 beside wseg_pcm_to_mono_f32")
     args = ap.parse_args(argv)
     import torch
-    import bench
     from whisperseg_amd import _lib
+    if args.planar:
+        lib = _lib.load(require_device=True)
+        lines = ["planar decode A/B: wseg_pcm_to_planar_f32 (all channels) beside wseg_pcm_to_mono_f32 on the same bytes, HIP events, "
+                 "GB/s = (bytes in + bytes out) / time, median of three repetitions after one warm-up (all three in brackets), %s"
+                 % torch.cuda.get_device_name(0)]
+
+        def emit(s):
+            print(s, flush=True)
+            lines.append(s)
+
+        planar_section(lib, emit)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    import bench
     from whisperseg_amd.engine import Engine
     from whisperseg_amd.model import DEFAULT_DTYPE
     from whisperseg_amd.wavio import load_wav, read_wav_raw

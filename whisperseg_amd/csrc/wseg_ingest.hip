@@ -10,6 +10,7 @@
 // one lane, one 16-byte store.  A group's bytes start on a dword for every frame size, so a lane reads the aligned dwords that
 // cover its group (16-byte loads where the group is a multiple of 16 bytes) and takes samples apart in registers; the last
 // n_frames % 4 frames are read byte by byte by one lane.  No LDS, no scratch; all indexing is 64-bit.
+// wseg_pcm_to_planar_f32 (further down) keeps the channels apart instead of averaging them, through an LDS image of a tile of frames.
 #include "wseg_common.h"
 
 namespace wseg {
@@ -158,6 +159,83 @@ static void launch_pcm(int ch, dim3 grid, hipStream_t s, const void* raw, long l
   else hipLaunchKernelGGL((pcm_to_mono_kernel<FMT, 0>), grid, dim3(256), 0, s, raw, n_frames, ch, out, out_aligned);
 }
 
+// ---- the channels kept apart (wseg_pcm_to_planar_f32) -------------------------------------------------------------------------
+// The mono kernel's CH = 0 path lets every lane walk its own four frames through global memory (a lane stride of four frames:
+// coalesced only through the cache).  Here a workgroup takes a TILE of kPlanarTile consecutive frames and goes through it in
+// passes of as many frames (a multiple of 16: every pass starts on a 16-byte boundary whatever the frame size) as fit the LDS
+// image: the pass's contiguous bytes come in with coalesced 16-byte loads, each byte once, and the planes are taken out of the
+// image — an item is (plane, four consecutive frames), consecutive lanes on consecutive groups of one plane, one 16-byte store
+// each.  The groups of a plane are laid on ITS 16-byte grid (a plane whose address is m floats behind a 16-byte boundary takes
+// frames 4g - m .. 4g - m + 3 as group g), so every plane gets 16-byte stores; the groups cut by the pass's two ends store
+// their frames dword by dword.  The image carries one pad dword behind every 16: the lane stride of the de-interleaving reads is
+// one frame's bytes in dwords, and frame sizes that are a power of two (s16 x 8: 16 dwords) would put the 32 lanes of a
+// ds_read_b32 group on two banks; padded, 16 -> 17 is conflict-free and 4 / 8 / 32 are 2-way.  The price is that the image is
+// written dword by dword (its 16-byte pieces are no longer aligned).  Measured (profiles/ingest_planar_ab.txt): 5.3-6.4 TB/s padded
+// against 3.6-3.9 TB/s with an unpadded image written by 16-byte LDS stores, for every frame size tried, odd ones included.
+constexpr int kPlanarTile = 1024;                  // frames per tile (whisperseg_amd/wavio.py::PLANAR_TILE_FRAMES)
+constexpr int kPlanarImage = 16384;                // bytes of a pass: 1024 frames of up to 16 bytes, 32 frames of 512
+constexpr int kPlanarGridCap = 2048;               // 8 workgroups per CU; longer streams take the grid stride (wavio.PLANAR_GRID_CAP)
+
+struct PaddedImage {
+  const uint32_t* w;
+  __device__ __forceinline__ uint32_t operator[](long long d) const { const int i = (int)d; return w[i + (i >> 4)]; }
+};
+
+template <int FMT>
+__global__ __launch_bounds__(256) void pcm_to_planar_kernel(const void* __restrict__ raw_, long long n_frames, int ch, int first, int n_out,
+                                                            float* __restrict__ out, long long plane_stride) {
+  constexpr int B = kBytes[FMT];
+  __shared__ uint32_t image[kPlanarImage / 4 + kPlanarImage / 64];
+  const PaddedImage img{image};
+  const uint4* __restrict__ raw = static_cast<const uint4*>(raw_);
+  const int frame_bytes = ch * B;                                                  // <= 512
+  const int pass_max = min(kPlanarTile, kPlanarImage / frame_bytes / 16 * 16);     // >= 32
+  const int slots = pass_max / 4 + 1;                                              // groups of a plane in a pass, at most
+  const int n_items = n_out * slots;
+  const int tid = threadIdx.x;
+  const long long n_tiles = (n_frames + kPlanarTile - 1) / kPlanarTile;
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long long t0 = tile * kPlanarTile;
+    const int n_tile = (int)min((long long)kPlanarTile, n_frames - t0);
+    for (int p0 = 0; p0 < n_tile; p0 += pass_max) {
+      const int n = min(pass_max, n_tile - p0);
+      const long long chunk0 = ((t0 + p0) * frame_bytes) >> 4;                    // (a multiple of 16 frames: exact)
+      const int chunks = (n * frame_bytes + 15) >> 4;                              // <= 1024; the file's last one may be cut: raw is readable to there
+      uint4 q[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (tid + 256 * k < chunks) q[k] = raw[chunk0 + tid + 256 * k];
+      __syncthreads();                                                             // the pass before has been taken out
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = tid + 256 * k;
+        if (i < chunks) {
+          uint32_t* p = image + 4 * i + (i >> 2);
+          p[0] = q[k].x; p[1] = q[k].y; p[2] = q[k].z; p[3] = q[k].w;
+        }
+      }
+      __syncthreads();
+      for (int it = tid; it < n_items; it += 256) {
+        const int c = it / slots, g = it - c * slots;
+        float* __restrict__ plane = out + (long long)c * plane_stride + (t0 + p0);
+        const int f0 = 4 * g - (int)(((uintptr_t)plane >> 2) & 3);
+        if (f0 >= n) continue;
+        const int b0 = f0 * frame_bytes + (first + c) * B;
+        if (f0 >= 0 && f0 + 4 <= n) {
+          float y[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) y[k] = sample_at<FMT>(img, (long long)(b0 + k * frame_bytes));
+          *reinterpret_cast<float4*>(plane + f0) = make_float4(y[0], y[1], y[2], y[3]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (f0 + k >= 0 && f0 + k < n) plane[f0 + k] = sample_at<FMT>(img, (long long)(b0 + k * frame_bytes));
+        }
+      }
+    }
+  }
+}
+
 }  // namespace wseg
 
 using namespace wseg;
@@ -183,6 +261,45 @@ extern "C" int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t c
     case WSEG_PCM_F32: launch_pcm<WSEG_PCM_F32>(channels, grid, s, raw, n_frames, out, out_aligned); break;
     default: launch_pcm<WSEG_PCM_F64>(channels, grid, s, raw, n_frames, out, out_aligned); break;
   }
+  WSEG_LAUNCH_CHECK();
+  return WSEG_OK;
+}
+
+extern "C" int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, int32_t first_channel,
+                                      int32_t n_out_channels, float* out, int64_t plane_stride, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  if (!raw || ((uintptr_t)raw & 15)) { set_error("wseg_pcm_to_planar_f32: raw must be a 16-byte aligned device pointer"); return WSEG_ERR_INVALID; }
+  if (!out || ((uintptr_t)out & 3)) { set_error("wseg_pcm_to_planar_f32: out must be a float32 device pointer"); return WSEG_ERR_INVALID; }
+  if (channels < 1 || channels > 64) { set_error("wseg_pcm_to_planar_f32: channels must be 1..64 (got %d)", channels); return WSEG_ERR_INVALID; }
+  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_planar_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  if (n_frames < 0) { set_error("wseg_pcm_to_planar_f32: n_frames is negative"); return WSEG_ERR_INVALID; }
+  if (first_channel < 0 || first_channel >= channels) {
+    set_error("wseg_pcm_to_planar_f32: first_channel must be 0..%d (got %d)", channels - 1, first_channel); return WSEG_ERR_INVALID;
+  }
+  if (n_out_channels < 1 || n_out_channels > channels - first_channel) {
+    set_error("wseg_pcm_to_planar_f32: n_out_channels must be 1..%d behind channel %d (got %d)", channels - first_channel, first_channel, n_out_channels);
+    return WSEG_ERR_INVALID;
+  }
+  if (n_out_channels > 1 && plane_stride < n_frames) {
+    set_error("wseg_pcm_to_planar_f32: plane_stride (%lld) is shorter than the %lld frames of a plane", (long long)plane_stride, (long long)n_frames);
+    return WSEG_ERR_INVALID;
+  }
+  if (n_frames == 0) return WSEG_OK;
+  long long blocks = (n_frames + kPlanarTile - 1) / kPlanarTile;
+  if (blocks > kPlanarGridCap) blocks = kPlanarGridCap;
+  const dim3 grid((unsigned)blocks);
+  const long long stride = n_out_channels > 1 ? plane_stride : 0;
+#define WSEG_PLANAR(F) hipLaunchKernelGGL((pcm_to_planar_kernel<F>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels, \
+                                          (int)first_channel, (int)n_out_channels, out, stride)
+  switch (format) {
+    case WSEG_PCM_U8: WSEG_PLANAR(WSEG_PCM_U8); break;
+    case WSEG_PCM_S16: WSEG_PLANAR(WSEG_PCM_S16); break;
+    case WSEG_PCM_S24: WSEG_PLANAR(WSEG_PCM_S24); break;
+    case WSEG_PCM_S32: WSEG_PLANAR(WSEG_PCM_S32); break;
+    case WSEG_PCM_F32: WSEG_PLANAR(WSEG_PCM_F32); break;
+    default: WSEG_PLANAR(WSEG_PCM_F64); break;
+  }
+#undef WSEG_PLANAR
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }

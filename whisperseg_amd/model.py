@@ -51,6 +51,26 @@ def _per_item(value):
     return itertools.repeat(value)
 
 
+PER_RECORDING = ("min_frequency", "spec_time_step", "min_segment_length", "eps", "time_per_frame_for_voting", "num_trials",
+                 "consolidation_method")      # segment_batch's parameters that may be lists with one entry per recording
+
+
+class _PerRow(list):
+    """A per-FILE parameter list read per ROW by segment_batch: `counts` (rows of each file so far, growing while the files are
+    read) says how many rows in a row take a file's entry.  A list, so that _per_item iterates it."""
+
+    def __init__(self, values, counts):
+        super().__init__(values)
+        self.counts = counts
+
+    def __iter__(self):
+        for i, value in enumerate(list.__iter__(self)):
+            if len(self.counts) <= i:         # (a row's parameters are drawn after the row itself: its file is counted by then)
+                raise ValueError("a per-recording parameter was read ahead of its file")
+            for _ in range(self.counts[i]):
+                yield value
+
+
 def _read_json(path, default=None):
     if not os.path.exists(path):
         return default
@@ -346,20 +366,56 @@ class SegmenterBase:
             self._ingest = wavio.DeviceIngest(self.device_list[0])
         return self._ingest
 
-    def segment_files(self, paths, **segment_batch_kwargs):
+    def segment_channels(self, audio, sr, **segment_kwargs):
+        """segment() of every channel of a recording kept apart (`librosa.load(..., mono=False)` upstream, wavio.load_wav(mono=False)
+        / load_wav_device(mono=False) here): `audio` is [channels, n] (numpy or a device tensor) or 1-D -> a list with one
+        prediction dict per channel.  Computed as segment_batch over the rows: the windows of all channels share one pooled decode."""
+        if getattr(audio, "ndim", None) not in (1, 2):
+            raise ValueError("audio must be [n] or [channels, n]")
+        return self.segment_batch([audio] if audio.ndim == 1 else list(audio), sr, **segment_kwargs)
+
+    def segment_files(self, paths, channel_id=None, **segment_batch_kwargs):
         """segment_batch((load_wav(p) for p in paths), ...) element for element, without the host decode and without the
         serial file reads: one reader thread fills a pool of two pinned buffers (self.ingest_buffer_bytes each at most; larger
         files go through in pieces) while this thread copies filled buffers to the device, decodes the samples there
         (wseg_pcm_to_mono_f32: load_wav's float32 bits) and runs the front-end and the pooled decode of segment_batch on the
-        resident PCM.  Errors of the reader are raised here with the file's name; the thread is joined on every way out."""
+        resident PCM.  Errors of the reader are raised here with the file's name; the thread is joined on every way out.
+        `channel_id` (the reference's, segment_service.py:73-80): an int -> a list of dicts, channel `channel_id` of every
+        multi-channel file and the samples of every one-channel file (only that plane is decoded: wseg_pcm_to_planar_f32);
+        "all" -> per file a list with one dict per channel, the rows of all channels of all files pooled through ONE
+        segment_batch in file-then-channel order.  Per-recording parameter lists stay per FILE: a file's value applies to each
+        of its channels."""
         paths = list(paths)
         if not paths:
             return []
-        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes)
+        if channel_id == "all":
+            return self._segment_files_all_channels(paths, segment_batch_kwargs)
+        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes,
+                                      **({} if channel_id is None else {"channel_id": channel_id}))
         try:
             return self.segment_batch(iter(pipeline), **segment_batch_kwargs)
         finally:
             pipeline.close()
+
+    def _segment_files_all_channels(self, paths, kwargs):
+        counts = []                      # rows per file, as the pipeline hands them out
+        kwargs = dict(kwargs)
+        for name in PER_RECORDING:       # a per-file list becomes a per-row one, drawn from as the files' channel counts get known
+            if isinstance(kwargs.get(name), (list, tuple, np.ndarray)):
+                kwargs[name] = _PerRow(kwargs[name], counts)
+        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes, channel_id="all")
+
+        def rows():
+            for audio, sr in pipeline:
+                counts.append(1 if audio.ndim == 1 else len(audio))
+                for row in ([audio] if audio.ndim == 1 else audio):
+                    yield row, sr
+
+        try:
+            flat = iter(self.segment_batch(rows(), **kwargs))
+        finally:
+            pipeline.close()
+        return [list(itertools.islice(flat, n)) for n in counts]
 
     # ---- scoring helpers (reference model.py:474-569) --------------------------------------------
     def segment_score(self, prediction, label, target_cluster=None, tolerance=None):

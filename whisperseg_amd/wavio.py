@@ -1,5 +1,7 @@
 """Minimal RIFF/WAVE reader standing in for `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61;
-librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono.
+librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono — or, with
+mono=False, kept apart as `librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80,
+scripts/backend.py:279-282, demo.py:76-78).
 PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled; no resampling here."""
 import collections
 import io
@@ -26,8 +28,10 @@ def _read_chunks(f):
         yield cid, data
 
 
-def load_wav(path_or_file):
-    """-> (float32 mono ndarray, sampling_rate)."""
+def load_wav(path_or_file, mono=True):
+    """-> (float32 mono ndarray, sampling_rate).  mono=False: the channels kept apart, float32 [channels, n_frames]
+    (C-contiguous) for a file of two or more channels and [n_frames] for a one-channel file; every sample converted as for the
+    mono mix, before its mean."""
     f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) else path_or_file
     try:
         if not hasattr(f, "read"):
@@ -65,18 +69,23 @@ def load_wav(path_or_file):
         x = np.frombuffer(raw, "<f4" if bits == 32 else "<f8").astype(np.float32)
     else:
         raise ValueError(f"unsupported WAVE format tag {tag}")
-    if ch > 1:
+    if ch > 1 and not mono:
+        x = x[: len(x) // ch * ch].reshape(-1, ch).T
+    elif ch > 1:
         x = x[: len(x) // ch * ch].reshape(-1, ch).mean(axis=1).astype(np.float32)
     return np.ascontiguousarray(x, dtype=np.float32), int(sr)
 
 
 # ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
 # load_wav above is the arithmetic's definition; what follows moves it to the device: read_wav_raw hands out the data chunk's
-# bytes untouched, libwseg's wseg_pcm_to_mono_f32 widens and averages them with load_wav's float32 bits.
+# bytes untouched, libwseg's wseg_pcm_to_mono_f32 widens and averages them with load_wav's float32 bits, and
+# wseg_pcm_to_planar_f32 widens the channels one asks for into planes (load_wav(mono=False)'s rows).
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)        # wseg_pcm_format (include/wseg.h)
 BYTES_PER_SAMPLE = (1, 2, 3, 4, 4, 8)
 MAX_CHANNELS = 64
 STAGING_BYTES = 256 << 20        # one pinned staging buffer; a longer data chunk goes through in pieces
+PLANAR_TILE_FRAMES = 1024        # kPlanarTile of csrc/wseg_ingest.hip: the frames a workgroup of wseg_pcm_to_planar_f32 stages at a time
+PLANAR_GRID_CAP = 2048           # kPlanarGridCap there: with more tiles than this the workgroups take a grid stride
 
 WavRaw = collections.namedtuple("WavRaw", "data format channels sr n_frames")
 WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames frame_bytes offset")
@@ -189,9 +198,25 @@ class DeviceIngest:
     def new_output(self, n_frames):
         return self.torch.empty(int(n_frames), dtype=self.torch.float32, device=self.device)
 
+    def new_planar_output(self, n_channels, n_frames):
+        """The planes of `n_channels` channels: float32 [n_channels, n_frames]."""
+        return self.torch.empty((int(n_channels), int(n_frames)), dtype=self.torch.float32, device=self.device)
+
     def submit(self, view, nbytes, info, out, frame0, n_frames):
         """Decode `n_frames` frames whose `nbytes` bytes sit at the front of buffer `view` into out[frame0 : frame0 + n_frames]
         -> an event that has completed once the copy out of the buffer has, i.e. once the buffer may be written again."""
+        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_pcm_to_mono_f32(
+            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), out[frame0:frame0 + n_frames].data_ptr(),
+            self._lib.stream_ptr()))
+
+    def submit_planar(self, view, nbytes, info, out, frame0, n_frames, first_channel):
+        """submit for the planes of new_planar_output: channels first_channel .. first_channel + out.shape[0] - 1 of the piece go
+        to out[:, frame0 : frame0 + n_frames] (wseg_pcm_to_planar_f32 with the whole recording's frame count as plane stride)."""
+        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_pcm_to_planar_f32(
+            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(first_channel), int(out.shape[0]),
+            out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
+
+    def _submit(self, view, nbytes, n_frames, decode):
         torch = self.torch
         with torch.cuda.device(self.device):
             event = torch.cuda.Event()
@@ -201,9 +226,7 @@ class DeviceIngest:
                 raw = torch.empty(-(-nbytes // 16) * 16, dtype=torch.uint8, device=self.device)
                 raw[:nbytes].copy_(self._pinned[view.ctypes.data][:nbytes], non_blocking=True)
                 event.record()
-                dst = out[frame0:frame0 + n_frames]
-                self._lib.check(self.lib.wseg_pcm_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format),
-                                                              dst.data_ptr(), self._lib.stream_ptr()))
+                self._lib.check(decode(raw))
             else:
                 event.record()
         return event
@@ -233,13 +256,32 @@ def check_channels(info, name="wav"):
         raise ValueError(f"{name}: {info.channels} channels (the device decode takes up to {MAX_CHANNELS})")
 
 
+def select_channels(info, channel_id):
+    """What a caller's `channel_id` asks of a file -> None: the mono decode (channel_id None, or a one-channel file, whose
+    `channel_id` is ignored as upstream's `if len(audio.shape) == 2` does), else (first_channel, n_channels) for the planar
+    decode: "all" is every channel, an int one channel by Python's indexing (IndexError when out of range)."""
+    if channel_id is None or info.channels == 1:
+        return None
+    if isinstance(channel_id, str):
+        if channel_id != "all":
+            raise ValueError(f"channel_id must be an integer, 'all' or None (got {channel_id!r})")
+        return 0, info.channels
+    k = int(channel_id)
+    if not -info.channels <= k < info.channels:
+        raise IndexError(f"channel_id {k} is out of range for a recording of {info.channels} channels")
+    return k % info.channels, 1
+
+
 _INGEST = {}
 
 
-def load_wav_device(path_or_file, device="cuda", chunk_frames=None):
+def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, channel_id=None):
     """load_wav on the GPU -> (float32 device tensor [n_frames], sampling_rate), the same samples bit for bit: sample bytes ->
     pinned staging -> non_blocking copy -> wseg_pcm_to_mono_f32 on the current stream.  A data chunk larger than the staging
-    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces."""
+    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.
+    mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
+    wseg_pcm_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
+    ignores it; negative k counts from the end, out of range raises IndexError."""
     import torch
     key = str(torch.device(device))
     if key not in _INGEST:
@@ -252,7 +294,8 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None):
         total = info.n_frames * info.frame_bytes
         views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * info.frame_bytes)))
         step = chunk_plan(info, len(views[0]), chunk_frames)
-        out = ingest.new_output(info.n_frames)
+        sel = select_channels(info, channel_id if channel_id is not None or mono else "all")
+        out = ingest.new_output(info.n_frames) if sel is None else ingest.new_planar_output(sel[1], info.n_frames)
         events = [None, None]        # the next piece is read while the copy of the one before is in flight
         f.seek(info.offset)
         for i, frame0 in enumerate(range(0, info.n_frames, step)):
@@ -260,14 +303,17 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None):
             if events[i % 2] is not None:
                 ingest.done(events[i % 2], wait=True)
             _read_exact(f, views[i % 2][:n * info.frame_bytes])
-            events[i % 2] = ingest.submit(views[i % 2], n * info.frame_bytes, info, out, frame0, n)
+            if sel is None:
+                events[i % 2] = ingest.submit(views[i % 2], n * info.frame_bytes, info, out, frame0, n)
+            else:
+                events[i % 2] = ingest.submit_planar(views[i % 2], n * info.frame_bytes, info, out, frame0, n, sel[0])
         for event in events:         # the buffers belong to the next call
             if event is not None:
                 ingest.done(event, wait=True)
     finally:
         if ours:
             f.close()
-    return out, info.sr
+    return (out if sel is None or channel_id is None else out[0]), info.sr
 
 
 def _named(exc, path):
@@ -287,10 +333,13 @@ class FilePipeline:
     (`n_buffers` x at most `buffer_bytes`; larger files go through in pieces), the consuming thread submits filled buffers to
     `ingest` (DeviceIngest, or anything with its acquire / new_output / submit / done) and gives a buffer back to the reader once
     the event of its submit has completed.  The reader makes no device call.  A reader error is raised by the consumer with the
-    file's name; close() — also called when the iteration ends, fails or is abandoned — stops and joins the thread."""
+    file's name; close() — also called when the iteration ends, fails or is abandoned — stops and joins the thread.
+    `channel_id`: None — the mono mix, as above; an int — that channel of every multi-channel file ([n_frames]; one-channel files
+    give their samples; out of range: IndexError with the file's name); "all" — what load_wav(p, mono=False) gives.  The planes
+    come from the ingest's new_planar_output / submit_planar, which the mono mix never calls."""
 
-    def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2):
-        self.paths, self.ingest = list(paths), ingest
+    def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2, channel_id=None):
+        self.paths, self.ingest, self.channel_id = list(paths), ingest, channel_id
         sizes = [os.path.getsize(p) for p in self.paths if os.path.exists(p)]
         self.views = ingest.acquire(n_buffers, min(int(buffer_bytes), max(sizes + [16 * MAX_CHANNELS * 8]))) if self.paths else []
         self.free, self.filled = queue.Queue(), queue.Queue()
@@ -318,6 +367,7 @@ class FilePipeline:
                 with open(path, "rb") as f:
                     info = scan_wav(f)
                     check_channels(info, os.path.basename(path))
+                    sel = select_channels(info, self.channel_id)
                     step = chunk_plan(info, len(self.views[0]))
                     f.seek(info.offset)
                     for frame0 in range(0, max(info.n_frames, 1), step):
@@ -330,9 +380,9 @@ class FilePipeline:
                         except BaseException:
                             self.free.put(view)
                             raise
-                        self.filled.put((index, info, view, frame0, n))
+                        self.filled.put((index, info, view, frame0, n, sel))
             except BaseException as exc:
-                self.filled.put((index, exc, None, 0, 0))
+                self.filled.put((index, exc, None, 0, 0, None))
                 return
         self.filled.put(None)
 
@@ -366,14 +416,20 @@ class FilePipeline:
                 item = self._next_item()
                 if item is None:
                     break
-                index, info, view, frame0, n = item
+                index, info, view, frame0, n, sel = item
                 if isinstance(info, BaseException):
                     raise _named(info, self.paths[index]) from info
-                if frame0 == 0:
-                    out = self.ingest.new_output(info.n_frames)
-                self.pending.append((view, self.ingest.submit(view, n * info.frame_bytes, info, out, frame0, n)))
+                if sel is None:
+                    if frame0 == 0:
+                        out = self.ingest.new_output(info.n_frames)
+                    event = self.ingest.submit(view, n * info.frame_bytes, info, out, frame0, n)
+                else:
+                    if frame0 == 0:
+                        out = self.ingest.new_planar_output(sel[1], info.n_frames)
+                    event = self.ingest.submit_planar(view, n * info.frame_bytes, info, out, frame0, n, sel[0])
+                self.pending.append((view, event))
                 if frame0 + n >= info.n_frames:
-                    yield out, info.sr
+                    yield (out if sel is None or self.channel_id == "all" else out[0]), info.sr
                     out = None
         finally:
             self.close()
