@@ -107,6 +107,26 @@ int wseg_logmel_f32(const wseg_logmel_desc* d, const float* audio, int64_t n_aud
  * ---------------------------------------------------------------------------------------------- */
 int wseg_resample_f32(const float* x, int64_t n_in, const float* taps, int32_t n_taps, int32_t up, int32_t down,
                       int32_t pre_pad, int32_t pre_remove, float* y, int64_t n_out, void* stream);
+/* The same for n_planes signals at once (the channels of a recording kept apart): y[p * y_plane_stride + m] has the bits of
+ * wseg_resample_f32's y[m] for the signal x + p * x_plane_stride, 0 <= p < n_planes — the same fmaf chain over the same k, in
+ * one launch whatever the number of planes.  Strides in floats, x_plane_stride >= n_in and y_plane_stride >= n_out (both
+ * ignored when n_planes == 1); pointers and strides of any float alignment.  n_planes 1..64.
+ * taps: wseg_resample_f32's array, as it is (a workgroup lays it out phase-major in LDS itself when it fits there).
+ * n_out == 0 launches nothing; n_in == 0 launches no kernel and zero-fills y.  Writes nothing outside the n_planes * n_out
+ * addressed floats.  Stream-ordered.  Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_resample_planar_f32(const float* x, int64_t n_in, int64_t x_plane_stride, int32_t n_planes,
+                             const float* taps, int32_t n_taps, int32_t up, int32_t down,
+                             int32_t pre_pad, int32_t pre_remove,
+                             float* y, int64_t n_out, int64_t y_plane_stride, void* stream);
+/* The launch plan of wseg_resample_planar_f32, which launches from the same function (host arithmetic, no device; n_in, n_out
+ * and the two alignment integers are validated only — the plan follows from up, down and n_taps).  *tile: outputs a workgroup
+ * takes at a time, a multiple of 64; *x_staged: whether a tile's input window — k_lo of its first output to k_hi of its last —
+ * is staged in LDS, and then *window: the floats reserved for it, ceil((tile - 1) * down / up) + ceil(n_taps / up) + 2
+ * (0 when the window is read from global memory); *taps_staged: whether the taps are copied to LDS, phase-major.
+ * Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_debug_resample_plan(int64_t n_in, int64_t n_out, int32_t n_taps, int32_t up, int32_t down,
+                             int32_t pre_pad, int32_t pre_remove,
+                             int32_t* tile, int32_t* window, int32_t* x_staged, int32_t* taps_staged);
 
 /* ------------------------------------------------------------------------------------------------
  * WAVE sample decode (audio ingest).

@@ -5,10 +5,13 @@
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --csv_save_path out.csv
     cat a.wav | python scripts/segment.py --model_path DIR --audio_path - --csv_save_path buffer
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --channel_id all --csv_save_path out.csv
+    python scripts/segment.py --model_path DIR --audio_folder wavs/ --sr 16000 --csv_save_path out.csv
 
 --channel_id (the `channel_id` of the reference's interactive entry points: segment_service.py:73-80, scripts/backend.py:279-282,
 demo.py:76-78) segments one channel of multi-channel recordings instead of their mono mix — an integer: the same columns, rows
 of that channel (a one-channel file gives its samples) — or `all`: every channel, with a `channel` column behind `filename`.
+--sr N (`librosa.load(..., sr=N)` of the same entry points) resamples every recording to N Hz on the GPU before it is segmented,
+whatever --channel_id says; absent, recordings keep their native rate, as in the reference's CLI.
 """
 import argparse
 import csv
@@ -27,6 +30,13 @@ def channel_id_arg(text):
     return "all" if text == "all" else int(text)
 
 
+def sr_arg(text):
+    value = int(text)
+    if value <= 0:
+        raise argparse.ArgumentTypeError("--sr must be a positive integer")
+    return value
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--model_path")
@@ -42,6 +52,8 @@ def build_parser():
     p.add_argument("--channel_id", default=None, type=channel_id_arg,
                    help="segment this channel of multi-channel recordings (an integer, negative from the end), or 'all' of them; "
                         "absent: the mono mix")
+    p.add_argument("--sr", default=None, type=sr_arg,
+                   help="resample every recording to this rate (Hz) on the GPU before segmenting; absent: the native rate")
     return p
 
 
@@ -66,6 +78,18 @@ def table(results, names=None, all_channels=False):
     return columns, rows
 
 
+def stdin_wav(sr=None, channel_id=None):
+    """The wav on stdin, decoded on the host -> (audio, rate): the mono mix, or with `channel_id` the channels kept apart and the
+    reference's selection (`audio[channel_id]` of a 2-D array; "all" keeps them).  `sr`: resampled to it on the GPU, 1-D or planes."""
+    audio, native = load_wav(io.BytesIO(sys.stdin.buffer.read()), mono=channel_id is None)
+    if audio.ndim == 2 and channel_id != "all":
+        audio = audio[channel_id]
+    if sr is None or sr == native or not audio.shape[-1]:
+        return audio, (native if sr is None else sr)
+    from whisperseg_amd.resample import resample
+    return resample(audio, native, sr), sr
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     assert args.csv_save_path.endswith(".csv") or args.csv_save_path == "buffer", \
@@ -76,27 +100,25 @@ def main(argv=None):
         segmenter = WhisperSegmenter(args.model_path, device=args.device, device_ids=args.device_ids)
     kwargs = dict(min_frequency=args.min_frequency, spec_time_step=args.spec_time_step, num_trials=args.num_trials,
                   batch_size=args.batch_size)
+    rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
         paths = glob.glob(args.audio_folder + "/*.wav") + glob.glob(args.audio_folder + "/*.WAV")
         # same rows as the reference's serial loop, but the windows of many files share the engine's decode slots; files
         # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
         # a large folder needs no more memory than a small one
-        results = segmenter.segment_files(paths, **kwargs) if args.channel_id is None \
-            else segmenter.segment_files(paths, channel_id=args.channel_id, **kwargs)
+        results = segmenter.segment_files(paths, **({} if args.channel_id is None else {"channel_id": args.channel_id}), **rate, **kwargs)
         columns, rows = table(results, [os.path.basename(p) for p in paths], args.channel_id == "all")
     elif args.channel_id is None:
-        audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read())) if args.audio_path == "-" else load_wav_device(args.audio_path)
+        audio, sr = stdin_wav(args.sr) if args.audio_path == "-" else load_wav_device(args.audio_path, **rate)
         columns, rows = table([segmenter.segment(audio, sr, **kwargs)])
     else:
         if args.audio_path == "-":       # the channels kept apart on the host, and the reference's selection (`audio[channel_id]` of a 2-D array)
-            audio, sr = load_wav(io.BytesIO(sys.stdin.buffer.read()), mono=False)
-            if audio.ndim == 2 and args.channel_id != "all":
-                audio = audio[args.channel_id]
+            audio, sr = stdin_wav(args.sr, args.channel_id)
         elif args.channel_id == "all":
-            audio, sr = load_wav_device(args.audio_path, mono=False)
+            audio, sr = load_wav_device(args.audio_path, mono=False, **rate)
         else:
-            audio, sr = load_wav_device(args.audio_path, channel_id=args.channel_id)
+            audio, sr = load_wav_device(args.audio_path, channel_id=args.channel_id, **rate)
         if args.channel_id == "all":
             columns, rows = table([segmenter.segment_channels(audio, sr, **kwargs)], all_channels=True)
         else:

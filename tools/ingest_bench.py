@@ -4,6 +4,7 @@
 
     python tools/ingest_bench.py [--files 64] [--seconds 60] [--out profiles/ingest_ab.txt]
     python tools/ingest_bench.py --planar [--out profiles/ingest_planar_ab.txt]
+    python tools/ingest_bench.py --resample [--out profiles/resample_planar_ab.txt]
 
 For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
 `--seconds` seconds into a temporary directory and reports
@@ -19,7 +20,12 @@ windows), decode length capped at --max-length (random weights emit no meaningfu
 the same bytes (random, generated on the device), for PLANAR_CASES x 60 s and 600 s of audio.  GB/s = (input bytes + output
 bytes) over HIP-event time — the planar kernel writes `channels` times the mono kernel's output, so rates compare, times do not.
 A repetition is a train of back-to-back launches (as many as move about 2 GB, at least one) between two events; one warm-up
-train, then three repetitions of each kernel, alternating; all three rates are printed, the median is the figure."""
+train, then three repetitions of each kernel, alternating; all three rates are printed, the median is the figure.
+
+--resample measures the two resamplers alone, no engine, by the same protocol: wseg_resample_planar_f32 (one launch for all planes)
+beside the loop it replaces (one wseg_resample_f32 launch per plane, back to back) on the same planes (seeded normal samples,
+generated on the device) and the same taps, for RESAMPLE_CASES x 1, 2 and 8 planes of 600 s.  The figure is time per call in ms
+(all planes), and with it M output samples/s, G fmaf/s and the GB/s of the planes read and written once."""
 import argparse
 import os
 import statistics
@@ -130,6 +136,88 @@ def planar_section(lib, emit):
     return ratios
 
 
+RESAMPLE_CASES = ((44100, 16000), (48000, 16000), (96000, 16000), (16000, 44100), (250000, 44100))
+
+
+def resample_section(lib, emit, seconds=600, plane_counts=(1, 2, 8)):
+    import torch
+    from whisperseg_amd import _lib
+    from whisperseg_amd.resample import launch_plan, plan
+    stream = lambda: _lib.stream_ptr()
+    verdicts = {}
+    for sr_in, sr_out in RESAMPLE_CASES:
+        n_in = seconds * sr_in
+        p = plan(n_in, sr_in, sr_out)
+        n_out, n_taps, up, down = p["n_out"], len(p["taps"]), p["up"], p["down"]
+        h = torch.from_numpy(p["taps"]).cuda()
+        emit("%d -> %d Hz: up / down %d / %d, %d taps, plan %s" % (sr_in, sr_out, up, down, n_taps, launch_plan(n_in, sr_in, sr_out)))
+        for planes in plane_counts:
+            g = torch.Generator(device="cuda").manual_seed(planes)
+            x = torch.randn((planes, n_in), dtype=torch.float32, device="cuda", generator=g)
+            y = {name: torch.empty((planes, n_out), dtype=torch.float32, device="cuda") for name in ("planar", "loop")}
+
+            def planar():
+                _lib.check(lib.wseg_resample_planar_f32(x.data_ptr(), n_in, n_in, planes, h.data_ptr(), n_taps, up, down, p["pre_pad"],
+                                                        p["pre_remove"], y["planar"].data_ptr(), n_out, n_out, stream()))
+
+            def loop():
+                for c in range(planes):
+                    _lib.check(lib.wseg_resample_f32(x[c].data_ptr(), n_in, h.data_ptr(), n_taps, up, down, p["pre_pad"], p["pre_remove"],
+                                                     y["loop"][c].data_ptr(), n_out, stream()))
+
+            calls = {"planar": planar, "loop": loop}
+            moved = 4 * planes * (n_in + n_out)
+            iters = max(1, int(2e9 // moved))
+
+            def train(name):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    calls[name]()
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b) / iters
+
+            ms = {"planar": [], "loop": []}
+            for name in calls:
+                train(name)
+            equal = bool(torch.equal(y["planar"].view(torch.int32), y["loop"].view(torch.int32)))
+            for _ in range(3):
+                for name in calls:
+                    ms[name].append(train(name))
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            fma = planes * n_out * (n_taps / up)
+            for name in ("planar", "loop"):
+                emit("%6d -> %6d Hz x%d %4d s  %-6s %9.3f ms  (%s; %d calls per repetition)  %8.1f M out/s  %7.1f G fmaf/s  %7.1f GB/s"
+                     % (sr_in, sr_out, planes, seconds, name, med[name], " ".join("%.3f" % v for v in ms[name]), iters,
+                        planes * n_out / med[name] / 1e3, fma / med[name] / 1e6, moved / med[name] / 1e6))
+            spread = max(max(v) - min(v) for v in ms.values())
+            ok = med["planar"] <= med["loop"] + spread
+            verdicts[(sr_in, sr_out, planes)] = ok and equal
+            emit("%6d -> %6d Hz x%d %4d s  loop / planar time = %.2f  (largest spread of three repetitions: %.3f ms; not slower: %s; bits equal: %s)"
+                 % (sr_in, sr_out, planes, seconds, med["loop"] / med["planar"], spread, ok, equal))
+            del x, y
+    return verdicts
+
+
+def _tool_section(args, title, section):
+    """A kernels-only mode: print the section's lines and keep them in --out."""
+    import torch
+    from whisperseg_amd import _lib
+    lib = _lib.load(require_device=True)
+    lines = [title + ", " + torch.cuda.get_device_name(0)]
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    section(lib, emit)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=64)
@@ -139,25 +227,19 @@ def main(argv=None):
     ap.add_argument("--dtype", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--planar", action="store_true", help="only the kernels: wseg_pcm_to_planar_f32 beside wseg_pcm_to_mono_f32")
+    ap.add_argument("--resample", action="store_true",
+                    help="only the kernels: wseg_resample_planar_f32 beside one wseg_resample_f32 launch per plane")
     args = ap.parse_args(argv)
+    if args.resample:
+        return _tool_section(args, "resample A/B: wseg_resample_planar_f32 (one launch, all planes) beside a loop of wseg_resample_f32 launches "
+                                   "over the same planes and taps, HIP events, ms per call of all planes, median of three repetitions after one "
+                                   "warm-up (all three in brackets)", resample_section)
     import torch
     from whisperseg_amd import _lib
     if args.planar:
-        lib = _lib.load(require_device=True)
-        lines = ["planar decode A/B: wseg_pcm_to_planar_f32 (all channels) beside wseg_pcm_to_mono_f32 on the same bytes, HIP events, "
-                 "GB/s = (bytes in + bytes out) / time, median of three repetitions after one warm-up (all three in brackets), %s"
-                 % torch.cuda.get_device_name(0)]
-
-        def emit(s):
-            print(s, flush=True)
-            lines.append(s)
-
-        planar_section(lib, emit)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "w") as f:
-                f.write("\n".join(lines) + "\n")
-        return
+        return _tool_section(args, "planar decode A/B: wseg_pcm_to_planar_f32 (all channels) beside wseg_pcm_to_mono_f32 on the same bytes, "
+                                   "HIP events, GB/s = (bytes in + bytes out) / time, median of three repetitions after one warm-up (all "
+                                   "three in brackets)", planar_section)
     import bench
     from whisperseg_amd.engine import Engine
     from whisperseg_amd.model import DEFAULT_DTYPE

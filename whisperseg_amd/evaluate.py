@@ -5,7 +5,7 @@ import csv
 import json
 import os
 
-from .wavio import load_wav_device
+from .wavio import FilePipeline, device_ingest
 
 
 def read_label(label_path, default_config={}, ignore_cluster=False):
@@ -98,21 +98,21 @@ def evaluate(audio_list, label_list, segmenter, batch_size, max_length, num_tria
 
 
 def evaluate_dataset(dataset_folder, model_path, num_trials, max_length=448, num_beams=4, batch_size=8, **kwargs):
-    """reference evaluate.py:53-84.  Recordings whose native rate differs from the label's `sr` are resampled (the
-    reference does it inside librosa.load) with whisperseg_amd.resample."""
+    """reference evaluate.py:53-84.  The folder goes through the file pipeline (reads overlapped with the device work) with
+    each label's `sr` as its file's target rate: recordings at another rate are resampled on the GPU behind their decode (the
+    reference does it inside librosa.load)."""
     from .model import WhisperSegmenter, WhisperSegmenterFast
-    audio_list, label_list = [], []
+    audio_list = []
     audio_paths, label_paths = get_audio_and_label_paths(dataset_folder)
-    for audio_path, label_path in zip(audio_paths, label_paths):
-        label = read_label(label_path)
-        audio, sr = load_wav_device(audio_path)      # load_wav's samples, decoded on the GPU
-        want = label.get("sr", None)
-        if want is not None and int(want) != sr:      # librosa.load(path, sr=label sr) upstream: resample on the GPU
-            from .resample import resample
-            audio, sr = resample(audio, sr, int(want)), int(want)
-        label["sr"] = sr
-        audio_list.append(audio)
-        label_list.append(label)
+    label_list = [read_label(p) for p in label_paths]
+    rates = [None if label.get("sr") is None else int(label["sr"]) for label in label_list]
+    pipeline = FilePipeline(audio_paths, device_ingest("cuda"), sr=rates)      # load_wav's samples, decoded on the GPU
+    try:
+        for (audio, sr), label in zip(pipeline, label_list):
+            label["sr"] = sr
+            audio_list.append(audio)
+    finally:
+        pipeline.close()
     try:
         segmenter = WhisperSegmenterFast(model_path=model_path, device="cuda")
     except Exception:

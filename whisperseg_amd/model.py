@@ -374,7 +374,7 @@ class SegmenterBase:
             raise ValueError("audio must be [n] or [channels, n]")
         return self.segment_batch([audio] if audio.ndim == 1 else list(audio), sr, **segment_kwargs)
 
-    def segment_files(self, paths, channel_id=None, **segment_batch_kwargs):
+    def segment_files(self, paths, channel_id=None, sr=None, **segment_batch_kwargs):
         """segment_batch((load_wav(p) for p in paths), ...) element for element, without the host decode and without the
         serial file reads: one reader thread fills a pool of two pinned buffers (self.ingest_buffer_bytes each at most; larger
         files go through in pieces) while this thread copies filled buffers to the device, decodes the samples there
@@ -384,26 +384,31 @@ class SegmenterBase:
         multi-channel file and the samples of every one-channel file (only that plane is decoded: wseg_pcm_to_planar_f32);
         "all" -> per file a list with one dict per channel, the rows of all channels of all files pooled through ONE
         segment_batch in file-then-channel order.  Per-recording parameter lists stay per FILE: a file's value applies to each
-        of its channels."""
+        of its channels.
+        `sr` (`librosa.load(..., sr=sr)` upstream): the rate the files are segmented at — an int, or a list with one entry per
+        FILE (None entries: the native rate), under every `channel_id`.  A file at another rate is resampled on the device once
+        it is decoded, all its planes in one launch (wseg_resample_planar_f32), and the front-end sees the target rate."""
         paths = list(paths)
         if not paths:
             return []
         if channel_id == "all":
-            return self._segment_files_all_channels(paths, segment_batch_kwargs)
+            return self._segment_files_all_channels(paths, sr, segment_batch_kwargs)
         pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes,
-                                      **({} if channel_id is None else {"channel_id": channel_id}))
+                                      **({} if channel_id is None else {"channel_id": channel_id}),
+                                      **({} if sr is None else {"sr": sr}))
         try:
             return self.segment_batch(iter(pipeline), **segment_batch_kwargs)
         finally:
             pipeline.close()
 
-    def _segment_files_all_channels(self, paths, kwargs):
+    def _segment_files_all_channels(self, paths, sr, kwargs):
         counts = []                      # rows per file, as the pipeline hands them out
         kwargs = dict(kwargs)
         for name in PER_RECORDING:       # a per-file list becomes a per-row one, drawn from as the files' channel counts get known
             if isinstance(kwargs.get(name), (list, tuple, np.ndarray)):
                 kwargs[name] = _PerRow(kwargs[name], counts)
-        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes, channel_id="all")
+        pipeline = wavio.FilePipeline(paths, self.ingest_backend(), buffer_bytes=self.ingest_buffer_bytes, channel_id="all",
+                                      **({} if sr is None else {"sr": sr}))
 
         def rows():
             for audio, sr in pipeline:

@@ -2,7 +2,8 @@
 librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono — or, with
 mono=False, kept apart as `librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80,
 scripts/backend.py:279-282, demo.py:76-78).
-PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled; no resampling here."""
+PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled.  load_wav keeps the native rate; the device path
+(load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU (whisperseg_amd.resample), all planes of a file at once."""
 import collections
 import io
 import os
@@ -216,6 +217,13 @@ class DeviceIngest:
             raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(first_channel), int(out.shape[0]),
             out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
 
+    def resample(self, out, sr_in, sr_out):
+        """whisperseg_amd.resample.resample of a decoded tensor ([n_frames] or planes) on the current stream, i.e. behind the decode
+        launches of the file's pieces: one launch whatever the number of planes."""
+        from .resample import resample
+        with self.torch.cuda.device(self.device):
+            return resample(out, sr_in, sr_out, device=self.device)
+
     def _submit(self, view, nbytes, n_frames, decode):
         torch = self.torch
         with torch.cuda.device(self.device):
@@ -272,21 +280,38 @@ def select_channels(info, channel_id):
     return k % info.channels, 1
 
 
+def check_rate(sr):
+    """A target rate: None (the native rate) or a positive integer -> None or int."""
+    if sr is None:
+        return None
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr <= 0:
+        raise ValueError(f"sr must be a positive integer or None (got {sr!r})")
+    return int(sr)
+
+
 _INGEST = {}
 
 
-def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, channel_id=None):
+def device_ingest(device="cuda"):
+    """The DeviceIngest of `device`, made once and kept: its pinned staging buffers are re-used from call to call."""
+    import torch
+    key = str(torch.device(device))
+    if key not in _INGEST:
+        _INGEST[key] = DeviceIngest(device)
+    return _INGEST[key]
+
+
+def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, channel_id=None, sr=None):
     """load_wav on the GPU -> (float32 device tensor [n_frames], sampling_rate), the same samples bit for bit: sample bytes ->
     pinned staging -> non_blocking copy -> wseg_pcm_to_mono_f32 on the current stream.  A data chunk larger than the staging
     buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.
     mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
     wseg_pcm_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
-    ignores it; negative k counts from the end, out of range raises IndexError."""
-    import torch
-    key = str(torch.device(device))
-    if key not in _INGEST:
-        _INGEST[key] = DeviceIngest(device)
-    ingest = _INGEST[key]
+    ignores it; negative k counts from the end, out of range raises IndexError.
+    sr=N: `librosa.load(..., sr=N)` — what was decoded is resampled on the device (DeviceIngest.resample: one launch for all planes)
+    and N is the rate returned; None, the native rate or a file of no frames: nothing is resampled."""
+    sr = check_rate(sr)
+    ingest = device_ingest(device)
     f, ours = _opened(path_or_file)
     try:
         info = scan_wav(f)
@@ -313,7 +338,10 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     finally:
         if ours:
             f.close()
-    return (out if sel is None or channel_id is None else out[0]), info.sr
+    out = out if sel is None or channel_id is None else out[0]
+    if sr is not None and sr != info.sr and info.n_frames:
+        return ingest.resample(out, info.sr, sr), sr
+    return out, (info.sr if sr is None else sr)
 
 
 def _named(exc, path):
@@ -336,10 +364,23 @@ class FilePipeline:
     file's name; close() — also called when the iteration ends, fails or is abandoned — stops and joins the thread.
     `channel_id`: None — the mono mix, as above; an int — that channel of every multi-channel file ([n_frames]; one-channel files
     give their samples; out of range: IndexError with the file's name); "all" — what load_wav(p, mono=False) gives.  The planes
-    come from the ingest's new_planar_output / submit_planar, which the mono mix never calls."""
+    come from the ingest's new_planar_output / submit_planar, which the mono mix never calls.
+    `sr`: None — every file at its native rate; an int — the target rate of every file; a sequence with one entry per path (None
+    entries: the native rate).  A file whose native rate differs from its target is resampled once its LAST piece has been
+    submitted — ingest.resample(decoded, native, target), all its planes in one call, stream-ordered behind the decodes — and
+    yielded with the target rate; the native-rate tensor is dropped there.  ingest.resample is not called otherwise (no `sr`,
+    a file already at its target, a file of no frames), so an ingest without it serves a pipeline that never resamples."""
 
-    def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2, channel_id=None):
+    def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2, channel_id=None, sr=None):
         self.paths, self.ingest, self.channel_id = list(paths), ingest, channel_id
+        if sr is None or isinstance(sr, (int, np.integer)) and not isinstance(sr, bool):
+            self.rates = [check_rate(sr)] * len(self.paths)
+        elif isinstance(sr, (str, bytes)) or not hasattr(sr, "__len__"):
+            raise ValueError(f"sr must be a positive integer, a sequence of them or None (got {sr!r})")
+        else:
+            if len(sr) != len(self.paths):
+                raise ValueError(f"sr has {len(sr)} entries for {len(self.paths)} files")
+            self.rates = [check_rate(v) for v in sr]
         sizes = [os.path.getsize(p) for p in self.paths if os.path.exists(p)]
         self.views = ingest.acquire(n_buffers, min(int(buffer_bytes), max(sizes + [16 * MAX_CHANNELS * 8]))) if self.paths else []
         self.free, self.filled = queue.Queue(), queue.Queue()
@@ -429,7 +470,11 @@ class FilePipeline:
                     event = self.ingest.submit_planar(view, n * info.frame_bytes, info, out, frame0, n, sel[0])
                 self.pending.append((view, event))
                 if frame0 + n >= info.n_frames:
-                    yield (out if sel is None or self.channel_id == "all" else out[0]), info.sr
+                    out = out if sel is None or self.channel_id == "all" else out[0]
+                    target = self.rates[index] if self.rates[index] is not None else info.sr
+                    if target != info.sr and info.n_frames:
+                        out = self.ingest.resample(out, info.sr, target)      # (the native-rate tensor is let go of here)
+                    yield out, target
                     out = None
         finally:
             self.close()
