@@ -118,6 +118,23 @@ int wseg_resample_planar_f32(const float* x, int64_t n_in, int64_t x_plane_strid
                              const float* taps, int32_t n_taps, int32_t up, int32_t down,
                              int32_t pre_pad, int32_t pre_remove,
                              float* y, int64_t n_out, int64_t y_plane_stride, void* stream);
+/* A RANGE of the outputs of wseg_resample_planar_f32 from a SEGMENT of each plane: what resamples a recording piece by piece, each
+ * piece as soon as it is decoded, with the last frames of the piece before carried over (whisperseg_amd/resample.py stream_plan).
+ * x[p * x_plane_stride + (k - x_first)] is input sample k of plane p of the recording, x_first <= k < x_first + x_frames; n_in is the
+ * recording's frame count and enters only as the clamp of a chain's last input.  y is the base of plane 0 of the WHOLE output:
+ * y[p * y_plane_stride + m] is written for m_first <= m < m_first + m_count and nothing else, with the bits the whole-recording call
+ * gives that output (the same fmaf chain over the same inputs; an empty chain gives 0).  wseg_resample_planar_f32 is this call with
+ * x_first = 0, x_frames = n_in, m_first = 0, m_count = n_out.
+ * Validated before any launch, WSEG_ERR_INVALID with the offending range in wseg_last_error(): every chain of the range must lie
+ * inside the segment — first input of output m_first >= x_first, last input of output m_first + m_count - 1 < x_first + x_frames —
+ * and 0 <= m_first, m_count >= 0, x_first >= 0, x_frames >= 0, x_first + x_frames <= n_in, x_plane_stride >= x_frames and
+ * y_plane_stride >= m_first + m_count (both ignored when n_planes == 1), n_planes 1..64.  Pointers and strides of any float
+ * alignment; no 16-byte load crosses an end of the segment.  m_count == 0 launches nothing.  Stream-ordered.
+ * Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_resample_planar_range_f32(const float* x, int64_t x_first, int64_t x_frames, int64_t x_plane_stride, int32_t n_planes,
+                                   int64_t n_in, const float* taps, int32_t n_taps, int32_t up, int32_t down,
+                                   int32_t pre_pad, int32_t pre_remove,
+                                   float* y, int64_t m_first, int64_t m_count, int64_t y_plane_stride, void* stream);
 /* The launch plan of wseg_resample_planar_f32, which launches from the same function (host arithmetic, no device; n_in, n_out
  * and the two alignment integers are validated only — the plan follows from up, down and n_taps).  *tile: outputs a workgroup
  * takes at a time, a multiple of 64; *x_staged: whether a tile's input window — k_lo of its first output to k_hi of its last —

@@ -5,6 +5,7 @@
     python tools/ingest_bench.py [--files 64] [--seconds 60] [--out profiles/ingest_ab.txt]
     python tools/ingest_bench.py --planar [--out profiles/ingest_planar_ab.txt]
     python tools/ingest_bench.py --resample [--out profiles/resample_planar_ab.txt]
+    python tools/ingest_bench.py --stream [--out profiles/resample_stream_ab.txt]
 
 For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
 `--seconds` seconds into a temporary directory and reports
@@ -25,7 +26,14 @@ train, then three repetitions of each kernel, alternating; all three rates are p
 --resample measures the two resamplers alone, no engine, by the same protocol: wseg_resample_planar_f32 (one launch for all planes)
 beside the loop it replaces (one wseg_resample_f32 launch per plane, back to back) on the same planes (seeded normal samples,
 generated on the device) and the same taps, for RESAMPLE_CASES x 1, 2 and 8 planes of 600 s.  The figure is time per call in ms
-(all planes), and with it M output samples/s, G fmaf/s and the GB/s of the planes read and written once."""
+(all planes), and with it M output samples/s, G fmaf/s and the GB/s of the planes read and written once.
+
+--stream measures the file path at a target rate, no engine, through the public entry points only (so the same file runs at any
+commit that has `sr=`): load_wav_device(path, sr=) and a pass over FilePipeline([path], sr=) as segment_files makes it, on ONE
+s16 file per case that goes through in pieces of --piece-mb MiB (chunk_frames / buffer_bytes), for STREAM_CASES x mono and 8
+channels kept apart.  Per call: HIP-event time (first enqueue to last kernel), wall time (file read from the page cache included,
+ends in a synchronise) and the rise of torch.cuda.max_memory_allocated over the call.  One warm-up of each entry point, then five
+repetitions, the two entry points alternating; all five are printed, the median is the figure."""
 import argparse
 import os
 import statistics
@@ -200,6 +208,67 @@ def resample_section(lib, emit, seconds=600, plane_counts=(1, 2, 8)):
     return verdicts
 
 
+STREAM_CASES = ((250000, 44100, 120), (48000, 16000, 480))       # (native rate, target rate, seconds of audio)
+
+
+def stream_section(lib, emit, piece_mb=4, channel_counts=(1, 8), reps=5):
+    import torch
+    import wav_cases as WC
+    from whisperseg_amd import wavio
+    ingest = wavio.device_ingest("cuda")
+    piece_bytes = piece_mb << 20
+    for sr_in, sr_out, seconds in STREAM_CASES:
+        for channels in channel_counts:
+            n = seconds * sr_in
+            rng = np.random.default_rng(channels)
+            with tempfile.TemporaryDirectory() as d:
+                path = os.path.join(d, "rec.wav")
+                with open(path, "wb") as f:
+                    f.write(WC.wav_bytes("s16", channels, sr_in, rng.integers(-32768, 32768, n * channels, dtype=np.int16).tobytes()))
+                chunk_frames = piece_bytes // (2 * channels) // 16 * 16
+                kw = dict(mono=False) if channels > 1 else {}
+
+                def load():
+                    return wavio.load_wav_device(path, sr=sr_out, chunk_frames=chunk_frames, **kw)[0]
+
+                def pipeline():
+                    items = list(wavio.FilePipeline([path], ingest, buffer_bytes=piece_bytes, sr=sr_out, **({"channel_id": "all"} if channels > 1 else {})))
+                    return items[0][0]
+
+                calls = {"load_wav_device": load, "FilePipeline": pipeline}
+
+                def timed(name):
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    base = torch.cuda.memory_allocated()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0 = time.perf_counter()
+                    a.record()
+                    out = calls[name]()
+                    b.record()
+                    b.synchronize()
+                    wall = time.perf_counter() - t0
+                    peak = torch.cuda.max_memory_allocated() - base
+                    shape = tuple(out.shape)
+                    del out
+                    return a.elapsed_time(b), wall * 1e3, peak, shape
+
+                for name in calls:
+                    timed(name)
+                runs = {name: [] for name in calls}
+                for _ in range(reps):
+                    for name in calls:
+                        runs[name].append(timed(name))
+                pieces = -(-n // chunk_frames)
+                for name, r in runs.items():
+                    ev, wall = [v[0] for v in r], [v[1] for v in r]
+                    emit("%6d -> %6d Hz x%d %4d s (%d pieces of %d MiB, %.0f MB native planes, output %s)  %-15s events %8.2f ms (%s)  wall %8.2f ms (%s)  "
+                         "peak rise %7.1f MiB"
+                         % (sr_in, sr_out, channels, seconds, pieces, piece_mb, 4e-6 * n * channels, "x".join(map(str, r[0][3])), name,
+                            statistics.median(ev), " ".join("%.2f" % v for v in ev), statistics.median(wall), " ".join("%.2f" % v for v in wall),
+                            max(v[2] for v in r) / 2 ** 20))
+
+
 def _tool_section(args, title, section):
     """A kernels-only mode: print the section's lines and keep them in --out."""
     import torch
@@ -229,7 +298,15 @@ def main(argv=None):
     ap.add_argument("--planar", action="store_true", help="only the kernels: wseg_pcm_to_planar_f32 beside wseg_pcm_to_mono_f32")
     ap.add_argument("--resample", action="store_true",
                     help="only the kernels: wseg_resample_planar_f32 beside one wseg_resample_f32 launch per plane")
+    ap.add_argument("--stream", action="store_true",
+                    help="only the file path at a target rate: load_wav_device(sr=) and FilePipeline(sr=) on a file that goes through in pieces")
+    ap.add_argument("--piece-mb", type=int, default=4, help="--stream: MiB per piece of the file")
     args = ap.parse_args(argv)
+    if args.stream:
+        return _tool_section(args, "file path at a target rate: load_wav_device(sr=) and a pass over FilePipeline(sr=) on one multi-piece s16 file, "
+                                   "HIP events and wall time per call in ms, median of five repetitions after one warm-up, the two entry "
+                                   "points alternating (all five in brackets); peak rise of torch.cuda.max_memory_allocated over a call",
+                             lambda lib, emit: stream_section(lib, emit, piece_mb=args.piece_mb))
     if args.resample:
         return _tool_section(args, "resample A/B: wseg_resample_planar_f32 (one launch, all planes) beside a loop of wseg_resample_f32 launches "
                                    "over the same planes and taps, HIP events, ms per call of all planes, median of three repetitions after one "

@@ -6,6 +6,7 @@
 // lane walks its chain with two dependent-latency global loads per fmaf (measured 0.17-0.47 TB/s of signal moved on an MI355X,
 // DESIGN.md §8).  resample_planar_kernel further down stages both operands in LDS; this kernel stays as the arithmetic's definition.
 #include "wseg_common.h"
+#include "wseg_resample_range.h"
 
 namespace wseg {
 
@@ -38,6 +39,12 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
 // where a phase-major table in global memory scatters the 64 lanes of a wave over 64 lines (measured: 2.7 times slower than
 // resample_kernel at 250 k -> 44.1 k, profiles/resample_planar_ab.txt).  Each output is resample_kernel's fmaf chain — same c, k_lo,
 // k_hi, same order, nothing multiplied outside [k_lo, k_hi] — hence the same bits, whichever of the four variants runs.
+// The kernel takes a RANGE of outputs and a SEGMENT of each plane (wseg_resample_planar_range_f32): x points at input sample x_first of
+// plane 0, the tiles are cut from m_first on, and n_in — the recording's length — still enters only as the clamp of k_hi.  The host
+// has checked that every chain of the range lies inside the segment; a tile's window is k_lo of its first output to k_hi of its last,
+// so no load — the 16-byte ones included, which are taken only where all four floats lie inside the window, on the 16-byte grid of
+// the ADDRESS, whatever the segment's alignment — leaves the segment.  A file resampled piece by piece (wavio.StreamResampler) is a
+// sequence of such calls; the whole-recording call is the range [0, n_out) over the segment [0, n_in).
 constexpr int kResampleMaxTile = 1024;             // outputs per tile, at most (a multiple of 64)
 constexpr int kResampleWindowMax = 4096;           // floats of a staged input window (16 KiB)
 constexpr int kResampleTapsMax = 10240;            // floats of a staged tap table, padded rows included (40 KiB)
@@ -65,24 +72,12 @@ static ResamplePlan resample_plan(int n_taps, int up, int down) {
   return p;
 }
 
-struct ResampleRange { long long c, k_c, k_lo, k_hi; };      // k_c: floor(c / up), the k of tap c mod up
-
-__device__ __forceinline__ ResampleRange resample_range(long long m, long long n_in, int n_h, int up, int down, int pre_pad, int pre_remove) {
-  ResampleRange r;
-  r.c = (m + pre_remove) * (long long)down - pre_pad;
-  r.k_c = r.c / up;
-  if (r.c < 0) r.k_c = -((-r.c + up - 1) / up);
-  const long long lo_num = r.c - n_h + 1;
-  r.k_lo = lo_num <= 0 ? 0 : (lo_num + up - 1) / up;
-  r.k_hi = r.k_c > n_in - 1 ? n_in - 1 : r.k_c;
-  return r;
-}
-
 template <bool XS, bool TS>
-__global__ __launch_bounds__(256) void resample_planar_kernel(const float* __restrict__ x, long long n_in, long long x_stride, int n_planes,
-                                                              const float* __restrict__ h, int n_h, int row_lds, int up, int down,
-                                                              int pre_pad, int pre_remove, float* __restrict__ y, long long n_out,
-                                                              long long y_stride, int tile, int window_floats) {
+__global__ __launch_bounds__(256) void resample_planar_kernel(const float* __restrict__ x, long long x_first, long long n_in, long long x_stride,
+                                                              int n_planes, const float* __restrict__ h, int n_h, int row_lds, int up,
+                                                              int down, int pre_pad, int pre_remove, float* __restrict__ y,
+                                                              long long m_first, long long m_count, long long y_stride, int tile,
+                                                              int window_floats) {
   extern __shared__ float4 resample_lds[];
   float* xw = reinterpret_cast<float*>(resample_lds);
   float* tw = xw + window_floats;
@@ -93,13 +88,14 @@ __global__ __launch_bounds__(256) void resample_planar_kernel(const float* __res
       tw[(i - j * up) * row_lds + j] = h[i];
     }
   }
-  const long long n_tiles = (n_out + tile - 1) / tile;
+  const long long n_tiles = (m_count + tile - 1) / tile;
   const long long n_items = n_tiles * n_planes;
   for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
     const long long plane = item / n_tiles;
-    const long long m0 = (item - plane * n_tiles) * tile;
-    const int n_tile = (int)min((long long)tile, n_out - m0);
-    const float* __restrict__ xp = x + plane * x_stride;
+    const long long t0 = (item - plane * n_tiles) * tile;
+    const long long m0 = m_first + t0;
+    const int n_tile = (int)min((long long)tile, m_count - t0);
+    const float* __restrict__ xp = x + plane * x_stride - x_first;      // xp[k] is input sample k, for the k of the segment
     float* __restrict__ yp = y + plane * y_stride;
     long long s0 = 0;                              // the input sample at xw[0]
     if constexpr (XS) {
@@ -172,34 +168,39 @@ extern "C" int wseg_debug_resample_plan(int64_t n_in, int64_t n_out, int32_t n_t
   return WSEG_OK;
 }
 
-extern "C" int wseg_resample_planar_f32(const float* x, int64_t n_in, int64_t x_plane_stride, int32_t n_planes, const float* taps,
-                                        int32_t n_taps, int32_t up, int32_t down, int32_t pre_pad, int32_t pre_remove, float* y,
-                                        int64_t n_out, int64_t y_plane_stride, void* stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  const char* who = "wseg_resample_planar_f32";
+// The range call under the name of the entry point that was called: every check, then the launch.
+static int resample_planar_range(const char* who, const float* x, int64_t x_first, int64_t x_frames, int64_t x_plane_stride, int32_t n_planes,
+                                 int64_t n_in, const float* taps, int32_t n_taps, int32_t up, int32_t down, int32_t pre_pad,
+                                 int32_t pre_remove, float* y, int64_t m_first, int64_t m_count, int64_t y_plane_stride, hipStream_t s) {
   if (!x || !taps || !y || (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)y) & 3)) {
     set_error("%s: x, taps and y must be float32 device pointers", who); return WSEG_ERR_INVALID;
   }
-  if (int e = resample_check(who, n_in, n_out, n_taps, up, down, pre_pad, pre_remove)) return e;
+  if (int e = resample_check(who, n_in, 0, n_taps, up, down, pre_pad, pre_remove)) return e;
   if (n_planes < 1 || n_planes > 64) { set_error("%s: n_planes must be 1..64 (got %d)", who, n_planes); return WSEG_ERR_INVALID; }
-  if (n_planes > 1 && (x_plane_stride < n_in || y_plane_stride < n_out)) {
+  char why[256];
+  if (resample_range_check(x_first, x_frames, n_in, n_taps, up, down, pre_pad, pre_remove, m_first, m_count, why, sizeof(why))) {
+    set_error("%s: %s", who, why); return WSEG_ERR_INVALID;
+  }
+  // y is the base of the whole output: its planes are at least as long as the last output written
+  if (n_planes > 1 && (x_plane_stride < x_frames || y_plane_stride < m_first + m_count)) {
     set_error("%s: plane strides (%lld, %lld) are shorter than the planes (%lld, %lld)", who, (long long)x_plane_stride,
-              (long long)y_plane_stride, (long long)n_in, (long long)n_out);
+              (long long)y_plane_stride, (long long)x_frames, (long long)(m_first + m_count));
     return WSEG_ERR_INVALID;
   }
-  if (n_out == 0) return WSEG_OK;
+  if (m_count == 0) return WSEG_OK;
+  const long long xs = n_planes > 1 ? x_plane_stride : 0, ys = n_planes > 1 ? y_plane_stride : 0;
   if (n_in == 0) {                                 // no sample, no chain: zeros, without a kernel
-    for (int p = 0; p < n_planes; ++p) WSEG_HIP_CHECK(hipMemsetAsync(y + (size_t)p * y_plane_stride, 0, (size_t)n_out * 4, s));
+    for (int p = 0; p < n_planes; ++p) WSEG_HIP_CHECK(hipMemsetAsync(y + (size_t)p * ys + m_first, 0, (size_t)m_count * 4, s));
     return WSEG_OK;
   }
   const ResamplePlan p = resample_plan(n_taps, up, down);
-  const long long items = (n_out + p.tile - 1) / p.tile * n_planes;
+  const long long items = (m_count + p.tile - 1) / p.tile * n_planes;
   const dim3 grid((unsigned)(items < kResampleGridCap ? items : kResampleGridCap));
-  const long long xs = n_planes > 1 ? x_plane_stride : 0, ys = n_planes > 1 ? y_plane_stride : 0;
   const int window_floats = p.x_staged ? (p.window + 3 + 3) / 4 * 4 : 0;
-#define WSEG_RESAMPLE(XS, TS) hipLaunchKernelGGL((resample_planar_kernel<XS, TS>), grid, dim3(256), p.lds_bytes, s, x, (long long)n_in, xs, \
-                                                 (int)n_planes, taps, (int)n_taps, p.row_lds, (int)up, (int)down, (int)pre_pad,               \
-                                                 (int)pre_remove, y, (long long)n_out, ys, p.tile, window_floats)
+#define WSEG_RESAMPLE(XS, TS) hipLaunchKernelGGL((resample_planar_kernel<XS, TS>), grid, dim3(256), p.lds_bytes, s, x, (long long)x_first,     \
+                                                 (long long)n_in, xs, (int)n_planes, taps, (int)n_taps, p.row_lds, (int)up, (int)down,        \
+                                                 (int)pre_pad, (int)pre_remove, y, (long long)m_first, (long long)m_count, ys, p.tile,        \
+                                                 window_floats)
   if (p.x_staged && p.taps_staged) WSEG_RESAMPLE(true, true);
   else if (p.x_staged) WSEG_RESAMPLE(true, false);
   else if (p.taps_staged) WSEG_RESAMPLE(false, true);
@@ -207,4 +208,20 @@ extern "C" int wseg_resample_planar_f32(const float* x, int64_t n_in, int64_t x_
 #undef WSEG_RESAMPLE
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
+}
+
+extern "C" int wseg_resample_planar_range_f32(const float* x, int64_t x_first, int64_t x_frames, int64_t x_plane_stride, int32_t n_planes,
+                                              int64_t n_in, const float* taps, int32_t n_taps, int32_t up, int32_t down, int32_t pre_pad,
+                                              int32_t pre_remove, float* y, int64_t m_first, int64_t m_count, int64_t y_plane_stride,
+                                              void* stream_) {
+  return resample_planar_range("wseg_resample_planar_range_f32", x, x_first, x_frames, x_plane_stride, n_planes, n_in, taps, n_taps, up, down,
+                               pre_pad, pre_remove, y, m_first, m_count, y_plane_stride, (hipStream_t)stream_);
+}
+
+// The whole recording: the range [0, n_out) over the segment [0, n_in).
+extern "C" int wseg_resample_planar_f32(const float* x, int64_t n_in, int64_t x_plane_stride, int32_t n_planes, const float* taps,
+                                        int32_t n_taps, int32_t up, int32_t down, int32_t pre_pad, int32_t pre_remove, float* y,
+                                        int64_t n_out, int64_t y_plane_stride, void* stream_) {
+  return resample_planar_range("wseg_resample_planar_f32", x, 0, n_in, x_plane_stride, n_planes, n_in, taps, n_taps, up, down, pre_pad,
+                               pre_remove, y, 0, n_out, y_plane_stride, (hipStream_t)stream_);
 }

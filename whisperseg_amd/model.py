@@ -386,8 +386,9 @@ class SegmenterBase:
         segment_batch in file-then-channel order.  Per-recording parameter lists stay per FILE: a file's value applies to each
         of its channels.
         `sr` (`librosa.load(..., sr=sr)` upstream): the rate the files are segmented at — an int, or a list with one entry per
-        FILE (None entries: the native rate), under every `channel_id`.  A file at another rate is resampled on the device once
-        it is decoded, all its planes in one launch (wseg_resample_planar_f32), and the front-end sees the target rate."""
+        FILE (None entries: the native rate), under every `channel_id`.  A file at another rate is resampled on the device piece by
+        piece as it is decoded, all its planes in one launch per piece (wseg_resample_planar_range_f32: no native-rate copy of the
+        file), and the front-end sees the target rate."""
         paths = list(paths)
         if not paths:
             return []

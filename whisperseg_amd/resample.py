@@ -5,8 +5,10 @@ a third-party resampler that is neither pinned nor installed here.  This module 
 polyphase scheme — Kaiser(beta=5)-windowed sinc low-pass of half-length 10*max(up, down), unity DC gain times `up`,
 centred output of ceil(n*up/down) samples — which is also what `scipy.signal.resample_poly` computes; the arithmetic runs
 in libwseg: `wseg_resample_f32` for one signal, `wseg_resample_planar_f32` for the channels of a recording kept apart
-([channels, n]: one launch, every row with the bits of the one-signal call).  The file path resamples through here:
-wavio.DeviceIngest.resample, hence FilePipeline(sr=), load_wav_device(sr=), segment_files(sr=) and the CLI's --sr."""
+([channels, n]: one launch, every row with the bits of the one-signal call), `wseg_resample_planar_range_f32` for a range of
+those outputs from a segment of the planes.  The file path — FilePipeline(sr=), load_wav_device(sr=), segment_files(sr=) and the
+CLI's --sr — resamples a file piece by piece with the range call (wavio.StreamResampler, planned by stream_plan below: the bits of
+resample() on the whole file, which never exists at its native rate); wavio.DeviceIngest.resample is resample()."""
 import ctypes as C
 import math
 
@@ -16,10 +18,15 @@ import torch
 from . import _lib
 
 
+def filter_half_len(up, down):
+    """Half the filter's length for the reduced ratio up/down: 2 * half_len + 1 taps (design_taps makes them, _ratio counts them)."""
+    return 10 * max(up, down)
+
+
 def design_taps(up, down, beta=5.0):
     """float32 FIR taps (already scaled by `up`) + half length, for the reduced ratio up/down."""
     max_rate = max(up, down)
-    half_len = 10 * max_rate
+    half_len = filter_half_len(up, down)
     n = 2 * half_len + 1
     m = np.arange(n, dtype=np.float64) - half_len
     cutoff = 1.0 / max_rate
@@ -30,14 +37,63 @@ def design_taps(up, down, beta=5.0):
     return h, half_len
 
 
-def plan(n_in, sr_in, sr_out):
+def _ratio(sr_in, sr_out):
+    """-> (up, down, n_taps, pre_pad, pre_remove): plan()'s integers without the taps."""
     g = math.gcd(int(sr_in), int(sr_out))
     up, down = int(sr_out) // g, int(sr_in) // g
-    n_out = -(-n_in * up // down)
-    taps, half_len = design_taps(up, down)
+    half_len = filter_half_len(up, down)
     pre_pad = down - half_len % down
-    pre_remove = (half_len + pre_pad) // down
+    return up, down, 2 * half_len + 1, pre_pad, (half_len + pre_pad) // down
+
+
+def plan(n_in, sr_in, sr_out):
+    up, down, n_taps, pre_pad, pre_remove = _ratio(sr_in, sr_out)
+    n_out = -(-n_in * up // down)
+    taps, _ = design_taps(up, down)
+    assert len(taps) == n_taps                       # stream_plan / stream_capacity count the taps without designing them
     return dict(up=up, down=down, n_out=n_out, taps=taps, pre_pad=pre_pad, pre_remove=pre_remove)
+
+
+def stream_capacity(sr_in, sr_out, piece_frames):
+    """The frames (per plane) a segment buffer must hold to resample a recording in pieces of at most `piece_frames` frames: the
+    frames retained from the pieces before plus one piece.  It depends on the ratio and the piece size only.
+    The retained frames are at most row - 1, row = ceil(n_taps / up): behind a piece that ends at frame E (exclusive) the first
+    output m not yet emitted has k_c(m) = floor(c / up) >= E, i.e. c >= E * up, hence
+    k_lo(m) >= ceil((E * up - n_taps + 1) / up) = E - floor((n_taps - 1) / up) = E - (row - 1), and frames k_lo(m) .. E - 1 are kept."""
+    up, _, n_taps, _, _ = _ratio(sr_in, sr_out)
+    return -(-n_taps // up) - 1 + int(piece_frames)
+
+
+def stream_plan(n_in, sr_in, sr_out, piece_frames):
+    """Resampling a recording of n_in frames piece by piece (wseg_resample_planar_range_f32), pure arithmetic: for every piece
+    [frame0, frame0 + n) of at most `piece_frames` frames, in order, yields dict(frame0, n, x_first, m_first, m_count, keep_from):
+      m_first .. m_first + m_count - 1  the outputs that become computable with this piece — those whose chain ends inside it or
+                                        before it, k_c(m) <= frame0 + n - 1, and that no earlier piece emitted; on the last piece
+                                        all that remain.  m_count == 0 is legal (a piece shorter than the step between two outputs);
+      x_first                           the first frame the segment holds when they are computed: keep_from of the piece before
+                                        (0 for the first), so the segment is [x_first, frame0 + n);
+      keep_from                         the first frame still needed afterwards: min(k_lo(next output), frame0 + n); frame0 + n once
+                                        every output has been emitted.
+    frame0 + n - keep_from never exceeds stream_capacity(sr_in, sr_out, piece_frames) - piece_frames."""
+    n_in, piece_frames = int(n_in), int(piece_frames)
+    if piece_frames <= 0:
+        raise ValueError("piece_frames must be positive")
+    up, down, n_taps, pre_pad, pre_remove = _ratio(sr_in, sr_out)
+    n_out = -(-n_in * up // down)
+    emitted, x_first = 0, 0
+    for frame0 in range(0, n_in, piece_frames):
+        n = min(piece_frames, n_in - frame0)
+        end = frame0 + n
+        if end >= n_in:
+            m_end = n_out
+        else:        # floor(c / up) <= end - 1  <=>  (m + pre_remove) * down <= (end - 1) * up + up - 1 + pre_pad
+            m_end = min(n_out, max(emitted, (end * up - 1 + pre_pad) // down - pre_remove + 1))
+        keep_from = end
+        if m_end < n_out:
+            c = (m_end + pre_remove) * down - pre_pad
+            keep_from = min(max(0, -(-(c - n_taps + 1) // up)), end)
+        yield dict(frame0=frame0, n=n, x_first=x_first, m_first=emitted, m_count=m_end - emitted, keep_from=keep_from)
+        emitted, x_first = m_end, keep_from
 
 
 PLANAR_GRID_CAP = 2048           # kResampleGridCap of csrc/wseg_resample.hip: with more tiles x planes than this the workgroups take a grid stride

@@ -3,7 +3,8 @@ librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1
 mono=False, kept apart as `librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80,
 scripts/backend.py:279-282, demo.py:76-78).
 PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled.  load_wav keeps the native rate; the device path
-(load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU (whisperseg_amd.resample), all planes of a file at once."""
+(load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU (whisperseg_amd.resample), all planes of a file at once and
+piece by piece as the file is read (StreamResampler)."""
 import collections
 import io
 import os
@@ -224,6 +225,11 @@ class DeviceIngest:
         with self.torch.cuda.device(self.device):
             return resample(out, sr_in, sr_out, device=self.device)
 
+    def open_resampled(self, info, sel, sr_out, piece_frames):
+        """A StreamResampler for ONE file that goes through in pieces of at most `piece_frames` frames: the file at `sr_out`
+        without its native-rate tensor.  sel: select_channels' answer (None: the mono mix)."""
+        return StreamResampler(self, info, sel, sr_out, piece_frames)
+
     def _submit(self, view, nbytes, n_frames, decode):
         torch = self.torch
         with torch.cuda.device(self.device):
@@ -244,6 +250,78 @@ class DeviceIngest:
         if wait:
             event.synchronize()
         return event.query()
+
+
+class StreamResampler:
+    """One open file resampled piece by piece on the device (DeviceIngest.open_resampled).  It owns the file's output at the target
+    rate — [n_out], or [planes, n_out] for a planar selection — and ONE segment buffer of resample.stream_capacity frames per plane
+    (plus up to 3 floats in front and a stride rounded up to four: see below).
+    submit(), per piece and in the file's order, on the current stream and without a host synchronisation: the frames the next
+    outputs still need move to the front of the segment, the piece is decoded behind them (wseg_pcm_to_mono_f32 /
+    wseg_pcm_to_planar_f32 with the segment's stride as plane stride), and ONE wseg_resample_planar_range_f32 launch writes the
+    outputs that have become computable, all planes at once (resample.stream_plan says which; a piece may add none).  Every output
+    has the bits resample() gives it on the whole decoded recording.  result(): the output, once the last piece has been submitted.
+    "The front" is 0 to 3 floats into the segment, such that the PIECE starts on a multiple of 16 bytes however many frames are
+    retained: wseg_pcm_to_mono_f32 stores 16 bytes per lane only to an aligned destination (dword stores otherwise), whereas the
+    range call reads a segment of any alignment."""
+
+    def __init__(self, ingest, info, sel, sr_out, piece_frames):
+        from . import resample as R
+        self.ingest, self.info, self.sel = ingest, info, sel
+        self.plan = R.plan(info.n_frames, info.sr, sr_out)
+        self.steps = R.stream_plan(info.n_frames, info.sr, sr_out, piece_frames)
+        self.capacity = R.stream_capacity(info.sr, sr_out, piece_frames)
+        planes = 1 if sel is None else sel[1]
+        if planes > R.MAX_PLANES:
+            raise ValueError(f"{planes} channels (one resample launch takes up to {R.MAX_PLANES})")
+        self.out = ingest.new_output(self.plan["n_out"]) if sel is None else ingest.new_planar_output(planes, self.plan["n_out"])
+        self.stride = -(-(self.capacity + 3) // 4) * 4       # (torch aligns the tensor itself to 512 bytes)
+        self.segment = ingest.new_planar_output(planes, self.stride)
+        self.taps = R._device_taps(self.plan, ingest.device)
+        self.first = self.end = self.lead = 0    # the segment holds frames [first, end) of the recording, `lead` floats in
+        self.pending = info.n_frames > 0
+
+    def submit(self, view, nbytes, frame0, n_frames):
+        """DeviceIngest.submit for the piece [frame0, frame0 + n_frames) -> the event after which `view` may be rewritten."""
+        ingest, info, p, seg = self.ingest, self.info, self.plan, self.segment
+        step = next(self.steps, None)
+        if step is None or (step["frame0"], step["n"]) != (frame0, n_frames) or frame0 != self.end:
+            raise ValueError(f"piece [{frame0}, {frame0} + {n_frames}) is not the next piece of the stream plan ({step})")
+        kept = self.end - step["x_first"]
+        src, lead = self.lead + step["x_first"] - self.first, -kept % 4
+        if kept + n_frames > self.capacity:
+            raise RuntimeError(f"{kept} retained frames + a piece of {n_frames} exceed the segment's {self.capacity}")
+        lib, stream_ptr = ingest.lib, ingest._lib.stream_ptr
+
+        def decode_and_resample(raw):
+            dst = seg.data_ptr() + 4 * (lead + kept)
+            if self.sel is None:
+                status = lib.wseg_pcm_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst, stream_ptr())
+            else:
+                status = lib.wseg_pcm_to_planar_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(self.sel[0]),
+                                                    int(seg.shape[0]), dst, self.stride, stream_ptr())
+            if status or not step["m_count"]:
+                return status
+            return lib.wseg_resample_planar_range_f32(
+                seg.data_ptr() + 4 * lead, step["x_first"], kept + n_frames, self.stride, int(seg.shape[0]), int(info.n_frames),
+                self.taps.data_ptr(), int(self.taps.numel()), p["up"], p["down"], p["pre_pad"], p["pre_remove"], self.out.data_ptr(),
+                step["m_first"], step["m_count"], p["n_out"], stream_ptr())
+
+        with ingest.torch.cuda.device(ingest.device):
+            if kept and src != lead:
+                kept_frames = seg[:, src:src + kept]
+                # the frames overlap their new place only when the history is longer than what came after it, i.e. with pieces
+                # shorter than the ceil(n_taps / up) - 1 retained frames (tens to a thousand frames: test sizes, not staging buffers)
+                seg[:, lead:lead + kept].copy_(kept_frames if src >= lead + kept else kept_frames.clone())
+            event = ingest._submit(view, nbytes, n_frames, decode_and_resample)
+        self.first, self.end, self.lead = step["x_first"], frame0 + n_frames, lead
+        self.pending = self.end < info.n_frames
+        return event
+
+    def result(self):
+        if self.pending:
+            raise RuntimeError(f"result() after {self.end} of {self.info.n_frames} frames")
+        return self.out
 
 
 def chunk_plan(info, buffer_bytes, chunk_frames=None):
@@ -308,8 +386,9 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
     wseg_pcm_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
     ignores it; negative k counts from the end, out of range raises IndexError.
-    sr=N: `librosa.load(..., sr=N)` — what was decoded is resampled on the device (DeviceIngest.resample: one launch for all planes)
-    and N is the rate returned; None, the native rate or a file of no frames: nothing is resampled."""
+    sr=N: `librosa.load(..., sr=N)` — every piece is resampled on the device as soon as it is decoded (StreamResampler: one launch
+    per piece for all planes, the bits of resample() on the whole decoded file, which is never held at its native rate) and N is the
+    rate returned; None, the native rate or a file of no frames: nothing is resampled."""
     sr = check_rate(sr)
     ingest = device_ingest(device)
     f, ours = _opened(path_or_file)
@@ -320,7 +399,12 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
         views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * info.frame_bytes)))
         step = chunk_plan(info, len(views[0]), chunk_frames)
         sel = select_channels(info, channel_id if channel_id is not None or mono else "all")
-        out = ingest.new_output(info.n_frames) if sel is None else ingest.new_planar_output(sel[1], info.n_frames)
+        target = info.sr if sr is None else sr
+        stream = None                # a file that changes rate is resampled as its pieces arrive: no native-rate tensor
+        if target != info.sr and info.n_frames:
+            stream = ingest.open_resampled(info, sel, target, min(step, info.n_frames))
+        else:
+            out = ingest.new_output(info.n_frames) if sel is None else ingest.new_planar_output(sel[1], info.n_frames)
         events = [None, None]        # the next piece is read while the copy of the one before is in flight
         f.seek(info.offset)
         for i, frame0 in enumerate(range(0, info.n_frames, step)):
@@ -328,7 +412,9 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
             if events[i % 2] is not None:
                 ingest.done(events[i % 2], wait=True)
             _read_exact(f, views[i % 2][:n * info.frame_bytes])
-            if sel is None:
+            if stream is not None:
+                events[i % 2] = stream.submit(views[i % 2], n * info.frame_bytes, frame0, n)
+            elif sel is None:
                 events[i % 2] = ingest.submit(views[i % 2], n * info.frame_bytes, info, out, frame0, n)
             else:
                 events[i % 2] = ingest.submit_planar(views[i % 2], n * info.frame_bytes, info, out, frame0, n, sel[0])
@@ -338,10 +424,9 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     finally:
         if ours:
             f.close()
-    out = out if sel is None or channel_id is None else out[0]
-    if sr is not None and sr != info.sr and info.n_frames:
-        return ingest.resample(out, info.sr, sr), sr
-    return out, (info.sr if sr is None else sr)
+    if stream is not None:
+        out = stream.result()
+    return (out if sel is None or channel_id is None else out[0]), target
 
 
 def _named(exc, path):
@@ -366,10 +451,14 @@ class FilePipeline:
     give their samples; out of range: IndexError with the file's name); "all" — what load_wav(p, mono=False) gives.  The planes
     come from the ingest's new_planar_output / submit_planar, which the mono mix never calls.
     `sr`: None — every file at its native rate; an int — the target rate of every file; a sequence with one entry per path (None
-    entries: the native rate).  A file whose native rate differs from its target is resampled once its LAST piece has been
-    submitted — ingest.resample(decoded, native, target), all its planes in one call, stream-ordered behind the decodes — and
-    yielded with the target rate; the native-rate tensor is dropped there.  ingest.resample is not called otherwise (no `sr`,
-    a file already at its target, a file of no frames), so an ingest without it serves a pipeline that never resamples."""
+    entries: the native rate).  A file whose native rate differs from its target is yielded with the target rate.  An ingest with
+    open_resampled (DeviceIngest) resamples it piece by piece — ingest.open_resampled(info, sel, target, piece_frames) when the
+    file's first piece arrives, .submit(view, nbytes, frame0, n) for every piece in place of submit / submit_planar, .result()
+    behind the last — so the file never exists at its native rate and the resampler runs while the reader reads on.  An ingest
+    that offers only `resample` is served as before: the file is decoded whole and resampled once its LAST piece has been
+    submitted — ingest.resample(decoded, native, target), all its planes in one call — and the native-rate tensor is dropped
+    there.  Neither is called otherwise (no `sr`, a file already at its target, a file of no frames), so an ingest without them
+    serves a pipeline that never resamples."""
 
     def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2, channel_id=None, sr=None):
         self.paths, self.ingest, self.channel_id = list(paths), ingest, channel_id
@@ -452,7 +541,7 @@ class FilePipeline:
 
     def __iter__(self):
         try:
-            out = None
+            out = stream = None
             while self.thread is not None:
                 item = self._next_item()
                 if item is None:
@@ -460,7 +549,12 @@ class FilePipeline:
                 index, info, view, frame0, n, sel = item
                 if isinstance(info, BaseException):
                     raise _named(info, self.paths[index]) from info
-                if sel is None:
+                target = self.rates[index] if self.rates[index] is not None else info.sr
+                if frame0 == 0 and target != info.sr and info.n_frames and hasattr(self.ingest, "open_resampled"):
+                    stream = self.ingest.open_resampled(info, sel, target, n)     # (a file's first piece is its longest)
+                if stream is not None:
+                    event = stream.submit(view, n * info.frame_bytes, frame0, n)
+                elif sel is None:
                     if frame0 == 0:
                         out = self.ingest.new_output(info.n_frames)
                     event = self.ingest.submit(view, n * info.frame_bytes, info, out, frame0, n)
@@ -470,12 +564,13 @@ class FilePipeline:
                     event = self.ingest.submit_planar(view, n * info.frame_bytes, info, out, frame0, n, sel[0])
                 self.pending.append((view, event))
                 if frame0 + n >= info.n_frames:
+                    if stream is not None:
+                        out = stream.result()
                     out = out if sel is None or self.channel_id == "all" else out[0]
-                    target = self.rates[index] if self.rates[index] is not None else info.sr
-                    if target != info.sr and info.n_frames:
+                    if stream is None and target != info.sr and info.n_frames:
                         out = self.ingest.resample(out, info.sr, target)      # (the native-rate tensor is let go of here)
                     yield out, target
-                    out = None
+                    out = stream = None
         finally:
             self.close()
 
