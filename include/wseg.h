@@ -146,7 +146,7 @@ int wseg_debug_resample_plan(int64_t n_in, int64_t n_out, int32_t n_taps, int32_
                              int32_t* tile, int32_t* window, int32_t* x_staged, int32_t* taps_staged);
 
 /* ------------------------------------------------------------------------------------------------
- * WAVE sample decode (audio ingest).
+ * Audio sample decode (audio ingest).
  * Replaces the decoding half of `librosa.load(path, sr=None)` at reference scripts/segment.py:48,61 and evaluate.py:58:
  * sample formats widened to float32 in [-1, 1) and channels averaged to mono, with the float32 bits
  * whisperseg_amd/wavio.py::load_wav produces on the host (u8 (x - 128) / 128, s16 x / 2^15, s24 sign-extended / 2^23,
@@ -171,6 +171,27 @@ int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, in
 int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format,
                            int32_t first_channel, int32_t n_out_channels,
                            float* out, int64_t plane_stride, void* stream);
+/* The same two decodes for every sample encoding the containers of whisperseg_amd/wavio.py carry (WAVE / RF64 / BW64, AIFF /
+ * AIFF-C, AU): what wavio.load_audio does on the host, with its float32 bits.  Codes 0..5 are wseg_pcm_format, same numbers, same
+ * arithmetic; the big-endian encodings are byte-swapped in registers and then widened as their little-endian siblings; G.711 codes
+ * are expanded to int16 with integer arithmetic (the standard's expansion, the tables of libsndfile and CPython's audioop:
+ * u-law extremes +-32124, A-law +-32256) and divided by 2^15.  Equality with libsndfile's floats is by construction (integer /
+ * 2^(bits-1), G.711 through int16), not pinned by a test.
+ * Every other part of the contract is that of wseg_pcm_to_mono_f32 / wseg_pcm_to_planar_f32: raw 16-byte aligned and readable to
+ * the next multiple of 16 bytes, out of any float alignment, channels 1..64, numpy's mean over the channels, nothing written
+ * outside the addressed floats, n_frames == 0 launches nothing, stream-ordered.  An encoding outside 0..13 is WSEG_ERR_INVALID
+ * ("encoding" in wseg_last_error()).  The wseg_pcm_* entry points are these with codes 0..5 and go on rejecting every other code.
+ * Added without moving WSEG_ABI_VERSION (an addition). */
+typedef enum {                      /* 0..5 are wseg_pcm_format, same numbers, same arithmetic */
+  WSEG_ENC_S8 = 6,                  /* signed 8-bit: x / 128 */
+  WSEG_ENC_S16BE = 7, WSEG_ENC_S24BE = 8, WSEG_ENC_S32BE = 9,   /* byte-swapped, then as S16 / S24 / S32 */
+  WSEG_ENC_F32BE = 10, WSEG_ENC_F64BE = 11,                     /* byte-swapped, then as F32 / F64 */
+  WSEG_ENC_ULAW = 12, WSEG_ENC_ALAW = 13   /* G.711: 8 bits -> int16 by the standard expansion, then x / 2^15 */
+} wseg_sample_encoding;
+int wseg_samples_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding, float* out, void* stream);
+int wseg_samples_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding,
+                               int32_t first_channel, int32_t n_out_channels,
+                               float* out, int64_t plane_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.

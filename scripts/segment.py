@@ -6,12 +6,17 @@
     cat a.wav | python scripts/segment.py --model_path DIR --audio_path - --csv_save_path buffer
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --channel_id all --csv_save_path out.csv
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --sr 16000 --csv_save_path out.csv
+    python scripts/segment.py --model_path DIR --audio_folder mixed/ --audio_ext wav aiff aifc au --csv_save_path out.csv
+
+Recordings may be RIFF/WAVE (RF64 / BW64 included), AIFF / AIFF-C or AU files (whisperseg_amd/wavio.py), whatever their names.
 
 --channel_id (the `channel_id` of the reference's interactive entry points: segment_service.py:73-80, scripts/backend.py:279-282,
 demo.py:76-78) segments one channel of multi-channel recordings instead of their mono mix — an integer: the same columns, rows
 of that channel (a one-channel file gives its samples) — or `all`: every channel, with a `channel` column behind `filename`.
 --sr N (`librosa.load(..., sr=N)` of the same entry points) resamples every recording to N Hz on the GPU before it is segmented,
 whatever --channel_id says; absent, recordings keep their native rate, as in the reference's CLI.
+--audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
+then `*.WAV`, as in the reference's CLI.
 """
 import argparse
 import csv
@@ -23,7 +28,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
-from whisperseg_amd.wavio import load_wav, load_wav_device  # noqa: E402
+from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
 
 
 def channel_id_arg(text):
@@ -40,8 +45,8 @@ def sr_arg(text):
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--model_path")
-    p.add_argument("--audio_path", default=None, help="one .wav file, or '-' to read a wav from stdin")
-    p.add_argument("--audio_folder", default=None, help="directory of .wav/.WAV files (when --audio_path is absent)")
+    p.add_argument("--audio_path", default=None, help="one audio file, or '-' to read one from stdin")
+    p.add_argument("--audio_folder", default=None, help="directory of .wav/.WAV files, or of --audio_ext's (when --audio_path is absent)")
     p.add_argument("--csv_save_path")
     p.add_argument("--device", default="cuda", help="'cuda' (an MI355X is required; 'cpu' raises)")
     p.add_argument("--device_ids", type=int, nargs="+", default=[0, ], help="GPU indices, one model replica each")
@@ -54,7 +59,16 @@ def build_parser():
                         "absent: the mono mix")
     p.add_argument("--sr", default=None, type=sr_arg,
                    help="resample every recording to this rate (Hz) on the GPU before segmenting; absent: the native rate")
+    p.add_argument("--audio_ext", default=None, nargs="+", metavar="EXT",
+                   help="folder mode: the file extensions to look for, each as *.ext then *.EXT, in this order; absent: wav")
     return p
+
+
+def folder_patterns(audio_ext=None):
+    """The glob patterns of folder mode, in the order their files are segmented."""
+    if audio_ext is None:
+        return ["*.wav", "*.WAV"]
+    return [pattern for ext in audio_ext for pattern in ("*." + ext.lstrip(".").lower(), "*." + ext.lstrip(".").upper())]
 
 
 def write_csv(columns, rows, dest):
@@ -79,9 +93,9 @@ def table(results, names=None, all_channels=False):
 
 
 def stdin_wav(sr=None, channel_id=None):
-    """The wav on stdin, decoded on the host -> (audio, rate): the mono mix, or with `channel_id` the channels kept apart and the
+    """The audio file on stdin, decoded on the host -> (audio, rate): the mono mix, or with `channel_id` the channels kept apart and the
     reference's selection (`audio[channel_id]` of a 2-D array; "all" keeps them).  `sr`: resampled to it on the GPU, 1-D or planes."""
-    audio, native = load_wav(io.BytesIO(sys.stdin.buffer.read()), mono=channel_id is None)
+    audio, native = load_audio(io.BytesIO(sys.stdin.buffer.read()), mono=channel_id is None)
     if audio.ndim == 2 and channel_id != "all":
         audio = audio[channel_id]
     if sr is None or sr == native or not audio.shape[-1]:
@@ -103,7 +117,7 @@ def main(argv=None):
     rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
-        paths = glob.glob(args.audio_folder + "/*.wav") + glob.glob(args.audio_folder + "/*.WAV")
+        paths = [p for pattern in folder_patterns(args.audio_ext) for p in glob.glob(args.audio_folder + "/" + pattern)]
         # same rows as the reference's serial loop, but the windows of many files share the engine's decode slots; files
         # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
         # a large folder needs no more memory than a small one

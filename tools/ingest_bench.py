@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """A/B of the audio ingest on one MI355X: host decode (wavio.load_wav, numpy, one thread) against the device decode
-(wseg_pcm_to_mono_f32) and the folder pipeline on top of it (SegmenterBase.segment_files).
+(wseg_pcm_to_mono_f32 / wseg_samples_to_mono_f32) and the folder pipeline on top of it (SegmenterBase.segment_files).
 
     python tools/ingest_bench.py [--files 64] [--seconds 60] [--out profiles/ingest_ab.txt]
     python tools/ingest_bench.py --planar [--out profiles/ingest_planar_ab.txt]
     python tools/ingest_bench.py --resample [--out profiles/resample_planar_ab.txt]
     python tools/ingest_bench.py --stream [--out profiles/resample_stream_ab.txt]
+    python tools/ingest_bench.py --encodings [--out profiles/ingest_encodings_ab.txt]
 
 For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
 `--seconds` seconds into a temporary directory and reports
@@ -22,6 +23,14 @@ the same bytes (random, generated on the device), for PLANAR_CASES x 60 s and 60
 bytes) over HIP-event time — the planar kernel writes `channels` times the mono kernel's output, so rates compare, times do not.
 A repetition is a train of back-to-back launches (as many as move about 2 GB, at least one) between two events; one warm-up
 train, then three repetitions of each kernel, alternating; all three rates are printed, the median is the figure.
+
+--encodings measures the decode kernels alone on the encodings of wseg_sample_encoding that RIFF/WAVE PCM does not carry, each
+beside its sibling of the same width (ENCODING_PAIRS: s16be | s16, s24be | s24, f64be | f64, u-law | u8), through
+wseg_samples_to_mono_f32 with one and two channels and wseg_samples_to_planar_f32 with two, on the same random bytes (600 s at
+48 kHz).  A repetition is a train of back-to-back launches that moves about 400 GB (a tenth of a second or more) between two HIP
+events; one warm-up train of each encoding, then five repetitions, the two encodings alternating; all five rates are printed, the
+median is the figure.  Bytes in and out are equal within a pair, so
+the rates compare directly; a line says whether the new encoding's median lies inside the spread of its sibling's own repetitions.
 
 --resample measures the two resamplers alone, no engine, by the same protocol: wseg_resample_planar_f32 (one launch for all planes)
 beside the loop it replaces (one wseg_resample_f32 launch per plane, back to back) on the same planes (seeded normal samples,
@@ -142,6 +151,55 @@ def planar_section(lib, emit):
                  % (fmt, channels, sr, seconds, ratios[(fmt, channels, seconds)], spread))
             del raw, planes, mono
     return ratios
+
+
+ENCODING_PAIRS = (("s16be", 7, "s16", 1, 2), ("s24be", 8, "s24", 2, 3), ("f64be", 11, "f64", 5, 8), ("ulaw", 12, "u8", 0, 1))
+
+
+def encodings_section(lib, emit, seconds=600, sr=48000, reps=5):
+    import torch
+    from whisperseg_amd import _lib
+    stream = lambda: _lib.stream_ptr()
+    n = seconds * sr
+    for new, new_code, old, old_code, width in ENCODING_PAIRS:
+        for kernel, channels in (("mono", 1), ("mono", 2), ("planar", 2)):
+            nbytes = n * channels * width
+            raw = torch.randint(0, 256, (-(-nbytes // 16) * 16,), dtype=torch.uint8, device="cuda")
+            out = torch.empty((channels if kernel == "planar" else 1, n), dtype=torch.float32, device="cuda")
+            moved = nbytes + 4 * out.numel()
+            iters = max(1, int(4e11 // moved))
+
+            def call(code):
+                if kernel == "mono":
+                    _lib.check(lib.wseg_samples_to_mono_f32(raw.data_ptr(), n, channels, code, out.data_ptr(), stream()))
+                else:
+                    _lib.check(lib.wseg_samples_to_planar_f32(raw.data_ptr(), n, channels, code, 0, channels, out.data_ptr(), n, stream()))
+
+            def train(code):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    call(code)
+                b.record()
+                b.synchronize()
+                return moved * iters / (a.elapsed_time(b) * 1e-3) / 1e9
+
+            codes = {new: new_code, old: old_code}
+            rates = {new: [], old: []}
+            for name in codes:
+                train(codes[name])
+            for _ in range(reps):
+                for name in codes:
+                    rates[name].append(train(codes[name]))
+            med = {k: statistics.median(v) for k, v in rates.items()}
+            for name in (new, old):
+                emit("%-6s x%d %-6s %-6s %8.1f GB/s  (%s; %d launches per repetition, %.1f MB in + %.1f MB out per launch)"
+                     % (kernel, channels, "%d Hz" % sr, name, med[name], " ".join("%.1f" % r for r in rates[name]), iters, nbytes / 1e6,
+                        (moved - nbytes) / 1e6))
+            inside = min(rates[old]) <= med[new] <= max(rates[old])
+            emit("%-6s x%d %s / %s GB/s = %.3f  (%s median %s the spread of %s's repetitions, %.1f .. %.1f GB/s)"
+                 % (kernel, channels, new, old, med[new] / med[old], new, "inside" if inside else "OUTSIDE", old, min(rates[old]), max(rates[old])))
+            del raw, out
 
 
 RESAMPLE_CASES = ((44100, 16000), (48000, 16000), (96000, 16000), (16000, 44100), (250000, 44100))
@@ -300,6 +358,8 @@ def main(argv=None):
                     help="only the kernels: wseg_resample_planar_f32 beside one wseg_resample_f32 launch per plane")
     ap.add_argument("--stream", action="store_true",
                     help="only the file path at a target rate: load_wav_device(sr=) and FilePipeline(sr=) on a file that goes through in pieces")
+    ap.add_argument("--encodings", action="store_true",
+                    help="only the kernels: every new sample encoding beside its sibling of the same width")
     ap.add_argument("--piece-mb", type=int, default=4, help="--stream: MiB per piece of the file")
     args = ap.parse_args(argv)
     if args.stream:
@@ -307,6 +367,10 @@ def main(argv=None):
                                    "HIP events and wall time per call in ms, median of five repetitions after one warm-up, the two entry "
                                    "points alternating (all five in brackets); peak rise of torch.cuda.max_memory_allocated over a call",
                              lambda lib, emit: stream_section(lib, emit, piece_mb=args.piece_mb))
+    if args.encodings:
+        return _tool_section(args, "sample encodings A/B: wseg_samples_to_mono_f32 / wseg_samples_to_planar_f32 on a new encoding beside its "
+                                   "sibling of the same width on the same bytes, HIP events, GB/s = (bytes in + bytes out) / time, median of "
+                                   "five repetitions after one warm-up, the two alternating (all five in brackets)", encodings_section)
     if args.resample:
         return _tool_section(args, "resample A/B: wseg_resample_planar_f32 (one launch, all planes) beside a loop of wseg_resample_f32 launches "
                                    "over the same planes and taps, HIP events, ms per call of all planes, median of three repetitions after one "

@@ -56,6 +56,22 @@ def slaney_mel_filters(sr, n_fft, min_frequency, max_frequency, n_mels=N_MELS):
     return fb
 
 
+def get_sampling_rate(audio_file):
+    """Native sampling rate of an audio file (reference audio_utils.py:19-23), from the header scan of wavio.scan_audio alone:
+    no sample is read."""
+    from .wavio import scan_audio
+    with open(audio_file, "rb") as f:
+        return scan_audio(f).sr
+
+
+def get_audio_duration(audio_file):
+    """Duration in seconds (reference audio_utils.py:25-30: frames / rate), from the header scan alone."""
+    from .wavio import scan_audio
+    with open(audio_file, "rb") as f:
+        info = scan_audio(f)
+    return info.n_frames / info.sr
+
+
 class _DeviceTables:
     """Device-resident tables for one (n_fft, hop, filterbank) configuration."""
 

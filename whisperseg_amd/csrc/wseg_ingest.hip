@@ -1,8 +1,12 @@
-// WAVE sample decode (audio ingest): interleaved little-endian PCM frames exactly as they sit in a RIFF data
-// chunk -> float32 mono.  Replaces the decoding half of `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61;
-// evaluate.py:58), i.e. what whisperseg_amd/wavio.py::load_wav does with numpy on the host, and produces the same float32 bits:
+// Audio sample decode (audio ingest): interleaved frames exactly as they sit in the sample chunk of a WAVE /
+// RF64, AIFF / AIFF-C or AU file -> float32 mono.  Replaces the decoding half of `librosa.load(path, sr=None)` (reference
+// scripts/segment.py:48,61; evaluate.py:58), i.e. what whisperseg_amd/wavio.py::load_wav / load_audio do with numpy on the host,
+// and produces the same float32 bits:
 //   u8 (x - 128) / 128 | s16 x / 2^15 | s24 sign-extended / 2^23 | s32 one int -> float32 rounding, then the exact scale 2^-31
 //   f32 copied | f64 one round-to-nearest-even conversion (beyond the float32 range: +-inf)
+//   wseg_sample_encoding 6..13 (whisperseg_amd/wavio.py::load_audio): s8 x / 128 | s16be / s24be / s32be / f32be / f64be the bytes
+//   swapped in registers, then as their little-endian siblings | u-law / A-law the G.711 expansion to int16 (integer arithmetic in
+//   registers, no table), then x / 2^15
 //   channels > 1: numpy's mean(axis=1) of the float32 samples of a frame — the sum starts from +0 (so a frame of -0.0 samples
 //   gives +0.0), runs left to right for fewer than 8 channels and in numpy's pairwise order from 8 channels on (eight strided
 //   partial sums, combined as a tree, the last channels % 8 samples added one by one), then ONE division by float(channels).
@@ -15,10 +19,24 @@
 
 namespace wseg {
 
-constexpr int kBytes[6] = {1, 2, 3, 4, 4, 8};      // bytes per sample of wseg_pcm_format
+constexpr int kBytes[14] = {1, 2, 3, 4, 4, 8, 1, 2, 3, 4, 4, 8, 1, 1};      // bytes per sample of wseg_sample_encoding
 
-// Sample at byte `b` (a multiple of the sample size for u8 / s16, of 4 for s32 / f32 / f64, any for s24) of the dword array `w`.
-// With a register array and a compile-time `b` this is shifts only.
+// G.711 code -> int16 (ITU-T G.711's expansion, as libsndfile and CPython's audioop tabulate it).
+__device__ __forceinline__ int ulaw_to_s16(uint32_t b) {
+  const uint32_t u = ~b & 0xffu;
+  const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u & 0x70u) >> 4));
+  return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ int alaw_to_s16(uint32_t b) {
+  const uint32_t a = (b ^ 0x55u) & 0xffu;
+  const uint32_t s = (a & 0x70u) >> 4;
+  uint32_t t = (a & 15u) << 4;
+  t = s ? (t + 0x108u) << (s - 1) : t + 8u;
+  return (a & 0x80u) ? (int)t : -(int)t;
+}
+
+// Sample at byte `b` (a multiple of the sample size for the 1- and 2-byte encodings, of 4 for the 4- and 8-byte ones, any for
+// s24 / s24be) of the dword array `w`.  With a register array and a compile-time `b` this is shifts only.
 template <int FMT, class W>
 __device__ __forceinline__ float sample_at(const W& w, long long b) {
   const long long d = b >> 2;
@@ -35,8 +53,28 @@ __device__ __forceinline__ float sample_at(const W& w, long long b) {
     return (float)(int32_t)w[d] * 4.656612873077393e-10f;      // 2^-31: exact, no result is subnormal
   } else if constexpr (FMT == WSEG_PCM_F32) {
     return __uint_as_float(w[d]);
-  } else {
+  } else if constexpr (FMT == WSEG_PCM_F64) {
     return (float)__longlong_as_double((long long)(((unsigned long long)w[d + 1] << 32) | w[d]));
+  } else if constexpr (FMT == WSEG_ENC_S8) {
+    return (float)(int8_t)(w[d] >> sh) / 128.0f;
+  } else if constexpr (FMT == WSEG_ENC_S16BE) {
+    const uint32_t v = w[d] >> sh;
+    return (float)(int16_t)(((v & 0xffu) << 8) | ((v >> 8) & 0xffu)) / 32768.0f;
+  } else if constexpr (FMT == WSEG_ENC_S24BE) {
+    uint32_t v = w[d] >> sh;
+    if (sh > 8) v |= w[d + 1] << (32 - sh);        // as for s24: the sample ends in the next dword
+    return (float)((int32_t)__builtin_bswap32(v) >> 8) / 8388608.0f;      // the swap puts the three bytes on top: the shift sign-extends
+  } else if constexpr (FMT == WSEG_ENC_S32BE) {
+    return (float)(int32_t)__builtin_bswap32(w[d]) * 4.656612873077393e-10f;
+  } else if constexpr (FMT == WSEG_ENC_F32BE) {
+    return __uint_as_float(__builtin_bswap32(w[d]));
+  } else if constexpr (FMT == WSEG_ENC_F64BE) {
+    return (float)__longlong_as_double((long long)(((unsigned long long)__builtin_bswap32(w[d]) << 32) | __builtin_bswap32(w[d + 1])));
+  } else if constexpr (FMT == WSEG_ENC_ULAW) {
+    return (float)ulaw_to_s16(w[d] >> sh) / 32768.0f;
+  } else {
+    static_assert(FMT == WSEG_ENC_ALAW, "unknown sample encoding");
+    return (float)alaw_to_s16(w[d] >> sh) / 32768.0f;
   }
 }
 
@@ -240,48 +278,50 @@ __global__ __launch_bounds__(256) void pcm_to_planar_kernel(const void* __restri
 
 using namespace wseg;
 
-extern "C" int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream_) {
+// The first checks of every entry point; the format / encoding check follows them and samples_to_mono / samples_to_planar do the rest.
+static bool head_ok(const char* fn, const void* raw, const float* out, int32_t channels) {
+  if (!raw || ((uintptr_t)raw & 15)) { set_error("%s: raw must be a 16-byte aligned device pointer", fn); return false; }
+  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return false; }
+  if (channels < 1 || channels > 64) { set_error("%s: channels must be 1..64 (got %d)", fn, channels); return false; }
+  return true;
+}
+
+// The remaining checks and the launch of wseg_pcm_to_mono_f32 / wseg_samples_to_mono_f32 (`fn`: the entry point's name for the
+// messages; the caller has checked the code, 0..13).
+static int samples_to_mono(const char* fn, const void* raw, int64_t n_frames, int32_t channels, int32_t code, float* out, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  if (!raw || ((uintptr_t)raw & 15)) { set_error("wseg_pcm_to_mono_f32: raw must be a 16-byte aligned device pointer"); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("wseg_pcm_to_mono_f32: out must be a float32 device pointer"); return WSEG_ERR_INVALID; }
-  if (channels < 1 || channels > 64) { set_error("wseg_pcm_to_mono_f32: channels must be 1..64 (got %d)", channels); return WSEG_ERR_INVALID; }
-  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_mono_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
-  if (n_frames < 0) { set_error("wseg_pcm_to_mono_f32: n_frames is negative"); return WSEG_ERR_INVALID; }
+  if (n_frames < 0) { set_error("%s: n_frames is negative", fn); return WSEG_ERR_INVALID; }
   if (n_frames == 0) return WSEG_OK;
   long long blocks = ((n_frames >> 2) + 255) / 256;
   if (blocks < 1) blocks = 1;                      // fewer than four frames: the tail lane alone
   if (blocks > 8192) blocks = 8192;                // 32 workgroups per CU; longer streams take the grid stride
   const dim3 grid((unsigned)blocks);
   const int out_aligned = ((uintptr_t)out & 15) == 0;
-  switch (format) {
-    case WSEG_PCM_U8: launch_pcm<WSEG_PCM_U8>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-    case WSEG_PCM_S16: launch_pcm<WSEG_PCM_S16>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-    case WSEG_PCM_S24: launch_pcm<WSEG_PCM_S24>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-    case WSEG_PCM_S32: launch_pcm<WSEG_PCM_S32>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-    case WSEG_PCM_F32: launch_pcm<WSEG_PCM_F32>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-    default: launch_pcm<WSEG_PCM_F64>(channels, grid, s, raw, n_frames, out, out_aligned); break;
+#define WSEG_MONO(F) case F: launch_pcm<F>(channels, grid, s, raw, n_frames, out, out_aligned); break
+  switch (code) {
+    WSEG_MONO(WSEG_PCM_U8); WSEG_MONO(WSEG_PCM_S16); WSEG_MONO(WSEG_PCM_S24); WSEG_MONO(WSEG_PCM_S32); WSEG_MONO(WSEG_PCM_F32);
+    WSEG_MONO(WSEG_PCM_F64); WSEG_MONO(WSEG_ENC_S8); WSEG_MONO(WSEG_ENC_S16BE); WSEG_MONO(WSEG_ENC_S24BE); WSEG_MONO(WSEG_ENC_S32BE);
+    WSEG_MONO(WSEG_ENC_F32BE); WSEG_MONO(WSEG_ENC_F64BE); WSEG_MONO(WSEG_ENC_ULAW);
+    default: launch_pcm<WSEG_ENC_ALAW>(channels, grid, s, raw, n_frames, out, out_aligned); break;
   }
+#undef WSEG_MONO
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }
 
-extern "C" int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, int32_t first_channel,
-                                      int32_t n_out_channels, float* out, int64_t plane_stride, void* stream_) {
+static int samples_to_planar(const char* fn, const void* raw, int64_t n_frames, int32_t channels, int32_t code, int32_t first_channel,
+                             int32_t n_out_channels, float* out, int64_t plane_stride, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
-  if (!raw || ((uintptr_t)raw & 15)) { set_error("wseg_pcm_to_planar_f32: raw must be a 16-byte aligned device pointer"); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("wseg_pcm_to_planar_f32: out must be a float32 device pointer"); return WSEG_ERR_INVALID; }
-  if (channels < 1 || channels > 64) { set_error("wseg_pcm_to_planar_f32: channels must be 1..64 (got %d)", channels); return WSEG_ERR_INVALID; }
-  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_planar_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
-  if (n_frames < 0) { set_error("wseg_pcm_to_planar_f32: n_frames is negative"); return WSEG_ERR_INVALID; }
+  if (n_frames < 0) { set_error("%s: n_frames is negative", fn); return WSEG_ERR_INVALID; }
   if (first_channel < 0 || first_channel >= channels) {
-    set_error("wseg_pcm_to_planar_f32: first_channel must be 0..%d (got %d)", channels - 1, first_channel); return WSEG_ERR_INVALID;
+    set_error("%s: first_channel must be 0..%d (got %d)", fn, channels - 1, first_channel); return WSEG_ERR_INVALID;
   }
   if (n_out_channels < 1 || n_out_channels > channels - first_channel) {
-    set_error("wseg_pcm_to_planar_f32: n_out_channels must be 1..%d behind channel %d (got %d)", channels - first_channel, first_channel, n_out_channels);
+    set_error("%s: n_out_channels must be 1..%d behind channel %d (got %d)", fn, channels - first_channel, first_channel, n_out_channels);
     return WSEG_ERR_INVALID;
   }
   if (n_out_channels > 1 && plane_stride < n_frames) {
-    set_error("wseg_pcm_to_planar_f32: plane_stride (%lld) is shorter than the %lld frames of a plane", (long long)plane_stride, (long long)n_frames);
+    set_error("%s: plane_stride (%lld) is shorter than the %lld frames of a plane", fn, (long long)plane_stride, (long long)n_frames);
     return WSEG_ERR_INVALID;
   }
   if (n_frames == 0) return WSEG_OK;
@@ -289,17 +329,44 @@ extern "C" int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t
   if (blocks > kPlanarGridCap) blocks = kPlanarGridCap;
   const dim3 grid((unsigned)blocks);
   const long long stride = n_out_channels > 1 ? plane_stride : 0;
-#define WSEG_PLANAR(F) hipLaunchKernelGGL((pcm_to_planar_kernel<F>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels, \
-                                          (int)first_channel, (int)n_out_channels, out, stride)
-  switch (format) {
-    case WSEG_PCM_U8: WSEG_PLANAR(WSEG_PCM_U8); break;
-    case WSEG_PCM_S16: WSEG_PLANAR(WSEG_PCM_S16); break;
-    case WSEG_PCM_S24: WSEG_PLANAR(WSEG_PCM_S24); break;
-    case WSEG_PCM_S32: WSEG_PLANAR(WSEG_PCM_S32); break;
-    case WSEG_PCM_F32: WSEG_PLANAR(WSEG_PCM_F32); break;
-    default: WSEG_PLANAR(WSEG_PCM_F64); break;
+#define WSEG_PLANAR(F) case F: hipLaunchKernelGGL((pcm_to_planar_kernel<F>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels, \
+                                                  (int)first_channel, (int)n_out_channels, out, stride); break
+  switch (code) {
+    WSEG_PLANAR(WSEG_PCM_U8); WSEG_PLANAR(WSEG_PCM_S16); WSEG_PLANAR(WSEG_PCM_S24); WSEG_PLANAR(WSEG_PCM_S32); WSEG_PLANAR(WSEG_PCM_F32);
+    WSEG_PLANAR(WSEG_PCM_F64); WSEG_PLANAR(WSEG_ENC_S8); WSEG_PLANAR(WSEG_ENC_S16BE); WSEG_PLANAR(WSEG_ENC_S24BE);
+    WSEG_PLANAR(WSEG_ENC_S32BE); WSEG_PLANAR(WSEG_ENC_F32BE); WSEG_PLANAR(WSEG_ENC_F64BE); WSEG_PLANAR(WSEG_ENC_ULAW);
+    default: hipLaunchKernelGGL((pcm_to_planar_kernel<WSEG_ENC_ALAW>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels,
+                                (int)first_channel, (int)n_out_channels, out, stride); break;
   }
 #undef WSEG_PLANAR
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
+}
+
+extern "C" int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream) {
+  if (!head_ok("wseg_pcm_to_mono_f32", raw, out, channels)) return WSEG_ERR_INVALID;
+  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_mono_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  return samples_to_mono("wseg_pcm_to_mono_f32", raw, n_frames, channels, format, out, stream);
+}
+
+extern "C" int wseg_samples_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding, float* out, void* stream) {
+  if (!head_ok("wseg_samples_to_mono_f32", raw, out, channels)) return WSEG_ERR_INVALID;
+  if (encoding < WSEG_PCM_U8 || encoding > WSEG_ENC_ALAW) { set_error("wseg_samples_to_mono_f32: unknown encoding %d", encoding); return WSEG_ERR_INVALID; }
+  return samples_to_mono("wseg_samples_to_mono_f32", raw, n_frames, channels, encoding, out, stream);
+}
+
+extern "C" int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, int32_t first_channel,
+                                      int32_t n_out_channels, float* out, int64_t plane_stride, void* stream) {
+  if (!head_ok("wseg_pcm_to_planar_f32", raw, out, channels)) return WSEG_ERR_INVALID;
+  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_planar_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  return samples_to_planar("wseg_pcm_to_planar_f32", raw, n_frames, channels, format, first_channel, n_out_channels, out, plane_stride, stream);
+}
+
+extern "C" int wseg_samples_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding, int32_t first_channel,
+                                          int32_t n_out_channels, float* out, int64_t plane_stride, void* stream) {
+  if (!head_ok("wseg_samples_to_planar_f32", raw, out, channels)) return WSEG_ERR_INVALID;
+  if (encoding < WSEG_PCM_U8 || encoding > WSEG_ENC_ALAW) {
+    set_error("wseg_samples_to_planar_f32: unknown encoding %d", encoding); return WSEG_ERR_INVALID;
+  }
+  return samples_to_planar("wseg_samples_to_planar_f32", raw, n_frames, channels, encoding, first_channel, n_out_channels, out, plane_stride, stream);
 }

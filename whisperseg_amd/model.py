@@ -375,13 +375,13 @@ class SegmenterBase:
         return self.segment_batch([audio] if audio.ndim == 1 else list(audio), sr, **segment_kwargs)
 
     def segment_files(self, paths, channel_id=None, sr=None, **segment_batch_kwargs):
-        """segment_batch((load_wav(p) for p in paths), ...) element for element, without the host decode and without the
+        """segment_batch((load_audio(p) for p in paths), ...) element for element (WAVE / RF64, AIFF / AIFF-C and AU files), without the host decode and without the
         serial file reads: one reader thread fills a pool of two pinned buffers (self.ingest_buffer_bytes each at most; larger
         files go through in pieces) while this thread copies filled buffers to the device, decodes the samples there
-        (wseg_pcm_to_mono_f32: load_wav's float32 bits) and runs the front-end and the pooled decode of segment_batch on the
+        (wseg_samples_to_mono_f32: load_audio's float32 bits) and runs the front-end and the pooled decode of segment_batch on the
         resident PCM.  Errors of the reader are raised here with the file's name; the thread is joined on every way out.
         `channel_id` (the reference's, segment_service.py:73-80): an int -> a list of dicts, channel `channel_id` of every
-        multi-channel file and the samples of every one-channel file (only that plane is decoded: wseg_pcm_to_planar_f32);
+        multi-channel file and the samples of every one-channel file (only that plane is decoded: wseg_samples_to_planar_f32);
         "all" -> per file a list with one dict per channel, the rows of all channels of all files pooled through ONE
         segment_batch in file-then-channel order.  Per-recording parameter lists stay per FILE: a file's value applies to each
         of its channels.

@@ -1,10 +1,18 @@
-"""Minimal RIFF/WAVE reader standing in for `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61;
-librosa/soundfile are not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono — or, with
-mono=False, kept apart as `librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80,
-scripts/backend.py:279-282, demo.py:76-78).
-PCM 8/16/24/32-bit, IEEE float 32/64 and WAVE_FORMAT_EXTENSIBLE are handled.  load_wav keeps the native rate; the device path
-(load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU (whisperseg_amd.resample), all planes of a file at once and
-piece by piece as the file is read (StreamResampler)."""
+"""Audio file reader standing in for `librosa.load(path, sr=None)` (reference scripts/segment.py:48,61; librosa/soundfile are
+not in the image): native sampling rate, float32 in [-1, 1), channels averaged to mono — or, with mono=False, kept apart as
+`librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80, scripts/backend.py:279-282,
+demo.py:76-78).
+Containers (sniffed from the first 12 bytes; load_audio / scan_audio / read_audio_raw):
+  RIFF/WAVE, RF64, BW64 — PCM 8/16/24/32-bit, IEEE float 32/64, G.711 A-law / u-law (tags 6 / 7), WAVE_FORMAT_EXTENSIBLE; an
+      RF64 / BW64 `ds64` chunk supplies the size of a `data` chunk whose own size field is 0xFFFFFFFF (load_wav / scan_wav /
+      read_wav_raw are the WAVE-only functions the others call)
+  AIFF / AIFF-C — big-endian PCM of 1..32 bits (8-bit signed); compression NONE / twos / sowt / `raw ` / fl32 / fl64 / ulaw / alaw
+  AU (.snd) — u-law, A-law, 8/16/24/32-bit linear, float 32/64
+Wave64, FLAC and lossy codecs are not read.  Integer samples are divided by 2^(bits-1) of their container width and G.711 codes go
+through the standard's int16 expansion, which is how libsndfile (behind librosa) produces its floats: equality with it is by
+construction, not pinned by a test (soundfile is not in the image).
+load_wav / load_audio keep the native rate; the device path (load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU
+(whisperseg_amd.resample), all planes of a file at once and piece by piece as the file is read (StreamResampler)."""
 import collections
 import io
 import os
@@ -15,82 +23,76 @@ import threading
 import numpy as np
 
 
-def _read_chunks(f):
-    header = f.read(12)
-    if len(header) < 12 or header[:4] not in (b"RIFF", b"RF64") or header[8:12] != b"WAVE":
-        raise ValueError("not a RIFF/WAVE file")
-    while True:
-        head = f.read(8)
-        if len(head) < 8:
-            return
-        cid, size = head[:4], struct.unpack("<I", head[4:])[0]
-        data = f.read(size)
-        if size % 2:
-            f.read(1)
-        yield cid, data
-
-
-def load_wav(path_or_file, mono=True):
-    """-> (float32 mono ndarray, sampling_rate).  mono=False: the channels kept apart, float32 [channels, n_frames]
-    (C-contiguous) for a file of two or more channels and [n_frames] for a one-channel file; every sample converted as for the
-    mono mix, before its mean."""
-    f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) else path_or_file
-    try:
-        if not hasattr(f, "read"):
-            f = io.BytesIO(f)
-        fmt, raw = None, None
-        for cid, data in _read_chunks(f):
-            if cid == b"fmt ":
-                tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", data[:16])
-                if tag == 0xFFFE and len(data) >= 26:
-                    tag = struct.unpack("<H", data[24:26])[0]
-                fmt = (tag, ch, sr, bits)
-            elif cid == b"data":
-                raw = data
-        if fmt is None or raw is None:
-            raise ValueError("missing fmt or data chunk")
-    finally:
-        if isinstance(path_or_file, (str, bytes)):
-            f.close()
-    tag, ch, sr, bits = fmt
-    if tag == 1:
-        if bits == 8:
-            x = (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0
-        elif bits == 16:
-            x = np.frombuffer(raw[: len(raw) // 2 * 2], "<i2").astype(np.float32) / 32768.0
-        elif bits == 24:
-            b = np.frombuffer(raw[: len(raw) // 3 * 3], np.uint8).reshape(-1, 3).astype(np.int32)
-            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-            v = np.where(v >= 1 << 23, v - (1 << 24), v)
-            x = v.astype(np.float32) / float(1 << 23)
-        elif bits == 32:
-            x = (np.frombuffer(raw[: len(raw) // 4 * 4], "<i4").astype(np.float64) / float(1 << 31)).astype(np.float32)
-        else:
-            raise ValueError(f"unsupported PCM width {bits}")
-    elif tag == 3:
-        x = np.frombuffer(raw, "<f4" if bits == 32 else "<f8").astype(np.float32)
-    else:
-        raise ValueError(f"unsupported WAVE format tag {tag}")
-    if ch > 1 and not mono:
-        x = x[: len(x) // ch * ch].reshape(-1, ch).T
-    elif ch > 1:
-        x = x[: len(x) // ch * ch].reshape(-1, ch).mean(axis=1).astype(np.float32)
-    return np.ascontiguousarray(x, dtype=np.float32), int(sr)
-
-
-# ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
-# load_wav above is the arithmetic's definition; what follows moves it to the device: read_wav_raw hands out the data chunk's
-# bytes untouched, libwseg's wseg_pcm_to_mono_f32 widens and averages them with load_wav's float32 bits, and
-# wseg_pcm_to_planar_f32 widens the channels one asks for into planes (load_wav(mono=False)'s rows).
-PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)        # wseg_pcm_format (include/wseg.h)
-BYTES_PER_SAMPLE = (1, 2, 3, 4, 4, 8)
+# wseg_sample_encoding (include/wseg.h); 0..5 are wseg_pcm_format
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)
+ENC_S8, ENC_S16BE, ENC_S24BE, ENC_S32BE, ENC_F32BE, ENC_F64BE, ENC_ULAW, ENC_ALAW = range(6, 14)
+BYTES_PER_SAMPLE = (1, 2, 3, 4, 4, 8, 1, 2, 3, 4, 4, 8, 1, 1)
 MAX_CHANNELS = 64
 STAGING_BYTES = 256 << 20        # one pinned staging buffer; a longer data chunk goes through in pieces
-PLANAR_TILE_FRAMES = 1024        # kPlanarTile of csrc/wseg_ingest.hip: the frames a workgroup of wseg_pcm_to_planar_f32 stages at a time
+PLANAR_TILE_FRAMES = 1024        # kPlanarTile of csrc/wseg_ingest.hip: the frames a workgroup of wseg_samples_to_planar_f32 stages at a time
 PLANAR_GRID_CAP = 2048           # kPlanarGridCap there: with more tiles than this the workgroups take a grid stride
 
 WavRaw = collections.namedtuple("WavRaw", "data format channels sr n_frames")
 WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames frame_bytes offset")
+
+WAVE_IDS = (b"RIFF", b"RF64", b"BW64")
+
+
+def _g711_tables():
+    """The 256 int16 values of the u-law and A-law codes (ITU-T G.711's expansion; csrc/wseg_ingest.hip does the same arithmetic
+    in registers)."""
+    b = np.arange(256, dtype=np.int32)
+    u = ~b & 0xFF
+    t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4)
+    ulaw = np.where(u & 0x80, 0x84 - t, t - 0x84)
+    a = b ^ 0x55
+    seg = (a & 0x70) >> 4
+    t = (a & 15) << 4
+    t = np.where(seg > 0, (t + 0x108) << np.maximum(seg - 1, 0), t + 8)
+    alaw = np.where(a & 0x80, t, -t)
+    return ulaw.astype(np.int16), alaw.astype(np.int16)
+
+
+ULAW_TO_S16, ALAW_TO_S16 = _g711_tables()
+
+
+def _s24(raw, order):
+    b = np.frombuffer(raw[: len(raw) // 3 * 3], np.uint8).reshape(-1, 3).astype(np.int32)
+    lo, mid, hi = order
+    v = b[:, lo] | (b[:, mid] << 8) | (b[:, hi] << 16)
+    v = np.where(v >= 1 << 23, v - (1 << 24), v)
+    return v.astype(np.float32) / float(1 << 23)
+
+
+def _decode(raw, code):
+    """Sample bytes of a wseg_sample_encoding -> float32 samples in file order: the definition of the arithmetic (bytes behind
+    the last whole integer sample are dropped; float data must end with a sample)."""
+    if code == PCM_U8:
+        return (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0
+    if code == ENC_S8:
+        return np.frombuffer(raw, np.int8).astype(np.float32) / 128.0
+    if code in (PCM_S16, ENC_S16BE):
+        return np.frombuffer(raw[: len(raw) // 2 * 2], "<i2" if code == PCM_S16 else ">i2").astype(np.float32) / 32768.0
+    if code in (PCM_S24, ENC_S24BE):
+        return _s24(raw, (0, 1, 2) if code == PCM_S24 else (2, 1, 0))
+    if code in (PCM_S32, ENC_S32BE):
+        v = np.frombuffer(raw[: len(raw) // 4 * 4], "<i4" if code == PCM_S32 else ">i4")
+        return (v.astype(np.float64) / float(1 << 31)).astype(np.float32)
+    if code in (PCM_F32, PCM_F64, ENC_F32BE, ENC_F64BE):
+        return np.frombuffer(raw, {PCM_F32: "<f4", PCM_F64: "<f8", ENC_F32BE: ">f4", ENC_F64BE: ">f8"}[code]).astype(np.float32)
+    if code in (ENC_ULAW, ENC_ALAW):
+        table = ULAW_TO_S16 if code == ENC_ULAW else ALAW_TO_S16
+        return table[np.frombuffer(raw, np.uint8)].astype(np.float32) / 32768.0
+    raise ValueError(f"unknown sample encoding {code}")
+
+
+def _channels(x, ch, mono):
+    """Interleaved samples -> the mono mix (numpy's float32 mean over a frame), or with mono=False the rows of the channels."""
+    if ch > 1 and not mono:
+        x = x[: len(x) // ch * ch].reshape(-1, ch).T
+    elif ch > 1:
+        x = x[: len(x) // ch * ch].reshape(-1, ch).mean(axis=1).astype(np.float32)
+    return np.ascontiguousarray(x, dtype=np.float32)
 
 
 def _pcm_format(tag, bits):
@@ -101,30 +103,96 @@ def _pcm_format(tag, bits):
         return {8: PCM_U8, 16: PCM_S16, 24: PCM_S24, 32: PCM_S32}[bits]
     if tag == 3:
         return PCM_F32 if bits == 32 else PCM_F64
+    if tag in (6, 7):
+        if bits != 8:
+            raise ValueError(f"unsupported G.711 width {bits}")
+        return ENC_ALAW if tag == 6 else ENC_ULAW
     raise ValueError(f"unsupported WAVE format tag {tag}")
 
 
+def _fmt_chunk(body):
+    tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+    if tag == 0xFFFE and len(body) >= 26:
+        tag = struct.unpack("<H", body[24:26])[0]
+    return tag, ch, sr, bits
+
+
+def _ds64_data_size(body):
+    """The `data` chunk's size of an RF64 / BW64 `ds64` chunk (riffSize u64, dataSize u64, sampleCount u64, tableLength u32,
+    table...; little-endian), None when the chunk is too short to hold one."""
+    return struct.unpack("<Q", body[8:16])[0] if len(body) >= 16 else None
+
+
+def _read_chunks(f):
+    header = f.read(12)
+    if len(header) < 12 or header[:4] not in WAVE_IDS or header[8:12] != b"WAVE":
+        raise ValueError("not a RIFF/WAVE file")
+    data_size = None
+    while True:
+        head = f.read(8)
+        if len(head) < 8:
+            return
+        cid, size = head[:4], struct.unpack("<I", head[4:])[0]
+        if cid == b"data" and size == 0xFFFFFFFF and data_size is not None:
+            size = data_size         # RF64 / BW64: the real size; the walk goes on behind the samples
+        data = f.read(size)
+        if size % 2:
+            f.read(1)
+        if cid == b"ds64":
+            data_size = _ds64_data_size(data)
+        yield cid, data
+
+
+def load_wav(path_or_file, mono=True):
+    """-> (float32 mono ndarray, sampling_rate) of a RIFF/WAVE (RF64, BW64) file.  mono=False: the channels kept apart, float32
+    [channels, n_frames] (C-contiguous) for a file of two or more channels and [n_frames] for a one-channel file; every sample
+    converted as for the mono mix, before its mean."""
+    f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) else path_or_file
+    try:
+        if not hasattr(f, "read"):
+            f = io.BytesIO(f)
+        fmt, raw = None, None
+        for cid, data in _read_chunks(f):
+            if cid == b"fmt ":
+                fmt = _fmt_chunk(data)
+            elif cid == b"data":
+                raw = data
+        if fmt is None or raw is None:
+            raise ValueError("missing fmt or data chunk")
+    finally:
+        if isinstance(path_or_file, (str, bytes)):
+            f.close()
+    tag, ch, sr, bits = fmt
+    return _channels(_decode(raw, _pcm_format(tag, bits)), ch, mono), int(sr)
+
+
+# ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
+# load_wav above (load_audio further down, for every container) is the arithmetic's definition; what follows moves it to the
+# device: read_wav_raw / read_audio_raw hand out the sample bytes untouched, libwseg's wseg_samples_to_mono_f32 widens and
+# averages them with load_audio's float32 bits, and wseg_samples_to_planar_f32 widens the channels one asks for into planes
+# (load_audio(mono=False)'s rows).
 def scan_wav(f):
     """load_wav's chunk walk over a seekable file without reading the samples -> WavInfo (offset: where the data chunk's bytes
     start).  As in load_wav the last `fmt ` / `data` chunk counts, a chunk cut short by the end of the file is taken as far as it
-    goes, and the samples are cut to whole frames."""
+    goes, the size of a `data` chunk that says 0xFFFFFFFF comes from the `ds64` chunk in front of it, and the samples are cut to
+    whole frames."""
     header = f.read(12)
-    if len(header) < 12 or header[:4] not in (b"RIFF", b"RF64") or header[8:12] != b"WAVE":
+    if len(header) < 12 or header[:4] not in WAVE_IDS or header[8:12] != b"WAVE":
         raise ValueError("not a RIFF/WAVE file")
     end = f.seek(0, 2)
-    pos, fmt, data = 12, None, None
+    pos, fmt, data, data_size = 12, None, None, None
     while pos + 8 <= end:
         f.seek(pos)
         head = f.read(8)
         cid, size = head[:4], struct.unpack("<I", head[4:])[0]
         pos += 8
         if cid == b"fmt ":
-            body = f.read(size)
-            tag, ch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
-            if tag == 0xFFFE and len(body) >= 26:
-                tag = struct.unpack("<H", body[24:26])[0]
-            fmt = (tag, ch, sr, bits)
+            fmt = _fmt_chunk(f.read(size))
+        elif cid == b"ds64":
+            data_size = _ds64_data_size(f.read(min(size, 16)))
         elif cid == b"data":
+            if size == 0xFFFFFFFF and data_size is not None:
+                size = data_size
             data = (pos, min(size, end - pos))
         pos += size + size % 2
     if fmt is None or data is None:
@@ -134,6 +202,130 @@ def scan_wav(f):
     ch = max(int(ch), 1)
     frame_bytes = ch * BYTES_PER_SAMPLE[code]
     return WavInfo(code, ch, int(sr), data[1] // frame_bytes, frame_bytes, data[0])
+
+
+# ---- AIFF / AIFF-C and AU: header scans; the samples are decoded by _decode (host) or the device entry points -----------------
+AIFC_PCM_BE = (None, ENC_S8, ENC_S16BE, ENC_S24BE, ENC_S32BE)        # by sample width in bytes
+AIFC_PCM_LE = (None, ENC_S8, PCM_S16, PCM_S24, PCM_S32)
+AIFC_FIXED = {b"fl32": ENC_F32BE, b"FL32": ENC_F32BE, b"fl64": ENC_F64BE, b"FL64": ENC_F64BE,
+              b"ulaw": ENC_ULAW, b"ULAW": ENC_ULAW, b"alaw": ENC_ALAW, b"ALAW": ENC_ALAW}
+AU_ENCODINGS = {1: ENC_ULAW, 2: ENC_S8, 3: ENC_S16BE, 4: ENC_S24BE, 5: ENC_S32BE, 6: ENC_F32BE, 7: ENC_F64BE, 27: ENC_ALAW}
+
+
+def _extended_to_rate(ten):
+    """An 80-bit extended float (AIFF's sample rate) -> int, rounded to nearest; ValueError below 1 Hz and for inf / NaN."""
+    exponent, mantissa = struct.unpack(">HQ", ten)
+    e = (exponent & 0x7FFF) - 16383 - 63
+    rate = 0
+    if not exponent & 0x8000 and (exponent & 0x7FFF) != 0x7FFF and e > -128:
+        rate = mantissa << e if e >= 0 else (mantissa + (1 << (-e - 1))) >> -e
+    if rate < 1:
+        raise ValueError("unsupported AIFF sample rate (below 1 Hz, or not a number)")
+    return rate
+
+
+def _info(code, ch, sr, declared, available, offset):
+    if ch < 1:
+        raise ValueError(f"unsupported channel count {ch}")
+    frame_bytes = ch * BYTES_PER_SAMPLE[code]
+    whole = max(available, 0) // frame_bytes
+    return WavInfo(code, ch, int(sr), whole if declared is None else min(declared, whole), frame_bytes, offset)
+
+
+def _scan_aiff(f):
+    header = f.read(12)
+    aifc = header[8:12] == b"AIFC"
+    end = f.seek(0, 2)
+    pos, comm, ssnd = 12, None, None
+    while pos + 8 <= end:
+        f.seek(pos)
+        head = f.read(8)
+        cid, size = head[:4], struct.unpack(">I", head[4:])[0]
+        pos += 8
+        if cid == b"COMM":
+            comm = f.read(min(size, 22))
+        elif cid == b"SSND":
+            lead = f.read(8)
+            if len(lead) < 8:
+                raise ValueError("the SSND chunk is cut short")
+            skip = struct.unpack(">I", lead[:4])[0]
+            ssnd = (pos + 8 + skip, min(size, end - pos) - 8 - skip)
+        pos += size + size % 2
+    if comm is None or len(comm) < (22 if aifc else 18):
+        raise ValueError("missing COMM chunk" if comm is None else "the COMM chunk is cut short")
+    ch, frames, bits = struct.unpack(">hIh", comm[:8])
+    sr = _extended_to_rate(comm[8:18])
+    if ssnd is None:
+        if frames:
+            raise ValueError("missing SSND chunk")
+        ssnd = (end, 0)
+    kind = comm[18:22] if aifc else b"NONE"
+    if kind in (b"NONE", b"twos", b"sowt", b"raw "):
+        if not 1 <= bits <= 32:
+            raise ValueError(f"unsupported PCM width {bits}")
+        width = (bits + 7) // 8
+        if kind == b"raw ":
+            if width != 1:
+                raise ValueError(f"unsupported PCM width {bits} for AIFF-C compression 'raw '")
+            code = PCM_U8
+        else:
+            code = (AIFC_PCM_LE if kind == b"sowt" else AIFC_PCM_BE)[width]
+    elif kind in AIFC_FIXED:
+        code = AIFC_FIXED[kind]
+    else:
+        raise ValueError(f"unsupported AIFF-C compression {kind.decode('latin-1')!r}")
+    return _info(code, ch, sr, frames, ssnd[1], ssnd[0])
+
+
+def _scan_au(f):
+    header = f.read(24)
+    if len(header) < 24:
+        raise ValueError("the AU header is cut short")
+    _, offset, size, encoding, sr, ch = struct.unpack(">6I", header)
+    if offset < 24:
+        raise ValueError(f"AU data offset {offset} lies inside the header")
+    if encoding not in AU_ENCODINGS:
+        raise ValueError(f"unsupported AU encoding {encoding}")
+    if sr < 1:
+        raise ValueError("unsupported AU sample rate 0")
+    end = f.seek(0, 2)
+    available = end - offset if size == 0xFFFFFFFF else min(size, end - offset)
+    return _info(AU_ENCODINGS[encoding], ch, sr, None, available, offset)
+
+
+def scan_audio(f):
+    """scan_wav for every container: the header walk over a seekable file without reading the samples -> WavInfo (format: a
+    wseg_sample_encoding; offset: where the samples start in the file).  The container is sniffed from the first 12 bytes."""
+    start = f.tell()
+    header = f.read(12)
+    f.seek(start)
+    if header[:4] in WAVE_IDS:
+        return scan_wav(f)
+    if header[:4] == b"FORM" and header[8:12] in (b"AIFF", b"AIFC"):
+        return _scan_aiff(f)
+    if header[:4] == b".snd":
+        return _scan_au(f)
+    raise ValueError("unknown audio container (not RIFF/WAVE, RF64, BW64, AIFF, AIFF-C or AU)")
+
+
+def load_audio(path_or_file, mono=True):
+    """load_wav for every container -> (float32 ndarray, sampling_rate): the definition of the arithmetic of the encodings WAVE
+    does not carry (signed 8-bit, big-endian PCM and floats; _decode has the float32 steps).  A WAVE file goes to load_wav."""
+    f, ours = _opened(path_or_file)
+    try:
+        start = f.tell()
+        header = f.read(12)
+        f.seek(start)
+        if header[:4] in WAVE_IDS:
+            return load_wav(f, mono=mono)
+        info = scan_audio(f)
+        raw = bytearray(info.n_frames * info.frame_bytes)
+        f.seek(info.offset)
+        _read_exact(f, memoryview(raw))
+    finally:
+        if ours:
+            f.close()
+    return _channels(_decode(bytes(raw), info.format), info.channels, mono), info.sr
 
 
 def _opened(path_or_file):
@@ -152,13 +344,10 @@ def _read_exact(f, view):
         got += n
 
 
-def read_wav_raw(path_or_file, into=None):
-    """-> WavRaw(data, format, channels, sr, n_frames): the sample bytes of whole frames exactly as they sit in the data chunk
-    (a uint8 memoryview of n_frames * channels * bytes-per-sample bytes), `format` a wseg_pcm_format code.  With `into` — a
-    caller's writable buffer, e.g. pinned memory — the bytes are read straight into it and `data` is a view of its front."""
+def _read_raw(path_or_file, into, scan):
     f, ours = _opened(path_or_file)
     try:
-        info = scan_wav(f)
+        info = scan(f)
         nbytes = info.n_frames * info.frame_bytes
         if into is None:
             into = bytearray(nbytes)
@@ -174,9 +363,21 @@ def read_wav_raw(path_or_file, into=None):
     return WavRaw(view, info.format, info.channels, info.sr, info.n_frames)
 
 
+def read_wav_raw(path_or_file, into=None):
+    """-> WavRaw(data, format, channels, sr, n_frames): the sample bytes of whole frames exactly as they sit in the data chunk
+    (a uint8 memoryview of n_frames * channels * bytes-per-sample bytes), `format` a wseg_sample_encoding code.  With `into` — a
+    caller's writable buffer, e.g. pinned memory — the bytes are read straight into it and `data` is a view of its front."""
+    return _read_raw(path_or_file, into, scan_wav)
+
+
+def read_audio_raw(path_or_file, into=None):
+    """read_wav_raw for every container scan_audio knows."""
+    return _read_raw(path_or_file, into, scan_audio)
+
+
 class DeviceIngest:
     """The device half of the ingest: pinned staging buffers, and `submit` = copy a filled buffer to the device and decode it
-    there (wseg_pcm_to_mono_f32), stream-ordered on the current stream.  Every call belongs to the thread that owns the
+    there (wseg_samples_to_mono_f32), stream-ordered on the current stream.  Every call belongs to the thread that owns the
     device; a reader thread only ever writes into the arrays `acquire` handed out."""
 
     def __init__(self, device="cuda"):
@@ -207,14 +408,14 @@ class DeviceIngest:
     def submit(self, view, nbytes, info, out, frame0, n_frames):
         """Decode `n_frames` frames whose `nbytes` bytes sit at the front of buffer `view` into out[frame0 : frame0 + n_frames]
         -> an event that has completed once the copy out of the buffer has, i.e. once the buffer may be written again."""
-        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_pcm_to_mono_f32(
+        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_mono_f32(
             raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), out[frame0:frame0 + n_frames].data_ptr(),
             self._lib.stream_ptr()))
 
     def submit_planar(self, view, nbytes, info, out, frame0, n_frames, first_channel):
         """submit for the planes of new_planar_output: channels first_channel .. first_channel + out.shape[0] - 1 of the piece go
-        to out[:, frame0 : frame0 + n_frames] (wseg_pcm_to_planar_f32 with the whole recording's frame count as plane stride)."""
-        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_pcm_to_planar_f32(
+        to out[:, frame0 : frame0 + n_frames] (wseg_samples_to_planar_f32 with the whole recording's frame count as plane stride)."""
+        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_planar_f32(
             raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(first_channel), int(out.shape[0]),
             out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
 
@@ -257,12 +458,12 @@ class StreamResampler:
     rate — [n_out], or [planes, n_out] for a planar selection — and ONE segment buffer of resample.stream_capacity frames per plane
     (plus up to 3 floats in front and a stride rounded up to four: see below).
     submit(), per piece and in the file's order, on the current stream and without a host synchronisation: the frames the next
-    outputs still need move to the front of the segment, the piece is decoded behind them (wseg_pcm_to_mono_f32 /
-    wseg_pcm_to_planar_f32 with the segment's stride as plane stride), and ONE wseg_resample_planar_range_f32 launch writes the
+    outputs still need move to the front of the segment, the piece is decoded behind them (wseg_samples_to_mono_f32 /
+    wseg_samples_to_planar_f32 with the segment's stride as plane stride), and ONE wseg_resample_planar_range_f32 launch writes the
     outputs that have become computable, all planes at once (resample.stream_plan says which; a piece may add none).  Every output
     has the bits resample() gives it on the whole decoded recording.  result(): the output, once the last piece has been submitted.
     "The front" is 0 to 3 floats into the segment, such that the PIECE starts on a multiple of 16 bytes however many frames are
-    retained: wseg_pcm_to_mono_f32 stores 16 bytes per lane only to an aligned destination (dword stores otherwise), whereas the
+    retained: wseg_samples_to_mono_f32 stores 16 bytes per lane only to an aligned destination (dword stores otherwise), whereas the
     range call reads a segment of any alignment."""
 
     def __init__(self, ingest, info, sel, sr_out, piece_frames):
@@ -296,9 +497,9 @@ class StreamResampler:
         def decode_and_resample(raw):
             dst = seg.data_ptr() + 4 * (lead + kept)
             if self.sel is None:
-                status = lib.wseg_pcm_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst, stream_ptr())
+                status = lib.wseg_samples_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst, stream_ptr())
             else:
-                status = lib.wseg_pcm_to_planar_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(self.sel[0]),
+                status = lib.wseg_samples_to_planar_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(self.sel[0]),
                                                     int(seg.shape[0]), dst, self.stride, stream_ptr())
             if status or not step["m_count"]:
                 return status
@@ -380,11 +581,12 @@ def device_ingest(device="cuda"):
 
 
 def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, channel_id=None, sr=None):
-    """load_wav on the GPU -> (float32 device tensor [n_frames], sampling_rate), the same samples bit for bit: sample bytes ->
-    pinned staging -> non_blocking copy -> wseg_pcm_to_mono_f32 on the current stream.  A data chunk larger than the staging
+    """load_audio on the GPU (any container of scan_audio) -> (float32 device tensor [n_frames], sampling_rate), the same samples bit
+    for bit: sample bytes ->
+    pinned staging -> non_blocking copy -> wseg_samples_to_mono_f32 on the current stream.  A data chunk larger than the staging
     buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.
     mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
-    wseg_pcm_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
+    wseg_samples_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
     ignores it; negative k counts from the end, out of range raises IndexError.
     sr=N: `librosa.load(..., sr=N)` — every piece is resampled on the device as soon as it is decoded (StreamResampler: one launch
     per piece for all planes, the bits of resample() on the whole decoded file, which is never held at its native rate) and N is the
@@ -393,7 +595,7 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     ingest = device_ingest(device)
     f, ours = _opened(path_or_file)
     try:
-        info = scan_wav(f)
+        info = scan_audio(f)
         check_channels(info)
         total = info.n_frames * info.frame_bytes
         views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * info.frame_bytes)))
@@ -495,7 +697,7 @@ class FilePipeline:
         for index, path in enumerate(self.paths):
             try:
                 with open(path, "rb") as f:
-                    info = scan_wav(f)
+                    info = scan_audio(f)
                     check_channels(info, os.path.basename(path))
                     sel = select_channels(info, self.channel_id)
                     step = chunk_plan(info, len(self.views[0]))
