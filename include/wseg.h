@@ -192,6 +192,29 @@ int wseg_samples_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels
 int wseg_samples_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding,
                                int32_t first_channel, int32_t n_out_channels,
                                float* out, int64_t plane_stride, void* stream);
+/* The same two decodes for the one BLOCK codec of the ingest, IMA / DVI ADPCM as WAVE carries it (format tag 0x0011, 4 bits per
+ * sample; whisperseg_amd/wavio.py::decode_ima_adpcm is the host definition, code 14 = wavio.ENC_IMA_ADPCM on the Python side only:
+ * wseg_samples_to_* go on rejecting it, a block file has no frame size).  raw holds n_blocks blocks of block_bytes bytes:
+ *   per channel, in channel order, a 4-byte header: int16 LE predictor | u8 step index | u8 reserved; the predictor is also the
+ *     block's first sample of that channel;
+ *   then groups of 4 bytes per channel, interleaved by channel (8 samples of channel 0, 8 of channel 1, ...), low nibble first.
+ * So block_bytes = 4 * channels * (1 + k), k >= 1, at most 65532 bytes per channel, and a block holds spb = 8 k + 1 frames.  Per nibble d, the
+ * standard's integer arithmetic: diff = step >> 3 (+ step if d & 4) (+ step >> 1 if d & 2) (+ step >> 2 if d & 1) with step =
+ * table[index]; predictor -= diff if d & 8 else += diff, clamped to int16; index += {-1,-1,-1,-1,2,4,6,8}[d & 7], clamped to 0..88
+ * (a header index above 88 is taken as 88).  A sample is predictor / 2^15 as for S16, the mono mix numpy's float32 mean as above.
+ * n_frames cuts the last block: (n_blocks - 1) * spb < n_frames <= n_blocks * spb (0 for no blocks).  mono: out[f], 0 <= f <
+ * n_frames; planar: out[(c - first_channel) * plane_stride + f] for first_channel <= c < first_channel + n_out_channels — only
+ * those channels' chains run.  raw: device, 16-byte aligned, readable to the next multiple of 16 bytes behind n_blocks *
+ * block_bytes; out of any float alignment; plane_stride in floats, >= n_frames (ignored when n_out_channels == 1); nothing is
+ * written outside the addressed floats; channels 1..64; n_blocks == 0 launches nothing; stream-ordered.  Every argument is
+ * validated on the host before a launch: WSEG_ERR_INVALID with the argument's name (raw, out, channels, block_bytes, n_blocks,
+ * n_frames, first_channel, n_out_channels, plane_stride) in wseg_last_error().
+ * Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_ima_adpcm_to_mono_f32(const void* raw, int64_t n_blocks, int32_t block_bytes, int32_t channels,
+                               int64_t n_frames, float* out, void* stream);
+int wseg_ima_adpcm_to_planar_f32(const void* raw, int64_t n_blocks, int32_t block_bytes, int32_t channels,
+                                 int64_t n_frames, int32_t first_channel, int32_t n_out_channels,
+                                 float* out, int64_t plane_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.

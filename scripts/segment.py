@@ -8,7 +8,7 @@
     python scripts/segment.py --model_path DIR --audio_folder wavs/ --sr 16000 --csv_save_path out.csv
     python scripts/segment.py --model_path DIR --audio_folder mixed/ --audio_ext wav aiff aifc au --csv_save_path out.csv
 
-Recordings may be RIFF/WAVE (RF64 / BW64 included), AIFF / AIFF-C or AU files (whisperseg_amd/wavio.py), whatever their names.
+Recordings may be RIFF/WAVE (RF64 / BW64 and IMA ADPCM included), AIFF / AIFF-C or AU files (whisperseg_amd/wavio.py), whatever their names.
 
 --channel_id (the `channel_id` of the reference's interactive entry points: segment_service.py:73-80, scripts/backend.py:279-282,
 demo.py:76-78) segments one channel of multi-channel recordings instead of their mono mix — an integer: the same columns, rows

@@ -7,6 +7,7 @@
     python tools/ingest_bench.py --resample [--out profiles/resample_planar_ab.txt]
     python tools/ingest_bench.py --stream [--out profiles/resample_stream_ab.txt]
     python tools/ingest_bench.py --encodings [--out profiles/ingest_encodings_ab.txt]
+    python tools/ingest_bench.py --adpcm [--out profiles/ingest_adpcm_ab.txt]
 
 For each of three recorder formats — s16 mono 16 kHz, s16 stereo 48 kHz, s24 stereo 96 kHz — it writes `--files` files of
 `--seconds` seconds into a temporary directory and reports
@@ -31,6 +32,13 @@ wseg_samples_to_mono_f32 with one and two channels and wseg_samples_to_planar_f3
 events; one warm-up train of each encoding, then five repetitions, the two encodings alternating; all five rates are printed, the
 median is the figure.  Bytes in and out are equal within a pair, so
 the rates compare directly; a line says whether the new encoding's median lies inside the spread of its sibling's own repetitions.
+
+--adpcm measures the IMA ADPCM decode alone (wseg_ima_adpcm_to_mono_f32, and wseg_ima_adpcm_to_planar_f32 with all channels for a
+multi-channel case) beside wseg_samples_to_mono_f32 / wseg_samples_to_planar_f32 on the same number of frames as s16 — the file the
+recorder would otherwise have written — for ADPCM_CASES x 600 s, on random bytes generated on the device.  A repetition is a train
+of back-to-back launches that moves about 20 GB between two HIP events; one warm-up train of each, then five repetitions, the two
+alternating; the figure is the median time per launch in ms and with it GB/s = (bytes in + bytes out) / time and M frames/s (all
+five times are printed).  The host line is load_audio on a 60 s file of the same geometry, read from the page cache.
 
 --resample measures the two resamplers alone, no engine, by the same protocol: wseg_resample_planar_f32 (one launch for all planes)
 beside the loop it replaces (one wseg_resample_f32 launch per plane, back to back) on the same planes (seeded normal samples,
@@ -202,6 +210,74 @@ def encodings_section(lib, emit, seconds=600, sr=48000, reps=5):
             del raw, out
 
 
+ADPCM_CASES = ((1, 16000, 256), (2, 48000, 2048), (8, 48000, 8192))       # (channels, rate, block bytes)
+
+
+def adpcm_section(lib, emit, seconds=600, reps=5):
+    import torch
+    import ima_adpcm_cases as IC
+    from whisperseg_amd import _lib
+    from whisperseg_amd.wavio import load_audio
+    stream = lambda: _lib.stream_ptr()
+    for channels, sr, block_bytes in ADPCM_CASES:
+        spb = IC.block_frames(channels, block_bytes)
+        n = seconds * sr
+        n_blocks = -(-n // spb)
+        name = "x%d %d Hz, blocks of %d bytes (%d frames)" % (channels, sr, block_bytes, spb)
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "rec.wav")
+            host_frames = 60 * sr
+            with open(path, "wb") as f:
+                f.write(IC.make_wav(channels, block_bytes, -(-host_frames // spb), sr=sr))
+            load_audio(path)
+            t0 = time.perf_counter()
+            frames = len(load_audio(path)[0])
+            host_s = time.perf_counter() - t0
+        emit("%-48s load_audio (host, a 60 s file)  %8.2f M frames/s  (%.2f s)" % (name, frames / host_s / 1e6, host_s))
+        adpcm_bytes, s16_bytes = n_blocks * block_bytes, 2 * n * channels
+        raw = {"adpcm": torch.randint(0, 256, (-(-adpcm_bytes // 16) * 16,), dtype=torch.uint8, device="cuda"),
+               "s16": torch.randint(0, 256, (-(-s16_bytes // 16) * 16,), dtype=torch.uint8, device="cuda")}
+        for kernel in ("mono",) + (("planar",) if channels > 1 else ()):
+            out = torch.empty((channels if kernel == "planar" else 1, n), dtype=torch.float32, device="cuda")
+            moved = {"adpcm": adpcm_bytes + 4 * out.numel(), "s16": s16_bytes + 4 * out.numel()}
+            iters = {k: max(1, int(2e10 // v)) for k, v in moved.items()}
+
+            def call(which):
+                if which == "adpcm" and kernel == "mono":
+                    _lib.check(lib.wseg_ima_adpcm_to_mono_f32(raw["adpcm"].data_ptr(), n_blocks, block_bytes, channels, n, out.data_ptr(), stream()))
+                elif which == "adpcm":
+                    _lib.check(lib.wseg_ima_adpcm_to_planar_f32(raw["adpcm"].data_ptr(), n_blocks, block_bytes, channels, n, 0, channels,
+                                                                out.data_ptr(), n, stream()))
+                elif kernel == "mono":
+                    _lib.check(lib.wseg_samples_to_mono_f32(raw["s16"].data_ptr(), n, channels, 1, out.data_ptr(), stream()))
+                else:
+                    _lib.check(lib.wseg_samples_to_planar_f32(raw["s16"].data_ptr(), n, channels, 1, 0, channels, out.data_ptr(), n, stream()))
+
+            def train(which):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters[which]):
+                    call(which)
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b) / iters[which]
+
+            ms = {"adpcm": [], "s16": []}
+            for which in ms:
+                train(which)
+            for _ in range(reps):
+                for which in ms:
+                    ms[which].append(train(which))
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            for which in ("adpcm", "s16"):
+                emit("%-48s %-6s %-5s %9.4f ms  %8.1f GB/s  %9.1f M frames/s  (%s; %d launches per repetition, %.1f MB in + %.1f MB out per launch)"
+                     % (name, kernel, which, med[which], moved[which] / med[which] / 1e6, n / med[which] / 1e3,
+                        " ".join("%.4f" % v for v in ms[which]), iters[which], (moved[which] - 4 * out.numel()) / 1e6, 4 * out.numel() / 1e6))
+            emit("%-48s %-6s adpcm / s16 time = %.2f" % (name, kernel, med["adpcm"] / med["s16"]))
+            del out
+        del raw
+
+
 RESAMPLE_CASES = ((44100, 16000), (48000, 16000), (96000, 16000), (16000, 44100), (250000, 44100))
 
 
@@ -360,6 +436,8 @@ def main(argv=None):
                     help="only the file path at a target rate: load_wav_device(sr=) and FilePipeline(sr=) on a file that goes through in pieces")
     ap.add_argument("--encodings", action="store_true",
                     help="only the kernels: every new sample encoding beside its sibling of the same width")
+    ap.add_argument("--adpcm", action="store_true",
+                    help="only the kernels: the IMA ADPCM decode beside the s16 decode of the same frames, and the host decode")
     ap.add_argument("--piece-mb", type=int, default=4, help="--stream: MiB per piece of the file")
     args = ap.parse_args(argv)
     if args.stream:
@@ -371,6 +449,10 @@ def main(argv=None):
         return _tool_section(args, "sample encodings A/B: wseg_samples_to_mono_f32 / wseg_samples_to_planar_f32 on a new encoding beside its "
                                    "sibling of the same width on the same bytes, HIP events, GB/s = (bytes in + bytes out) / time, median of "
                                    "five repetitions after one warm-up, the two alternating (all five in brackets)", encodings_section)
+    if args.adpcm:
+        return _tool_section(args, "IMA ADPCM decode A/B: wseg_ima_adpcm_to_mono_f32 / _planar_f32 beside wseg_samples_to_mono_f32 / _planar_f32 on the "
+                                   "same frames as s16, 600 s of audio, HIP events, ms per launch, GB/s = (bytes in + bytes out) / time, median of "
+                                   "five repetitions after one warm-up, the two alternating (all five in brackets); host: load_audio", adpcm_section)
     if args.resample:
         return _tool_section(args, "resample A/B: wseg_resample_planar_f32 (one launch, all planes) beside a loop of wseg_resample_f32 launches "
                                    "over the same planes and taps, HIP events, ms per call of all planes, median of three repetitions after one "

@@ -15,7 +15,9 @@
 // cover its group (16-byte loads where the group is a multiple of 16 bytes) and takes samples apart in registers; the last
 // n_frames % 4 frames are read byte by byte by one lane.  No LDS, no scratch; all indexing is 64-bit.
 // wseg_pcm_to_planar_f32 (further down) keeps the channels apart instead of averaging them, through an LDS image of a tile of frames.
+// wseg_ima_adpcm_to_mono_f32 / _planar_f32 (last) decode the one block codec of the ingest, IMA ADPCM: one sequential chain per lane.
 #include "wseg_common.h"
+#include "wseg_ima_adpcm_plan.h"
 
 namespace wseg {
 
@@ -274,6 +276,128 @@ __global__ __launch_bounds__(256) void pcm_to_planar_kernel(const void* __restri
   }
 }
 
+// ---- IMA ADPCM (wseg_ima_adpcm_to_mono_f32 / wseg_ima_adpcm_to_planar_f32) -------------------------------------------------------
+// A block codec: inside a block every sample of a channel follows from the one before it (predictor and step index), so the unit of
+// parallel work is a CHAIN, one (block, channel) pair, and a lane runs one chain: block_frames - 1 dependent steps, each with a
+// divergent look-up of the step table — which therefore sits in LDS (89 dwords the workgroup fills), not in constant memory.
+// A workgroup takes GROUPS of floor(256 / channels) whole blocks, so that every channel of a frame is decoded in the workgroup
+// that averages it.  The bytes of a group go through an LDS image in PASSES of kAdpcmPassDwords data dwords per chain (pass 0 with
+// the block's headers in front): a row per block, filled by coalesced 16-byte loads — consecutive lanes on consecutive 16-byte
+// pieces of one block's stretch, then of the next block's; only a piece that straddles the end of a stretch (blocks that are no
+// multiple of 16 bytes, or the seam of two passes) is fetched by both sides, each keeping its own dwords.  The rows are an odd
+// number of dwords apart: the chains of a one-channel file read the image at a lane stride of one row, and block sizes are
+// typically powers of two (the pad of PaddedImage above, per row instead of per 16 dwords).
+// A chain advances in SLICES of four dwords = 32 samples, written as floats to its row of the stage (33 floats: slice 0 also holds
+// the block's first sample, which is the header's predictor; an odd stride again).  Behind a barrier the slice leaves as contiguous
+// runs: an item is (plane, block, four frames on the PLANE's 16-byte grid), consecutive lanes on consecutive items of one run, a
+// 16-byte store each and dword stores at the run's cut ends — as in pcm_to_planar_kernel; block starts b * block_frames are odd
+// offsets, so the grid is taken from the address.  The mono mix averages the stage's rows of a block with frame_mean (numpy's order).
+// All trip counts (groups, passes, slices) are uniform over the workgroup; lanes without a chain only pass the barriers.
+__device__ const int kImaSteps[89] = {
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157,
+    173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707,
+    1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635,
+    13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};
+
+// MONO: every channel's chain runs and the frames' means go to out; else the chains of channels first .. first + n_sel - 1 go to
+// planes plane_stride floats apart.
+template <bool MONO>
+__global__ __launch_bounds__(256) void ima_adpcm_kernel(const void* __restrict__ raw_, long long n_blocks, int ch, long long n_frames, int first,
+                                                        int n_sel, float* __restrict__ out, long long plane_stride, AdpcmPlan plan) {
+  __shared__ uint32_t image[kAdpcmImageDwords];
+  __shared__ float stage[kAdpcmLanes * kAdpcmStageStride];
+  __shared__ int steps[89];
+  const int tid = threadIdx.x;
+  if (tid < 89) steps[tid] = kImaSteps[tid];                   // (read behind the barrier that follows the first image fill)
+  const uint4* __restrict__ raw = static_cast<const uint4*>(raw_);
+  const int rs = plan.row_stride, nd = plan.data_dwords;
+  const int chains = MONO ? ch : n_sel;                        // chains per block
+  const int my_block = tid / chains, my_c = (MONO ? 0 : first) + (tid - my_block * chains);
+  float* const my_stage = stage + tid * kAdpcmStageStride;     // (tid = my_block * chains + the chain's number in its block)
+  for (long long grp = blockIdx.x; grp < plan.n_groups; grp += gridDim.x) {
+    const long long b0 = grp * plan.group_blocks;
+    const int gb = (int)min((long long)plan.group_blocks, n_blocks - b0);
+    const bool has_chain = my_block < gb;
+    int pred = 0, idx = 0;
+    for (int pass = 0; pass < plan.n_passes; ++pass) {
+      const int j0 = pass * kAdpcmPassDwords, nj = min(kAdpcmPassDwords, nd - j0);
+      const int lo = pass ? ch * (1 + j0) : 0, len = ch * (1 + j0 + nj) - lo;    // the stretch [lo, lo + len) of a block's dwords
+      const int pieces = (4 * len + 27) >> 4;                  // the 16-byte pieces it can touch, wherever it starts
+      for (int i = tid; i < gb * pieces; i += 256) {
+        const int r = i / pieces, k = i - r * pieces;
+        const long long d_lo = (b0 + r) * plan.block_dwords + lo;
+        const long long piece = (d_lo >> 2) + k;
+        const int rel = (int)((piece << 2) - d_lo);            // -3 .. : the piece's first dword, counted from the stretch's
+        if (rel < len) {                                       // (the piece starts inside the block: raw is readable to its end)
+          const uint4 q = raw[piece];
+          const uint32_t v[4] = {q.x, q.y, q.z, q.w};
+          uint32_t* row = image + r * rs;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (rel + e >= 0 && rel + e < len) row[rel + e] = v[e];
+        }
+      }
+      __syncthreads();
+      if (pass == 0 && has_chain) {                            // the chain's header: int16 predictor, u8 step index, u8 reserved
+        const uint32_t h = image[my_block * rs + my_c];
+        pred = (int)(int16_t)(h & 0xffffu);
+        idx = min((int)((h >> 16) & 0xffu), 88);
+      }
+      const int base = my_block * rs + (pass ? 0 : ch) + my_c;  // the chain's data dword j0 + j at base + j * ch
+      for (int s = 0; 4 * s < nj; ++s) {
+        const int nq = min(kAdpcmSliceDwords, nj - 4 * s);
+        const bool first_slice = pass == 0 && s == 0;
+        if (has_chain) {
+          if (first_slice) my_stage[0] = (float)pred / 32768.0f;
+          for (int q = 0; q < nq; ++q) {
+            const uint32_t w = image[base + (4 * s + q) * ch];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {                      // low nibble first
+              const int d = (int)((w >> (4 * e)) & 15u);
+              const int step = steps[idx];
+              int diff = step >> 3;
+              if (d & 4) diff += step;
+              if (d & 2) diff += step >> 1;
+              if (d & 1) diff += step >> 2;
+              pred = (d & 8) ? pred - diff : pred + diff;
+              pred = min(max(pred, -32768), 32767);
+              idx += (d & 4) ? ((d & 3) << 1) + 2 : -1;
+              idx = min(max(idx, 0), 88);
+              my_stage[1 + 8 * q + e] = (float)pred / 32768.0f;
+            }
+          }
+        }
+        __syncthreads();
+        // the slice's run of a block: samples [r0, r0 + run) of the block, at stage offset so of the chains' rows
+        const int r0 = first_slice ? 0 : 1 + 8 * (j0 + 4 * s), so = first_slice ? 0 : 1, run = 8 * nq + (first_slice ? 1 : 0);
+        const int n_items = (MONO ? 1 : n_sel) * gb * 9;        // 33 frames and up to 3 in front of them: nine groups of four
+        for (int it = tid; it < n_items; it += 256) {
+          const int row = it / 9, g = it - row * 9;
+          const int p = row / gb, bl = row - p * gb;            // plane-major: consecutive rows are consecutive blocks of one plane
+          const long long f_first = (b0 + bl) * plan.block_frames + r0;
+          const int n = (int)min((long long)run, n_frames - f_first);      // n_frames cuts the last block (n <= 0: nothing left)
+          float* __restrict__ dst = out + p * plane_stride + f_first;
+          const int f0 = 4 * g - (int)(((uintptr_t)dst >> 2) & 3);
+          if (f0 >= n) continue;
+          const float* src = stage + (bl * chains + p) * kAdpcmStageStride + so;
+          auto value = [&](int f) {
+            if (!MONO || ch == 1) return src[f];
+            return frame_mean<0>(ch, [&](int c) { return src[c * kAdpcmStageStride + f]; });
+          };
+          if (f0 >= 0 && f0 + 4 <= n) {
+            *reinterpret_cast<float4*>(dst + f0) = make_float4(value(f0), value(f0 + 1), value(f0 + 2), value(f0 + 3));
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (f0 + k >= 0 && f0 + k < n) dst[f0 + k] = value(f0 + k);
+          }
+        }
+        __syncthreads();                                       // the stage, and behind the last slice the image, may be rewritten
+      }
+    }
+  }
+}
+
 }  // namespace wseg
 
 using namespace wseg;
@@ -369,4 +493,40 @@ extern "C" int wseg_samples_to_planar_f32(const void* raw, int64_t n_frames, int
     set_error("wseg_samples_to_planar_f32: unknown encoding %d", encoding); return WSEG_ERR_INVALID;
   }
   return samples_to_planar("wseg_samples_to_planar_f32", raw, n_frames, channels, encoding, first_channel, n_out_channels, out, plane_stride, stream);
+}
+
+// The checks and the launch of both IMA ADPCM entry points (planar: n_out_channels >= 1; mono: 0).
+static int ima_adpcm_decode(const char* fn, const void* raw, int64_t n_blocks, int32_t block_bytes, int32_t channels, int64_t n_frames,
+                            int32_t first_channel, int32_t n_out_channels, bool mono, float* out, int64_t plane_stride, void* stream_) {
+  if (!head_ok(fn, raw, out, channels)) return WSEG_ERR_INVALID;
+  AdpcmPlan plan;
+  char msg[200];
+  if (ima_adpcm_plan(n_blocks, block_bytes, channels, n_frames, &plan, msg, sizeof(msg)) ||
+      (!mono && ima_adpcm_planar_check(channels, n_frames, first_channel, n_out_channels, plane_stride, msg, sizeof(msg)))) {
+    set_error("%s: %s", fn, msg);
+    return WSEG_ERR_INVALID;
+  }
+  if (n_blocks == 0) return WSEG_OK;
+  hipStream_t s = (hipStream_t)stream_;
+  const dim3 grid((unsigned)plan.grid);
+  if (mono) {
+    hipLaunchKernelGGL((ima_adpcm_kernel<true>), grid, dim3(kAdpcmLanes), 0, s, raw, (long long)n_blocks, (int)channels, (long long)n_frames, 0,
+                       (int)channels, out, 0LL, plan);
+  } else {
+    hipLaunchKernelGGL((ima_adpcm_kernel<false>), grid, dim3(kAdpcmLanes), 0, s, raw, (long long)n_blocks, (int)channels, (long long)n_frames,
+                       (int)first_channel, (int)n_out_channels, out, n_out_channels > 1 ? (long long)plane_stride : 0LL, plan);
+  }
+  WSEG_LAUNCH_CHECK();
+  return WSEG_OK;
+}
+
+extern "C" int wseg_ima_adpcm_to_mono_f32(const void* raw, int64_t n_blocks, int32_t block_bytes, int32_t channels, int64_t n_frames,
+                                          float* out, void* stream) {
+  return ima_adpcm_decode("wseg_ima_adpcm_to_mono_f32", raw, n_blocks, block_bytes, channels, n_frames, 0, 0, true, out, 0, stream);
+}
+
+extern "C" int wseg_ima_adpcm_to_planar_f32(const void* raw, int64_t n_blocks, int32_t block_bytes, int32_t channels, int64_t n_frames,
+                                            int32_t first_channel, int32_t n_out_channels, float* out, int64_t plane_stride, void* stream) {
+  return ima_adpcm_decode("wseg_ima_adpcm_to_planar_f32", raw, n_blocks, block_bytes, channels, n_frames, first_channel, n_out_channels,
+                          false, out, plane_stride, stream);
 }

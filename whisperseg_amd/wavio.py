@@ -3,14 +3,21 @@ not in the image): native sampling rate, float32 in [-1, 1), channels averaged t
 `librosa.load(..., mono=False)` does for the reference's `channel_id` (segment_service.py:73-80, scripts/backend.py:279-282,
 demo.py:76-78).
 Containers (sniffed from the first 12 bytes; load_audio / scan_audio / read_audio_raw):
-  RIFF/WAVE, RF64, BW64 — PCM 8/16/24/32-bit, IEEE float 32/64, G.711 A-law / u-law (tags 6 / 7), WAVE_FORMAT_EXTENSIBLE; an
-      RF64 / BW64 `ds64` chunk supplies the size of a `data` chunk whose own size field is 0xFFFFFFFF (load_wav / scan_wav /
-      read_wav_raw are the WAVE-only functions the others call)
+  RIFF/WAVE, RF64, BW64 — PCM 8/16/24/32-bit, IEEE float 32/64, G.711 A-law / u-law (tags 6 / 7), IMA / DVI ADPCM (tag 0x11,
+      4 bits), WAVE_FORMAT_EXTENSIBLE; an RF64 / BW64 `ds64` chunk supplies the size of a `data` chunk whose own size field is
+      0xFFFFFFFF (load_wav / scan_wav / read_wav_raw are the WAVE-only functions the others call)
   AIFF / AIFF-C — big-endian PCM of 1..32 bits (8-bit signed); compression NONE / twos / sowt / `raw ` / fl32 / fl64 / ulaw / alaw
   AU (.snd) — u-law, A-law, 8/16/24/32-bit linear, float 32/64
-Wave64, FLAC and lossy codecs are not read.  Integer samples are divided by 2^(bits-1) of their container width and G.711 codes go
-through the standard's int16 expansion, which is how libsndfile (behind librosa) produces its floats: equality with it is by
-construction, not pinned by a test (soundfile is not in the image).
+IMA ADPCM is the one compressed encoding that is read, and the one BLOCK codec: a block of nBlockAlign bytes holds, per channel, a
+4-byte header (int16 predictor = the block's first sample, u8 step index, u8 reserved) and then groups of 4 bytes per channel, low
+nibble first; decode_ima_adpcm is the definition (the standard's integer arithmetic, pinned against the stdlib's audioop.adpcm2lin).
+Its frame count is the `fact` chunk's where there is one that the whole blocks can hold, else blocks x samples per block; bytes
+behind the last whole block are dropped.  MS ADPCM (tag 2), AIFF-C `ima4`, Wave64 and FLAC are not read: nothing in the image
+decodes them independently, so no test could pin their arithmetic.
+Integer samples are divided by 2^(bits-1) of their container width, G.711 codes go through the standard's int16 expansion and ADPCM
+through the standard's int16 predictor (then / 2^15), which is how libsndfile (behind librosa) produces its floats: equality with
+it is by construction, not pinned by a test (soundfile is not in the image) — nor is libsndfile's treatment of `fact` and of a
+partial last block.
 load_wav / load_audio keep the native rate; the device path (load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU
 (whisperseg_amd.resample), all planes of a file at once and piece by piece as the file is read (StreamResampler)."""
 import collections
@@ -27,13 +34,16 @@ import numpy as np
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)
 ENC_S8, ENC_S16BE, ENC_S24BE, ENC_S32BE, ENC_F32BE, ENC_F64BE, ENC_ULAW, ENC_ALAW = range(6, 14)
 BYTES_PER_SAMPLE = (1, 2, 3, 4, 4, 8, 1, 2, 3, 4, 4, 8, 1, 1)
+ENC_IMA_ADPCM = 14               # Python-side only: a block codec has no bytes per sample, and wseg_samples_to_* reject the code
 MAX_CHANNELS = 64
 STAGING_BYTES = 256 << 20        # one pinned staging buffer; a longer data chunk goes through in pieces
 PLANAR_TILE_FRAMES = 1024        # kPlanarTile of csrc/wseg_ingest.hip: the frames a workgroup of wseg_samples_to_planar_f32 stages at a time
 PLANAR_GRID_CAP = 2048           # kPlanarGridCap there: with more tiles than this the workgroups take a grid stride
+ADPCM_GRID_CAP = 1024            # kAdpcmGridCap of csrc/wseg_ima_adpcm_plan.h: workgroups of the IMA ADPCM decode, floor(256 / channels) blocks each
 
 WavRaw = collections.namedtuple("WavRaw", "data format channels sr n_frames")
-WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames frame_bytes offset")
+# block_bytes / block_frames: bytes and frames of a block of a block codec (ENC_IMA_ADPCM; frame_bytes is 0 then), else 0
+WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames frame_bytes offset block_bytes block_frames", defaults=(0, 0))
 
 WAVE_IDS = (b"RIFF", b"RF64", b"BW64")
 
@@ -86,6 +96,54 @@ def _decode(raw, code):
     raise ValueError(f"unknown sample encoding {code}")
 
 
+IMA_STEPS = np.array([
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157,
+    173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707,
+    1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635,
+    13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767], np.int32)
+IMA_INDEX_STEPS = np.array([-1, -1, -1, -1, 2, 4, 6, 8], np.int32)
+
+
+def ima_block_frames(channels, block_bytes, declared=None):
+    """Frames of an IMA ADPCM block of `block_bytes` bytes: 2 * (block_bytes / channels - 4) + 1 (a header per channel, then whole
+    groups of 4 bytes per channel); ValueError for a size no block can have, or when the header's wSamplesPerBlock (`declared`)
+    says otherwise (libsndfile refuses such files too)."""
+    if channels < 1 or block_bytes <= 4 * channels or (block_bytes - 4 * channels) % (4 * channels):
+        raise ValueError(f"unsupported IMA ADPCM nBlockAlign {block_bytes} for {channels} channels (not a header and whole groups of "
+                         f"4 bytes per channel)")
+    spb = 2 * (block_bytes // channels - 4) + 1
+    if declared is not None and declared != spb:
+        raise ValueError(f"IMA ADPCM wSamplesPerBlock {declared} does not match the {spb} samples of a block of {block_bytes} bytes")
+    return spb
+
+
+def decode_ima_adpcm(raw, channels, block_bytes):
+    """The whole blocks of `raw` (IMA / DVI ADPCM as WAVE lays it out, see the module's docstring) -> int16 [n_blocks * spb, channels]:
+    the definition of the arithmetic, vectorised over blocks x channels with one loop over the spb - 1 steps of a chain.  Per nibble
+    d: diff = step >> 3 (+ step if d & 4) (+ step >> 1 if d & 2) (+ step >> 2 if d & 1); the predictor moves down by it if d & 8,
+    else up, and is clamped to int16; the step index moves by {-1,-1,-1,-1,2,4,6,8}[d & 7], clamped to 0..88 (a header's index above
+    88 is taken as 88)."""
+    spb = ima_block_frames(channels, block_bytes)
+    n_blocks = len(raw) // block_bytes
+    b = np.frombuffer(raw, np.uint8, n_blocks * block_bytes).reshape(n_blocks, block_bytes)
+    head = b[:, :4 * channels].reshape(n_blocks, channels, 4)
+    pred = head[:, :, :2].copy().view("<i2")[:, :, 0].astype(np.int32)
+    index = np.minimum(head[:, :, 2].astype(np.int32), 88)
+    data = b[:, 4 * channels:].reshape(n_blocks, (spb - 1) // 8, channels, 4)              # [block, group, channel, byte]
+    nibbles = np.stack([data & 15, data >> 4], axis=-1).reshape(n_blocks, (spb - 1) // 8, channels, 8)      # low nibble first
+    nibbles = nibbles.transpose(0, 1, 3, 2).reshape(n_blocks, spb - 1, channels).astype(np.int32)
+    out = np.empty((n_blocks, spb, channels), np.int16)
+    out[:, 0] = pred
+    for k in range(spb - 1):
+        d = nibbles[:, k]
+        step = IMA_STEPS[index]
+        diff = (step >> 3) + np.where(d & 4, step, 0) + np.where(d & 2, step >> 1, 0) + np.where(d & 1, step >> 2, 0)
+        pred = np.clip(np.where(d & 8, pred - diff, pred + diff), -32768, 32767)
+        index = np.clip(index + IMA_INDEX_STEPS[d & 7], 0, 88)
+        out[:, k + 1] = pred
+    return out.reshape(n_blocks * spb, channels)
+
+
 def _channels(x, ch, mono):
     """Interleaved samples -> the mono mix (numpy's float32 mean over a frame), or with mono=False the rows of the channels."""
     if ch > 1 and not mono:
@@ -115,6 +173,37 @@ def _fmt_chunk(body):
     if tag == 0xFFFE and len(body) >= 26:
         tag = struct.unpack("<H", body[24:26])[0]
     return tag, ch, sr, bits
+
+
+IMA_ADPCM_TAG = 0x0011
+
+
+def _fmt_ima_adpcm(body):
+    """The block fields of a tag-0x11 `fmt ` chunk -> (nBlockAlign, samples per block), checked: 4 bits per sample, and the
+    extension's wSamplesPerBlock, where there is one, must be what the block size gives."""
+    ch, block_bytes, bits = struct.unpack("<H", body[2:4])[0], struct.unpack("<H", body[12:14])[0], struct.unpack("<H", body[14:16])[0]
+    if bits != 4:
+        raise ValueError(f"unsupported IMA ADPCM width {bits}")
+    declared = struct.unpack("<H", body[18:20])[0] if len(body) >= 20 and struct.unpack("<H", body[16:18])[0] >= 2 else None
+    return block_bytes, ima_block_frames(max(int(ch), 1), block_bytes, declared)
+
+
+def _ima_frames(data_bytes, block_bytes, spb, fact):
+    """Frames of an IMA ADPCM data chunk: the `fact` chunk's count where the whole blocks can hold it, else all of theirs."""
+    most = data_bytes // block_bytes * spb
+    return fact if fact is not None and fact <= most else most
+
+
+def _fact_chunk(body):
+    return struct.unpack("<I", body[:4])[0] if len(body) >= 4 else None
+
+
+def piece_bytes(info, n):
+    """The bytes of `n` frames from the start of a piece of the file (a piece starts on a frame, of a block file on a block):
+    n * frame_bytes, or for a block encoding the whole blocks that hold them, ceil(n / block_frames) * block_bytes."""
+    if info.block_bytes:
+        return -(-n // info.block_frames) * info.block_bytes
+    return n * info.frame_bytes
 
 
 def _ds64_data_size(body):
@@ -151,10 +240,12 @@ def load_wav(path_or_file, mono=True):
     try:
         if not hasattr(f, "read"):
             f = io.BytesIO(f)
-        fmt, raw = None, None
+        fmt, raw, fmt_body, fact = None, None, None, None
         for cid, data in _read_chunks(f):
             if cid == b"fmt ":
-                fmt = _fmt_chunk(data)
+                fmt, fmt_body = _fmt_chunk(data), data
+            elif cid == b"fact":
+                fact = _fact_chunk(data)
             elif cid == b"data":
                 raw = data
         if fmt is None or raw is None:
@@ -163,6 +254,11 @@ def load_wav(path_or_file, mono=True):
         if isinstance(path_or_file, (str, bytes)):
             f.close()
     tag, ch, sr, bits = fmt
+    if tag == IMA_ADPCM_TAG:
+        ch = max(int(ch), 1)
+        block_bytes, spb = _fmt_ima_adpcm(fmt_body)
+        x = decode_ima_adpcm(raw, ch, block_bytes)[:_ima_frames(len(raw), block_bytes, spb, fact)]
+        return _channels(x.astype(np.float32).reshape(-1) / 32768.0, ch, mono), int(sr)
     return _channels(_decode(raw, _pcm_format(tag, bits)), ch, mono), int(sr)
 
 
@@ -180,14 +276,17 @@ def scan_wav(f):
     if len(header) < 12 or header[:4] not in WAVE_IDS or header[8:12] != b"WAVE":
         raise ValueError("not a RIFF/WAVE file")
     end = f.seek(0, 2)
-    pos, fmt, data, data_size = 12, None, None, None
+    pos, fmt, data, data_size, fmt_body, fact = 12, None, None, None, None, None
     while pos + 8 <= end:
         f.seek(pos)
         head = f.read(8)
         cid, size = head[:4], struct.unpack("<I", head[4:])[0]
         pos += 8
         if cid == b"fmt ":
-            fmt = _fmt_chunk(f.read(size))
+            fmt_body = f.read(size)
+            fmt = _fmt_chunk(fmt_body)
+        elif cid == b"fact":
+            fact = _fact_chunk(f.read(min(size, 4)))
         elif cid == b"ds64":
             data_size = _ds64_data_size(f.read(min(size, 16)))
         elif cid == b"data":
@@ -198,8 +297,11 @@ def scan_wav(f):
     if fmt is None or data is None:
         raise ValueError("missing fmt or data chunk")
     tag, ch, sr, bits = fmt
-    code = _pcm_format(tag, bits)
     ch = max(int(ch), 1)
+    if tag == IMA_ADPCM_TAG:
+        block_bytes, spb = _fmt_ima_adpcm(fmt_body)
+        return WavInfo(ENC_IMA_ADPCM, ch, int(sr), _ima_frames(data[1], block_bytes, spb, fact), 0, data[0], block_bytes, spb)
+    code = _pcm_format(tag, bits)
     frame_bytes = ch * BYTES_PER_SAMPLE[code]
     return WavInfo(code, ch, int(sr), data[1] // frame_bytes, frame_bytes, data[0])
 
@@ -348,7 +450,7 @@ def _read_raw(path_or_file, into, scan):
     f, ours = _opened(path_or_file)
     try:
         info = scan(f)
-        nbytes = info.n_frames * info.frame_bytes
+        nbytes = piece_bytes(info, info.n_frames)
         if into is None:
             into = bytearray(nbytes)
         view = memoryview(into).cast("B")
@@ -365,8 +467,9 @@ def _read_raw(path_or_file, into, scan):
 
 def read_wav_raw(path_or_file, into=None):
     """-> WavRaw(data, format, channels, sr, n_frames): the sample bytes of whole frames exactly as they sit in the data chunk
-    (a uint8 memoryview of n_frames * channels * bytes-per-sample bytes), `format` a wseg_sample_encoding code.  With `into` — a
-    caller's writable buffer, e.g. pinned memory — the bytes are read straight into it and `data` is a view of its front."""
+    (a uint8 memoryview of n_frames * channels * bytes-per-sample bytes; of an IMA ADPCM file the whole blocks that hold n_frames),
+    `format` a wseg_sample_encoding code or ENC_IMA_ADPCM.  With `into` — a caller's writable buffer, e.g. pinned memory — the
+    bytes are read straight into it and `data` is a view of its front."""
     return _read_raw(path_or_file, into, scan_wav)
 
 
@@ -377,8 +480,9 @@ def read_audio_raw(path_or_file, into=None):
 
 class DeviceIngest:
     """The device half of the ingest: pinned staging buffers, and `submit` = copy a filled buffer to the device and decode it
-    there (wseg_samples_to_mono_f32), stream-ordered on the current stream.  Every call belongs to the thread that owns the
-    device; a reader thread only ever writes into the arrays `acquire` handed out."""
+    there (wseg_samples_to_mono_f32; the blocks of an IMA ADPCM file: wseg_ima_adpcm_to_mono_f32 — submit, submit_planar and
+    StreamResampler.submit dispatch on info.format), stream-ordered on the current stream.  Every call belongs to the thread that
+    owns the device; a reader thread only ever writes into the arrays `acquire` handed out."""
 
     def __init__(self, device="cuda"):
         import torch
@@ -408,13 +512,21 @@ class DeviceIngest:
     def submit(self, view, nbytes, info, out, frame0, n_frames):
         """Decode `n_frames` frames whose `nbytes` bytes sit at the front of buffer `view` into out[frame0 : frame0 + n_frames]
         -> an event that has completed once the copy out of the buffer has, i.e. once the buffer may be written again."""
+        dst = out[frame0:frame0 + n_frames]
+        if info.format == ENC_IMA_ADPCM:
+            return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_ima_adpcm_to_mono_f32(
+                raw.data_ptr(), -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames),
+                dst.data_ptr(), self._lib.stream_ptr()))
         return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_mono_f32(
-            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), out[frame0:frame0 + n_frames].data_ptr(),
-            self._lib.stream_ptr()))
+            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst.data_ptr(), self._lib.stream_ptr()))
 
     def submit_planar(self, view, nbytes, info, out, frame0, n_frames, first_channel):
         """submit for the planes of new_planar_output: channels first_channel .. first_channel + out.shape[0] - 1 of the piece go
         to out[:, frame0 : frame0 + n_frames] (wseg_samples_to_planar_f32 with the whole recording's frame count as plane stride)."""
+        if info.format == ENC_IMA_ADPCM:
+            return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_ima_adpcm_to_planar_f32(
+                raw.data_ptr(), -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames),
+                int(first_channel), int(out.shape[0]), out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
         return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_planar_f32(
             raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(first_channel), int(out.shape[0]),
             out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
@@ -496,7 +608,14 @@ class StreamResampler:
 
         def decode_and_resample(raw):
             dst = seg.data_ptr() + 4 * (lead + kept)
-            if self.sel is None:
+            if info.format == ENC_IMA_ADPCM:
+                blocks = -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames)
+                if self.sel is None:
+                    status = lib.wseg_ima_adpcm_to_mono_f32(raw.data_ptr(), *blocks, dst, stream_ptr())
+                else:
+                    status = lib.wseg_ima_adpcm_to_planar_f32(raw.data_ptr(), *blocks, int(self.sel[0]), int(seg.shape[0]), dst, self.stride,
+                                                          stream_ptr())
+            elif self.sel is None:
                 status = lib.wseg_samples_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst, stream_ptr())
             else:
                 status = lib.wseg_samples_to_planar_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(self.sel[0]),
@@ -527,7 +646,21 @@ class StreamResampler:
 
 def chunk_plan(info, buffer_bytes, chunk_frames=None):
     """Frames per piece of a data chunk that goes through buffers of `buffer_bytes`: a multiple of 16 frames, so that every
-    piece starts on a multiple of 16 bytes (and of 16 output floats) whatever the frame size."""
+    piece starts on a multiple of 16 bytes (and of 16 output floats) whatever the frame size.  Of a block file (IMA ADPCM) a piece
+    is a multiple of 16 BLOCKS: a multiple of 16 raw bytes, the block size being one of 4, and of 16 frames; a file that fits the
+    buffer whole is one piece even where the buffer holds fewer than 16 blocks."""
+    if info.block_bytes:
+        unit = 16 * info.block_frames
+        fit = buffer_bytes // (16 * info.block_bytes) * unit
+        if piece_bytes(info, info.n_frames) <= buffer_bytes:
+            fit = max(fit, -(-max(info.n_frames, 1) // unit) * unit)
+        if fit < unit:
+            raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 blocks of {info.block_bytes} bytes")
+        if chunk_frames is not None:
+            if chunk_frames <= 0 or chunk_frames % unit:
+                raise ValueError(f"chunk_frames must be a positive multiple of 16 blocks = {unit} frames")
+            fit = min(fit, int(chunk_frames))
+        return fit
     fit = buffer_bytes // info.frame_bytes // 16 * 16
     if fit < 16:
         raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 frames of {info.frame_bytes} bytes")
@@ -584,7 +717,8 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     """load_audio on the GPU (any container of scan_audio) -> (float32 device tensor [n_frames], sampling_rate), the same samples bit
     for bit: sample bytes ->
     pinned staging -> non_blocking copy -> wseg_samples_to_mono_f32 on the current stream.  A data chunk larger than the staging
-    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.
+    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.  An IMA ADPCM file goes through as
+    its blocks (wseg_ima_adpcm_to_mono_f32 / _planar_f32), in pieces of a multiple of 16 blocks (`chunk_frames`: of 16 * block_frames).
     mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
     wseg_samples_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
     ignores it; negative k counts from the end, out of range raises IndexError.
@@ -597,8 +731,8 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
     try:
         info = scan_audio(f)
         check_channels(info)
-        total = info.n_frames * info.frame_bytes
-        views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * info.frame_bytes)))
+        total = piece_bytes(info, info.n_frames)
+        views = ingest.acquire(2, min(STAGING_BYTES, max(total, 16 * (info.block_bytes or info.frame_bytes))))
         step = chunk_plan(info, len(views[0]), chunk_frames)
         sel = select_channels(info, channel_id if channel_id is not None or mono else "all")
         target = info.sr if sr is None else sr
@@ -613,13 +747,14 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
             n = min(step, info.n_frames - frame0)
             if events[i % 2] is not None:
                 ingest.done(events[i % 2], wait=True)
-            _read_exact(f, views[i % 2][:n * info.frame_bytes])
+            nbytes = piece_bytes(info, n)
+            _read_exact(f, views[i % 2][:nbytes])
             if stream is not None:
-                events[i % 2] = stream.submit(views[i % 2], n * info.frame_bytes, frame0, n)
+                events[i % 2] = stream.submit(views[i % 2], nbytes, frame0, n)
             elif sel is None:
-                events[i % 2] = ingest.submit(views[i % 2], n * info.frame_bytes, info, out, frame0, n)
+                events[i % 2] = ingest.submit(views[i % 2], nbytes, info, out, frame0, n)
             else:
-                events[i % 2] = ingest.submit_planar(views[i % 2], n * info.frame_bytes, info, out, frame0, n, sel[0])
+                events[i % 2] = ingest.submit_planar(views[i % 2], nbytes, info, out, frame0, n, sel[0])
         for event in events:         # the buffers belong to the next call
             if event is not None:
                 ingest.done(event, wait=True)
@@ -708,7 +843,7 @@ class FilePipeline:
                         if view is None:
                             return
                         try:
-                            _read_exact(f, view[:n * info.frame_bytes])
+                            _read_exact(f, view[:piece_bytes(info, n)])
                         except BaseException:
                             self.free.put(view)
                             raise
@@ -751,19 +886,20 @@ class FilePipeline:
                 index, info, view, frame0, n, sel = item
                 if isinstance(info, BaseException):
                     raise _named(info, self.paths[index]) from info
+                nbytes = piece_bytes(info, n)
                 target = self.rates[index] if self.rates[index] is not None else info.sr
                 if frame0 == 0 and target != info.sr and info.n_frames and hasattr(self.ingest, "open_resampled"):
                     stream = self.ingest.open_resampled(info, sel, target, n)     # (a file's first piece is its longest)
                 if stream is not None:
-                    event = stream.submit(view, n * info.frame_bytes, frame0, n)
+                    event = stream.submit(view, nbytes, frame0, n)
                 elif sel is None:
                     if frame0 == 0:
                         out = self.ingest.new_output(info.n_frames)
-                    event = self.ingest.submit(view, n * info.frame_bytes, info, out, frame0, n)
+                    event = self.ingest.submit(view, nbytes, info, out, frame0, n)
                 else:
                     if frame0 == 0:
                         out = self.ingest.new_planar_output(sel[1], info.n_frames)
-                    event = self.ingest.submit_planar(view, n * info.frame_bytes, info, out, frame0, n, sel[0])
+                    event = self.ingest.submit_planar(view, nbytes, info, out, frame0, n, sel[0])
                 self.pending.append((view, event))
                 if frame0 + n >= info.n_frames:
                     if stream is not None:
