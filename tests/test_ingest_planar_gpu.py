@@ -139,6 +139,27 @@ def test_load_wav_device_planar_and_channel_id(gpu_lib, tmp_path):
     assert empty.shape == (3, 0)
 
 
+def test_load_wav_device_channel_id_all_gives_every_plane(gpu_lib):
+    """channel_id="all" is mono=False: the planes of load_wav(mono=False), not the first of them — from a sample file in five
+    pieces (the last one ragged), from an IMA ADPCM file whose `fact` count cuts the last block, and resampled piece by piece."""
+    import ima_adpcm_cases as IC
+    from whisperseg_amd.resample import resample
+    s16 = WC.make_wav("s16", 3, 300)
+    adpcm = IC.make_wav(2, 256, 5, cut=100)
+    for blob, kw, shape in ((s16, {"chunk_frames": 64}, (3, 300)), (adpcm, {"chunk_frames": 16 * IC.block_frames(2, 256)}, (2, 5 * 249 - 100))):
+        want, sr = load_wav(io.BytesIO(blob), mono=False)
+        assert want.shape == shape
+        got, got_sr = load_wav_device(io.BytesIO(blob), channel_id="all", **kw)
+        planes, _ = load_wav_device(io.BytesIO(blob), mono=False, **kw)
+        assert got_sr == sr and got.shape == shape and np.array_equal(bits(got.cpu().numpy()), bits(want))
+        assert torch.equal(got.view(torch.int32), planes.view(torch.int32))
+    want = resample(torch.from_numpy(load_wav(io.BytesIO(s16), mono=False)[0]).cuda(), 16000, 32000)
+    got, got_sr = load_wav_device(io.BytesIO(s16), channel_id="all", sr=32000, chunk_frames=64)
+    planes, _ = load_wav_device(io.BytesIO(s16), mono=False, sr=32000, chunk_frames=64)
+    assert got_sr == 32000 and got.shape == want.shape == (3, 600)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32)) and torch.equal(got.view(torch.int32), planes.view(torch.int32))
+
+
 @pytest.fixture(scope="module")
 def folder(tmp_path_factory):
     """meerkat_5s.wav as is; s16 stereo: the signal, and the signal reversed in time; s24 x 3 channels at twice the rate: the

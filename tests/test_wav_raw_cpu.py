@@ -10,6 +10,8 @@ import threading
 import numpy as np
 import pytest
 
+import audio_cases as AC
+import ima_adpcm_cases as IC
 import wav_cases as WC
 from conftest import GOLDEN
 from whisperseg_amd import wavio
@@ -232,3 +234,122 @@ def test_segment_files_raises_a_readers_error_with_the_files_name(tmp_path):
 def test_segment_files_of_nothing():
     seg = stub_segmenter(1 << 20)
     assert seg.segment_files([]) == [] and seg.host.acquired == [] and not reader_threads()
+
+
+# ---- the piece plan, as a table ---------------------------------------------------------------------------------------------------
+NO_16 = "chunk_frames must be a positive multiple of 16"
+MIB3 = (3 << 20) + 5
+# (frame_bytes, buffer_bytes, [chunk_plan for chunk_frames None / 16 / 40 / 0]); a str: the ValueError's message
+FRAME_PLANS = [
+    (1, 15, ["a staging buffer of 15 bytes does not hold 16 frames of 1 bytes"] * 4),
+    (1, 16, [16, 16, NO_16, NO_16]),
+    (1, MIB3, [3145728, 16, NO_16, NO_16]),
+    (6, 95, ["a staging buffer of 95 bytes does not hold 16 frames of 6 bytes"] * 4),
+    (6, 96, [16, 16, NO_16, NO_16]),
+    (6, MIB3, [524288, 16, NO_16, NO_16]),
+    (512, 8191, ["a staging buffer of 8191 bytes does not hold 16 frames of 512 bytes"] * 4),
+    (512, 8192, [16, 16, NO_16, NO_16]),
+    (512, MIB3, [6144, 16, NO_16, NO_16]),
+]
+# (channels, block_bytes, blocks in the file, frames cut off the last, buffer_bytes, [chunk_plan for chunk_frames None / 16 blocks /
+# 24 blocks / 0]); the files of 5 blocks fit a buffer of 5 blocks whole
+BLOCK_PLANS = [
+    (1, 256, 100000, 0, 4095, ["a staging buffer of 4095 bytes does not hold 16 blocks of 256 bytes"] * 4),
+    (1, 256, 100000, 0, 4096, [8080, 8080] + [NO_16 + " blocks = 8080 frames"] * 2),
+    (1, 256, 100000, 0, MIB3, [6205440, 8080] + [NO_16 + " blocks = 8080 frames"] * 2),
+    (2, 2048, 100000, 0, 32767, ["a staging buffer of 32767 bytes does not hold 16 blocks of 2048 bytes"] * 4),
+    (2, 2048, 100000, 0, 32768, [32656, 32656] + [NO_16 + " blocks = 32656 frames"] * 2),
+    (2, 2048, 100000, 0, MIB3, [3134976, 32656] + [NO_16 + " blocks = 32656 frames"] * 2),
+    (64, 512, 100000, 0, 8191, ["a staging buffer of 8191 bytes does not hold 16 blocks of 512 bytes"] * 4),
+    (64, 512, 100000, 0, 8192, [144, 144] + [NO_16 + " blocks = 144 frames"] * 2),
+    (64, 512, 100000, 0, MIB3, [55296, 144] + [NO_16 + " blocks = 144 frames"] * 2),
+    (2, 2048, 5, 0, 10239, ["a staging buffer of 10239 bytes does not hold 16 blocks of 2048 bytes"] * 4),
+    (2, 2048, 5, 0, 10240, [32656, 32656] + [NO_16 + " blocks = 32656 frames"] * 2),
+    (2, 2048, 5, 100, 10239, ["a staging buffer of 10239 bytes does not hold 16 blocks of 2048 bytes"] * 4),
+    (2, 2048, 5, 100, 10240, [32656, 32656] + [NO_16 + " blocks = 32656 frames"] * 2),
+]
+
+
+def plans(info, buffer_bytes, chunk_frames):
+    got = []
+    for c in chunk_frames:
+        try:
+            got.append(wavio.chunk_plan(info, buffer_bytes, c))
+        except ValueError as exc:
+            got.append(str(exc))
+    return got
+
+
+def test_chunk_plan_table():
+    """Values and messages of chunk_plan as it stood with one body for frames and one for blocks."""
+    for frame_bytes, buffer_bytes, want in FRAME_PLANS:
+        info = wavio.WavInfo(wavio.PCM_S16, 1, 16000, 10 ** 9, frame_bytes, 44)
+        assert plans(info, buffer_bytes, (None, 16, 40, 0)) == want, (frame_bytes, buffer_bytes)
+    for channels, block_bytes, n_blocks, cut, buffer_bytes, want in BLOCK_PLANS:
+        spb = wavio.ima_block_frames(channels, block_bytes)
+        info = wavio.WavInfo(wavio.ENC_IMA_ADPCM, channels, 16000, n_blocks * spb - cut, 0, 60, block_bytes, spb)
+        assert plans(info, buffer_bytes, (None, 16 * spb, 24 * spb, 0)) == want, (channels, block_bytes, n_blocks, cut, buffer_bytes)
+
+
+# ---- one chunk walk: load_wav, read_wav_raw and scan_wav on awkward files ---------------------------------------------------------
+def chunk(cid, body):
+    return cid + struct.pack("<I", len(body)) + body + b"\x00" * (len(body) % 2)
+
+
+def riff(*chunks):
+    return b"RIFF" + struct.pack("<I", 4 + sum(map(len, chunks))) + b"WAVE" + b"".join(chunks)
+
+
+def awkward_files():
+    """name -> (file, the WavInfo of its scan, the bytes read_wav_raw hands out)."""
+    rng = np.random.default_rng(11)
+    s16 = WC.sample_bytes("s16", WC.random_samples("s16", 3 * 50, rng))
+    f32 = WC.sample_bytes("f32", WC.random_samples("f32", 2 * 20, rng))
+    blocks = IC.random_blocks(2, 72, 3)
+    fmt = AC.wav_chunks(1, 16, 3, 16000)
+    return {
+        "two fmt chunks": (riff(AC.wav_chunks(1, 24, 2, 8000), fmt, chunk(b"data", s16)), wavio.WavInfo(1, 3, 16000, 50, 6, 68), s16),
+        "two data chunks": (riff(fmt, chunk(b"data", s16[:60]), chunk(b"data", s16)), wavio.WavInfo(1, 3, 16000, 50, 6, 112), s16),
+        "an odd chunk before data": (WC.wav_bytes("s16", 3, 16000, s16, junk_before_data=7), wavio.WavInfo(1, 3, 16000, 50, 6, 60), s16),
+        "ds64 and a trailing chunk": (AC.rf64_bytes("s16", 3, 16000, s16, trailing=AC.list_chunk(301)), wavio.WavInfo(1, 3, 16000, 50, 6, 80), s16),
+        "fact after data": (IC.wav_bytes(2, 11025, 72, blocks, trailing=chunk(b"fact", struct.pack("<I", 2 * 65 + 7))),
+                            wavio.WavInfo(wavio.ENC_IMA_ADPCM, 2, 11025, 2 * 65 + 7, 0, 48, 72, 65), blocks),
+        "float data that ends inside a sample": (WC.wav_bytes("f32", 2, 16000, f32[:-1]), wavio.WavInfo(4, 2, 16000, 19, 8, 44), f32[:19 * 8]),
+    }
+
+
+@pytest.mark.parametrize("name", list(awkward_files()))
+def test_load_wav_read_wav_raw_and_scan_wav_agree_on_awkward_files(name):
+    blob, info, data = awkward_files()[name]
+    assert wavio.scan_wav(io.BytesIO(blob)) == info == wavio.scan_audio(io.BytesIO(blob))
+    raw = read_wav_raw(io.BytesIO(blob))
+    assert tuple(raw[1:]) == tuple(info[:4]) and bytes(raw.data) == data == blob[info.offset:info.offset + len(data)]
+    if info.format == wavio.ENC_IMA_ADPCM:
+        restated = IC.floats(IC.audioop_decode(bytes(raw.data), raw.channels, info.block_bytes)[:raw.n_frames])
+    else:
+        restated = WC.restate(raw.data, raw.format, raw.channels, raw.n_frames)
+    assert restated.shape == (info.n_frames,)
+    for loader in (load_wav, wavio.load_audio):
+        if name == "float data that ends inside a sample":       # the loaders refuse it; the raw path gives the whole frames
+            with pytest.raises(ValueError, match="multiple of element size"):
+                loader(io.BytesIO(blob))
+            continue
+        want, sr = loader(io.BytesIO(blob))
+        assert sr == info.sr and np.array_equal(bits(want), bits(restated))
+        planes = loader(io.BytesIO(blob), mono=False)[0]
+        assert planes.shape == (info.channels, info.n_frames) and np.array_equal(bits(planes.mean(axis=0).astype(np.float32)), bits(want))
+
+
+def test_awkward_files_fail_with_one_message():
+    s16 = WC.sample_bytes("s16", [1, 2, 3, 4])
+    fmt = AC.wav_chunks(1, 16, 1, 16000)
+    cases = [(riff(fmt, AC.wav_chunks(2, 4, 1, 16000), chunk(b"data", s16)), "unsupported WAVE format tag 2"),      # the LAST fmt chunk counts
+             (riff(fmt, AC.wav_chunks(1, 12, 1, 16000), chunk(b"data", s16)), "unsupported PCM width 12"),
+             (riff(chunk(b"data", s16), chunk(b"fact", b"\x04\x00\x00\x00")), "missing fmt or data chunk"),
+             (riff(fmt, chunk(b"LIST", b"data" + s16)), "missing fmt or data chunk"),
+             (riff(fmt, chunk(b"data", s16))[:8] + b"WAVX", "not a RIFF/WAVE file")]
+    for blob, text in cases:
+        for call in (load_wav, read_wav_raw, wavio.scan_wav, wavio.load_audio):
+            with pytest.raises(ValueError) as exc:
+                call(io.BytesIO(blob))
+            assert str(exc.value) == text, call

@@ -83,13 +83,13 @@ int main() {
         std::printf("  a bad block size or channel count is accepted (%s)\n", msg); ++fails;
       }
       const int64_t n = (int64_t)1 << 40;
-      if (ima_adpcm_planar_check(ch, n, 0, ch, n, msg, sizeof(msg)) || ima_adpcm_planar_check(ch, n, ch - 1, 1, 0, msg, sizeof(msg)) ||
-          !rejected(ima_adpcm_planar_check(ch, n, ch, 1, n, msg, sizeof(msg)), "first_channel") ||
-          !rejected(ima_adpcm_planar_check(ch, n, -1, 1, n, msg, sizeof(msg)), "first_channel") ||
-          !rejected(ima_adpcm_planar_check(ch, n, 0, ch + 1, n, msg, sizeof(msg)), "n_out_channels") ||
-          !rejected(ima_adpcm_planar_check(ch, n, 0, 0, n, msg, sizeof(msg)), "n_out_channels") ||
-          !rejected(ima_adpcm_planar_check(ch, n, ch - 1, 2, n, msg, sizeof(msg)), "n_out_channels") ||
-          (ch > 1 && !rejected(ima_adpcm_planar_check(ch, n, 0, 2, n - 1, msg, sizeof(msg)), "plane_stride"))) {
+      if (planar_range_check(ch, n, 0, ch, n, msg, sizeof(msg)) || planar_range_check(ch, n, ch - 1, 1, 0, msg, sizeof(msg)) ||
+          !rejected(planar_range_check(ch, n, ch, 1, n, msg, sizeof(msg)), "first_channel") ||
+          !rejected(planar_range_check(ch, n, -1, 1, n, msg, sizeof(msg)), "first_channel") ||
+          !rejected(planar_range_check(ch, n, 0, ch + 1, n, msg, sizeof(msg)), "n_out_channels") ||
+          !rejected(planar_range_check(ch, n, 0, 0, n, msg, sizeof(msg)), "n_out_channels") ||
+          !rejected(planar_range_check(ch, n, ch - 1, 2, n, msg, sizeof(msg)), "n_out_channels") ||
+          (ch > 1 && !rejected(planar_range_check(ch, n, 0, 2, n - 1, msg, sizeof(msg)), "plane_stride"))) {
         std::printf("  a planar range is misjudged (%s)\n", msg); ++fails;
       }
       std::printf("%2d channels, blocks of %5d bytes (%6d frames): %d passes, rows %4d dwords apart, %3d blocks a group: %s\n", ch, (int)block_bytes,

@@ -1,6 +1,7 @@
 // The host arithmetic of the IMA ADPCM decode (wseg_ima_adpcm_to_mono_f32 / wseg_ima_adpcm_to_planar_f32), in one place: the
-// validation of a call and the launch plan the kernel of wseg_ingest.hip is started with.  Plain C++ with no HIP dependency, so that
-// a host-only program can run it under a sanitizer (tools/ima_adpcm_plan_check.cpp).
+// validation of a call and the launch plan the kernel of wseg_ingest.hip is started with — and planar_range_check, the argument
+// check of every planar entry point of that file.  Plain C++ with no HIP dependency, so that a host-only program can run it under
+// a sanitizer (tools/ima_adpcm_plan_check.cpp).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -61,8 +62,9 @@ inline int ima_adpcm_plan(int64_t n_blocks, int32_t block_bytes, int32_t channel
   return 0;
 }
 
-// The planar entry point's own arguments (after ima_adpcm_plan) -> 0, or -1 with the argument's name in msg.
-inline int ima_adpcm_planar_check(int32_t channels, int64_t n_frames, int32_t first_channel, int32_t n_out_channels, int64_t plane_stride,
+// The arguments every planar entry point has beside its mono sibling's — wseg_pcm_to_planar_f32 / wseg_samples_to_planar_f32 and,
+// after ima_adpcm_plan, wseg_ima_adpcm_to_planar_f32 — -> 0, or -1 with the argument's name in msg.
+inline int planar_range_check(int32_t channels, int64_t n_frames, int32_t first_channel, int32_t n_out_channels, int64_t plane_stride,
                                   char* msg, size_t msg_len) {
   if (first_channel < 0 || first_channel >= channels) {
     snprintf(msg, msg_len, "first_channel must be 0..%d (got %d)", (int)channels - 1, (int)first_channel);

@@ -16,6 +16,7 @@
 // n_frames % 4 frames are read byte by byte by one lane.  No LDS, no scratch; all indexing is 64-bit.
 // wseg_pcm_to_planar_f32 (further down) keeps the channels apart instead of averaging them, through an LDS image of a tile of frames.
 // wseg_ima_adpcm_to_mono_f32 / _planar_f32 (last) decode the one block codec of the ingest, IMA ADPCM: one sequential chain per lane.
+#include <type_traits>
 #include "wseg_common.h"
 #include "wseg_ima_adpcm_plan.h"
 
@@ -402,12 +403,26 @@ __global__ __launch_bounds__(256) void ima_adpcm_kernel(const void* __restrict__
 
 using namespace wseg;
 
-// The first checks of every entry point; the format / encoding check follows them and samples_to_mono / samples_to_planar do the rest.
-static bool head_ok(const char* fn, const void* raw, const float* out, int32_t channels) {
+// The first checks of every entry point, in this order (`what`: the name of its format / encoding argument, whose codes are
+// 0..last; nullptr: it has none); samples_to_mono / samples_to_planar / ima_adpcm_decode do the rest.
+static bool head_ok(const char* fn, const void* raw, const float* out, int32_t channels, const char* what = nullptr, int32_t code = 0,
+                    int32_t last = 0) {
   if (!raw || ((uintptr_t)raw & 15)) { set_error("%s: raw must be a 16-byte aligned device pointer", fn); return false; }
   if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return false; }
   if (channels < 1 || channels > 64) { set_error("%s: channels must be 1..64 (got %d)", fn, channels); return false; }
+  if (what && (code < 0 || code > last)) { set_error("%s: unknown %s %d", fn, what, code); return false; }
   return true;
+}
+
+// THE list of the encodings (wseg_sample_encoding): f(std::integral_constant<int, E>()) for the E that `code` is, so that f has
+// the encoding as a compile-time constant -> whether it is one of them.
+template <int... E>
+struct Encodings {};
+using AllEncodings = Encodings<WSEG_PCM_U8, WSEG_PCM_S16, WSEG_PCM_S24, WSEG_PCM_S32, WSEG_PCM_F32, WSEG_PCM_F64, WSEG_ENC_S8, WSEG_ENC_S16BE,
+                               WSEG_ENC_S24BE, WSEG_ENC_S32BE, WSEG_ENC_F32BE, WSEG_ENC_F64BE, WSEG_ENC_ULAW, WSEG_ENC_ALAW>;
+template <class F, int... E>
+static bool with_encoding(int code, F f, Encodings<E...>) {
+  return ((code == E && (f(std::integral_constant<int, E>()), true)) || ...);
 }
 
 // The remaining checks and the launch of wseg_pcm_to_mono_f32 / wseg_samples_to_mono_f32 (`fn`: the entry point's name for the
@@ -421,14 +436,7 @@ static int samples_to_mono(const char* fn, const void* raw, int64_t n_frames, in
   if (blocks > 8192) blocks = 8192;                // 32 workgroups per CU; longer streams take the grid stride
   const dim3 grid((unsigned)blocks);
   const int out_aligned = ((uintptr_t)out & 15) == 0;
-#define WSEG_MONO(F) case F: launch_pcm<F>(channels, grid, s, raw, n_frames, out, out_aligned); break
-  switch (code) {
-    WSEG_MONO(WSEG_PCM_U8); WSEG_MONO(WSEG_PCM_S16); WSEG_MONO(WSEG_PCM_S24); WSEG_MONO(WSEG_PCM_S32); WSEG_MONO(WSEG_PCM_F32);
-    WSEG_MONO(WSEG_PCM_F64); WSEG_MONO(WSEG_ENC_S8); WSEG_MONO(WSEG_ENC_S16BE); WSEG_MONO(WSEG_ENC_S24BE); WSEG_MONO(WSEG_ENC_S32BE);
-    WSEG_MONO(WSEG_ENC_F32BE); WSEG_MONO(WSEG_ENC_F64BE); WSEG_MONO(WSEG_ENC_ULAW);
-    default: launch_pcm<WSEG_ENC_ALAW>(channels, grid, s, raw, n_frames, out, out_aligned); break;
-  }
-#undef WSEG_MONO
+  with_encoding(code, [&](auto fmt) { launch_pcm<decltype(fmt)::value>(channels, grid, s, raw, n_frames, out, out_aligned); }, AllEncodings());
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }
@@ -437,15 +445,9 @@ static int samples_to_planar(const char* fn, const void* raw, int64_t n_frames, 
                              int32_t n_out_channels, float* out, int64_t plane_stride, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
   if (n_frames < 0) { set_error("%s: n_frames is negative", fn); return WSEG_ERR_INVALID; }
-  if (first_channel < 0 || first_channel >= channels) {
-    set_error("%s: first_channel must be 0..%d (got %d)", fn, channels - 1, first_channel); return WSEG_ERR_INVALID;
-  }
-  if (n_out_channels < 1 || n_out_channels > channels - first_channel) {
-    set_error("%s: n_out_channels must be 1..%d behind channel %d (got %d)", fn, channels - first_channel, first_channel, n_out_channels);
-    return WSEG_ERR_INVALID;
-  }
-  if (n_out_channels > 1 && plane_stride < n_frames) {
-    set_error("%s: plane_stride (%lld) is shorter than the %lld frames of a plane", fn, (long long)plane_stride, (long long)n_frames);
+  char msg[200];
+  if (planar_range_check(channels, n_frames, first_channel, n_out_channels, plane_stride, msg, sizeof(msg))) {
+    set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }
   if (n_frames == 0) return WSEG_OK;
@@ -453,45 +455,33 @@ static int samples_to_planar(const char* fn, const void* raw, int64_t n_frames, 
   if (blocks > kPlanarGridCap) blocks = kPlanarGridCap;
   const dim3 grid((unsigned)blocks);
   const long long stride = n_out_channels > 1 ? plane_stride : 0;
-#define WSEG_PLANAR(F) case F: hipLaunchKernelGGL((pcm_to_planar_kernel<F>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels, \
-                                                  (int)first_channel, (int)n_out_channels, out, stride); break
-  switch (code) {
-    WSEG_PLANAR(WSEG_PCM_U8); WSEG_PLANAR(WSEG_PCM_S16); WSEG_PLANAR(WSEG_PCM_S24); WSEG_PLANAR(WSEG_PCM_S32); WSEG_PLANAR(WSEG_PCM_F32);
-    WSEG_PLANAR(WSEG_PCM_F64); WSEG_PLANAR(WSEG_ENC_S8); WSEG_PLANAR(WSEG_ENC_S16BE); WSEG_PLANAR(WSEG_ENC_S24BE);
-    WSEG_PLANAR(WSEG_ENC_S32BE); WSEG_PLANAR(WSEG_ENC_F32BE); WSEG_PLANAR(WSEG_ENC_F64BE); WSEG_PLANAR(WSEG_ENC_ULAW);
-    default: hipLaunchKernelGGL((pcm_to_planar_kernel<WSEG_ENC_ALAW>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels,
-                                (int)first_channel, (int)n_out_channels, out, stride); break;
-  }
-#undef WSEG_PLANAR
+  with_encoding(code, [&](auto fmt) {
+    hipLaunchKernelGGL((pcm_to_planar_kernel<decltype(fmt)::value>), grid, dim3(256), 0, s, raw, (long long)n_frames, (int)channels, (int)first_channel,
+                       (int)n_out_channels, out, stride);
+  }, AllEncodings());
   WSEG_LAUNCH_CHECK();
   return WSEG_OK;
 }
 
 extern "C" int wseg_pcm_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, float* out, void* stream) {
-  if (!head_ok("wseg_pcm_to_mono_f32", raw, out, channels)) return WSEG_ERR_INVALID;
-  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_mono_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  if (!head_ok("wseg_pcm_to_mono_f32", raw, out, channels, "format", format, WSEG_PCM_F64)) return WSEG_ERR_INVALID;
   return samples_to_mono("wseg_pcm_to_mono_f32", raw, n_frames, channels, format, out, stream);
 }
 
 extern "C" int wseg_samples_to_mono_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding, float* out, void* stream) {
-  if (!head_ok("wseg_samples_to_mono_f32", raw, out, channels)) return WSEG_ERR_INVALID;
-  if (encoding < WSEG_PCM_U8 || encoding > WSEG_ENC_ALAW) { set_error("wseg_samples_to_mono_f32: unknown encoding %d", encoding); return WSEG_ERR_INVALID; }
+  if (!head_ok("wseg_samples_to_mono_f32", raw, out, channels, "encoding", encoding, WSEG_ENC_ALAW)) return WSEG_ERR_INVALID;
   return samples_to_mono("wseg_samples_to_mono_f32", raw, n_frames, channels, encoding, out, stream);
 }
 
 extern "C" int wseg_pcm_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t format, int32_t first_channel,
                                       int32_t n_out_channels, float* out, int64_t plane_stride, void* stream) {
-  if (!head_ok("wseg_pcm_to_planar_f32", raw, out, channels)) return WSEG_ERR_INVALID;
-  if (format < WSEG_PCM_U8 || format > WSEG_PCM_F64) { set_error("wseg_pcm_to_planar_f32: unknown format %d", format); return WSEG_ERR_INVALID; }
+  if (!head_ok("wseg_pcm_to_planar_f32", raw, out, channels, "format", format, WSEG_PCM_F64)) return WSEG_ERR_INVALID;
   return samples_to_planar("wseg_pcm_to_planar_f32", raw, n_frames, channels, format, first_channel, n_out_channels, out, plane_stride, stream);
 }
 
 extern "C" int wseg_samples_to_planar_f32(const void* raw, int64_t n_frames, int32_t channels, int32_t encoding, int32_t first_channel,
                                           int32_t n_out_channels, float* out, int64_t plane_stride, void* stream) {
-  if (!head_ok("wseg_samples_to_planar_f32", raw, out, channels)) return WSEG_ERR_INVALID;
-  if (encoding < WSEG_PCM_U8 || encoding > WSEG_ENC_ALAW) {
-    set_error("wseg_samples_to_planar_f32: unknown encoding %d", encoding); return WSEG_ERR_INVALID;
-  }
+  if (!head_ok("wseg_samples_to_planar_f32", raw, out, channels, "encoding", encoding, WSEG_ENC_ALAW)) return WSEG_ERR_INVALID;
   return samples_to_planar("wseg_samples_to_planar_f32", raw, n_frames, channels, encoding, first_channel, n_out_channels, out, plane_stride, stream);
 }
 
@@ -502,7 +492,7 @@ static int ima_adpcm_decode(const char* fn, const void* raw, int64_t n_blocks, i
   AdpcmPlan plan;
   char msg[200];
   if (ima_adpcm_plan(n_blocks, block_bytes, channels, n_frames, &plan, msg, sizeof(msg)) ||
-      (!mono && ima_adpcm_planar_check(channels, n_frames, first_channel, n_out_channels, plane_stride, msg, sizeof(msg)))) {
+      (!mono && planar_range_check(channels, n_frames, first_channel, n_out_channels, plane_stride, msg, sizeof(msg)))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }

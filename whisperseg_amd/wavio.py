@@ -5,7 +5,7 @@ demo.py:76-78).
 Containers (sniffed from the first 12 bytes; load_audio / scan_audio / read_audio_raw):
   RIFF/WAVE, RF64, BW64 — PCM 8/16/24/32-bit, IEEE float 32/64, G.711 A-law / u-law (tags 6 / 7), IMA / DVI ADPCM (tag 0x11,
       4 bits), WAVE_FORMAT_EXTENSIBLE; an RF64 / BW64 `ds64` chunk supplies the size of a `data` chunk whose own size field is
-      0xFFFFFFFF (load_wav / scan_wav / read_wav_raw are the WAVE-only functions the others call)
+      0xFFFFFFFF (load_wav / scan_wav / read_wav_raw refuse everything else; _walk_wav is the one walk over the chunks)
   AIFF / AIFF-C — big-endian PCM of 1..32 bits (8-bit signed); compression NONE / twos / sowt / `raw ` / fl32 / fl64 / ulaw / alaw
   AU (.snd) — u-law, A-law, 8/16/24/32-bit linear, float 32/64
 IMA ADPCM is the one compressed encoding that is read, and the one BLOCK codec: a block of nBlockAlign bytes holds, per channel, a
@@ -18,8 +18,10 @@ Integer samples are divided by 2^(bits-1) of their container width, G.711 codes 
 through the standard's int16 predictor (then / 2^15), which is how libsndfile (behind librosa) produces its floats: equality with
 it is by construction, not pinned by a test (soundfile is not in the image) — nor is libsndfile's treatment of `fact` and of a
 partial last block.
-load_wav / load_audio keep the native rate; the device path (load_wav_device, FilePipeline) takes `sr=` and resamples on the GPU
-(whisperseg_amd.resample), all planes of a file at once and piece by piece as the file is read (StreamResampler)."""
+load_wav / load_audio (one loader, _load, behind the container's header scan) keep the native rate; the device path
+(load_wav_device, FilePipeline: one piece loop each, both over a FileOutput, which decodes through DeviceIngest.decode) takes `sr=`
+and resamples on the GPU (whisperseg_amd.resample), all planes of a file at once and piece by piece as the file is read
+(StreamResampler)."""
 import collections
 import io
 import os
@@ -212,66 +214,12 @@ def _ds64_data_size(body):
     return struct.unpack("<Q", body[8:16])[0] if len(body) >= 16 else None
 
 
-def _read_chunks(f):
-    header = f.read(12)
-    if len(header) < 12 or header[:4] not in WAVE_IDS or header[8:12] != b"WAVE":
-        raise ValueError("not a RIFF/WAVE file")
-    data_size = None
-    while True:
-        head = f.read(8)
-        if len(head) < 8:
-            return
-        cid, size = head[:4], struct.unpack("<I", head[4:])[0]
-        if cid == b"data" and size == 0xFFFFFFFF and data_size is not None:
-            size = data_size         # RF64 / BW64: the real size; the walk goes on behind the samples
-        data = f.read(size)
-        if size % 2:
-            f.read(1)
-        if cid == b"ds64":
-            data_size = _ds64_data_size(data)
-        yield cid, data
-
-
-def load_wav(path_or_file, mono=True):
-    """-> (float32 mono ndarray, sampling_rate) of a RIFF/WAVE (RF64, BW64) file.  mono=False: the channels kept apart, float32
-    [channels, n_frames] (C-contiguous) for a file of two or more channels and [n_frames] for a one-channel file; every sample
-    converted as for the mono mix, before its mean."""
-    f = open(path_or_file, "rb") if isinstance(path_or_file, (str, bytes)) else path_or_file
-    try:
-        if not hasattr(f, "read"):
-            f = io.BytesIO(f)
-        fmt, raw, fmt_body, fact = None, None, None, None
-        for cid, data in _read_chunks(f):
-            if cid == b"fmt ":
-                fmt, fmt_body = _fmt_chunk(data), data
-            elif cid == b"fact":
-                fact = _fact_chunk(data)
-            elif cid == b"data":
-                raw = data
-        if fmt is None or raw is None:
-            raise ValueError("missing fmt or data chunk")
-    finally:
-        if isinstance(path_or_file, (str, bytes)):
-            f.close()
-    tag, ch, sr, bits = fmt
-    if tag == IMA_ADPCM_TAG:
-        ch = max(int(ch), 1)
-        block_bytes, spb = _fmt_ima_adpcm(fmt_body)
-        x = decode_ima_adpcm(raw, ch, block_bytes)[:_ima_frames(len(raw), block_bytes, spb, fact)]
-        return _channels(x.astype(np.float32).reshape(-1) / 32768.0, ch, mono), int(sr)
-    return _channels(_decode(raw, _pcm_format(tag, bits)), ch, mono), int(sr)
-
-
-# ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
-# load_wav above (load_audio further down, for every container) is the arithmetic's definition; what follows moves it to the
-# device: read_wav_raw / read_audio_raw hand out the sample bytes untouched, libwseg's wseg_samples_to_mono_f32 widens and
-# averages them with load_audio's float32 bits, and wseg_samples_to_planar_f32 widens the channels one asks for into planes
-# (load_audio(mono=False)'s rows).
-def scan_wav(f):
-    """load_wav's chunk walk over a seekable file without reading the samples -> WavInfo (offset: where the data chunk's bytes
-    start).  As in load_wav the last `fmt ` / `data` chunk counts, a chunk cut short by the end of the file is taken as far as it
-    goes, the size of a `data` chunk that says 0xFFFFFFFF comes from the `ds64` chunk in front of it, and the samples are cut to
-    whole frames."""
+def _walk_wav(f):
+    """THE chunk walk of a RIFF/WAVE (RF64, BW64) file, seeking from header to header -> (tag, channels, sr, bits) of the `fmt `
+    chunk, its body, the `fact` chunk's count (None without one), where the `data` chunk's bytes start and how many of them the
+    file holds.  The last `fmt ` / `data` chunk counts, a chunk cut short by the end of the file is taken as far as it goes,
+    an odd-sized chunk is followed by a pad byte, and the size of a `data` chunk that says 0xFFFFFFFF comes from the `ds64` chunk
+    in front of it (the walk goes on behind the samples)."""
     header = f.read(12)
     if len(header) < 12 or header[:4] not in WAVE_IDS or header[8:12] != b"WAVE":
         raise ValueError("not a RIFF/WAVE file")
@@ -297,13 +245,25 @@ def scan_wav(f):
     if fmt is None or data is None:
         raise ValueError("missing fmt or data chunk")
     tag, ch, sr, bits = fmt
-    ch = max(int(ch), 1)
+    return tag, max(int(ch), 1), int(sr), bits, fmt_body, fact, data[0], data[1]
+
+
+def _scan_wav_data(f):
+    """The header scan of a WAVE file for a loader -> (WavInfo, the bytes of the data chunk to decode): ALL the file holds of it,
+    not the whole frames alone, so that _decode refuses float data that ends inside a sample."""
+    tag, ch, sr, bits, fmt_body, fact, offset, data_bytes = _walk_wav(f)
     if tag == IMA_ADPCM_TAG:
         block_bytes, spb = _fmt_ima_adpcm(fmt_body)
-        return WavInfo(ENC_IMA_ADPCM, ch, int(sr), _ima_frames(data[1], block_bytes, spb, fact), 0, data[0], block_bytes, spb)
+        return WavInfo(ENC_IMA_ADPCM, ch, sr, _ima_frames(data_bytes, block_bytes, spb, fact), 0, offset, block_bytes, spb), data_bytes
     code = _pcm_format(tag, bits)
     frame_bytes = ch * BYTES_PER_SAMPLE[code]
-    return WavInfo(code, ch, int(sr), data[1] // frame_bytes, frame_bytes, data[0])
+    return WavInfo(code, ch, sr, data_bytes // frame_bytes, frame_bytes, offset), data_bytes
+
+
+def scan_wav(f):
+    """The header scan of a WAVE file (seekable) without reading the samples -> WavInfo (offset: where the data chunk's bytes
+    start; the samples are cut to whole frames, of an IMA ADPCM file to what `fact` and the whole blocks allow)."""
+    return _scan_wav_data(f)[0]
 
 
 # ---- AIFF / AIFF-C and AU: header scans; the samples are decoded by _decode (host) or the device entry points -----------------
@@ -395,39 +355,26 @@ def _scan_au(f):
     return _info(AU_ENCODINGS[encoding], ch, sr, None, available, offset)
 
 
-def scan_audio(f):
-    """scan_wav for every container: the header walk over a seekable file without reading the samples -> WavInfo (format: a
-    wseg_sample_encoding; offset: where the samples start in the file).  The container is sniffed from the first 12 bytes."""
+def _scan_audio_data(f):
+    """_scan_wav_data for every container, sniffed from the first 12 bytes; of AIFF and AU the whole frames are the bytes to decode."""
     start = f.tell()
     header = f.read(12)
     f.seek(start)
     if header[:4] in WAVE_IDS:
-        return scan_wav(f)
+        return _scan_wav_data(f)
     if header[:4] == b"FORM" and header[8:12] in (b"AIFF", b"AIFC"):
-        return _scan_aiff(f)
-    if header[:4] == b".snd":
-        return _scan_au(f)
-    raise ValueError("unknown audio container (not RIFF/WAVE, RF64, BW64, AIFF, AIFF-C or AU)")
+        info = _scan_aiff(f)
+    elif header[:4] == b".snd":
+        info = _scan_au(f)
+    else:
+        raise ValueError("unknown audio container (not RIFF/WAVE, RF64, BW64, AIFF, AIFF-C or AU)")
+    return info, info.n_frames * info.frame_bytes
 
 
-def load_audio(path_or_file, mono=True):
-    """load_wav for every container -> (float32 ndarray, sampling_rate): the definition of the arithmetic of the encodings WAVE
-    does not carry (signed 8-bit, big-endian PCM and floats; _decode has the float32 steps).  A WAVE file goes to load_wav."""
-    f, ours = _opened(path_or_file)
-    try:
-        start = f.tell()
-        header = f.read(12)
-        f.seek(start)
-        if header[:4] in WAVE_IDS:
-            return load_wav(f, mono=mono)
-        info = scan_audio(f)
-        raw = bytearray(info.n_frames * info.frame_bytes)
-        f.seek(info.offset)
-        _read_exact(f, memoryview(raw))
-    finally:
-        if ours:
-            f.close()
-    return _channels(_decode(bytes(raw), info.format), info.channels, mono), info.sr
+def scan_audio(f):
+    """scan_wav for every container: the header walk over a seekable file without reading the samples -> WavInfo (format: a
+    wseg_sample_encoding or ENC_IMA_ADPCM; offset: where the samples start in the file)."""
+    return _scan_audio_data(f)[0]
 
 
 def _opened(path_or_file):
@@ -437,6 +384,39 @@ def _opened(path_or_file):
     return (path_or_file if hasattr(path_or_file, "read") else io.BytesIO(path_or_file)), False
 
 
+def _load(path_or_file, mono, scan_data):
+    f, ours = _opened(path_or_file)
+    try:
+        info, nbytes = scan_data(f)
+        f.seek(info.offset)
+        raw = f.read(nbytes)
+    finally:
+        if ours:
+            f.close()
+    if info.format == ENC_IMA_ADPCM:
+        x = decode_ima_adpcm(raw, info.channels, info.block_bytes)[:info.n_frames].astype(np.float32).reshape(-1) / 32768.0
+    else:
+        x = _decode(raw, info.format)
+    return _channels(x, info.channels, mono), info.sr
+
+
+def load_wav(path_or_file, mono=True):
+    """-> (float32 mono ndarray, sampling_rate) of a RIFF/WAVE (RF64, BW64) file: a path, a seekable binary file or its bytes in a
+    buffer.  mono=False: the channels kept apart, float32 [channels, n_frames] (C-contiguous) for a file of two or more channels
+    and [n_frames] for a one-channel file; every sample converted as for the mono mix, before its mean."""
+    return _load(path_or_file, mono, _scan_wav_data)
+
+
+def load_audio(path_or_file, mono=True):
+    """load_wav for every container scan_audio knows: with _decode and decode_ima_adpcm the definition of the arithmetic that the
+    device path is held against."""
+    return _load(path_or_file, mono, _scan_audio_data)
+
+
+# ---- the same files, decoded on the GPU ----------------------------------------------------------------------------------
+# load_audio above is the arithmetic's definition; what follows moves it to the device: read_wav_raw / read_audio_raw hand out
+# the sample bytes untouched, libwseg's wseg_samples_to_mono_f32 widens and averages them with load_audio's float32 bits, and
+# wseg_samples_to_planar_f32 widens the channels one asks for into planes (load_audio(mono=False)'s rows).
 def _read_exact(f, view):
     got = 0
     while got < len(view):
@@ -480,9 +460,8 @@ def read_audio_raw(path_or_file, into=None):
 
 class DeviceIngest:
     """The device half of the ingest: pinned staging buffers, and `submit` = copy a filled buffer to the device and decode it
-    there (wseg_samples_to_mono_f32; the blocks of an IMA ADPCM file: wseg_ima_adpcm_to_mono_f32 — submit, submit_planar and
-    StreamResampler.submit dispatch on info.format), stream-ordered on the current stream.  Every call belongs to the thread that
-    owns the device; a reader thread only ever writes into the arrays `acquire` handed out."""
+    there (`decode`, which submit, submit_planar and StreamResampler.submit all go through), stream-ordered on the current stream.
+    Every call belongs to the thread that owns the device; a reader thread only ever writes into the arrays `acquire` handed out."""
 
     def __init__(self, device="cuda"):
         import torch
@@ -512,24 +491,30 @@ class DeviceIngest:
     def submit(self, view, nbytes, info, out, frame0, n_frames):
         """Decode `n_frames` frames whose `nbytes` bytes sit at the front of buffer `view` into out[frame0 : frame0 + n_frames]
         -> an event that has completed once the copy out of the buffer has, i.e. once the buffer may be written again."""
-        dst = out[frame0:frame0 + n_frames]
-        if info.format == ENC_IMA_ADPCM:
-            return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_ima_adpcm_to_mono_f32(
-                raw.data_ptr(), -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames),
-                dst.data_ptr(), self._lib.stream_ptr()))
-        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_mono_f32(
-            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst.data_ptr(), self._lib.stream_ptr()))
+        dst = out.data_ptr() + 4 * int(frame0)
+        return self._submit(view, nbytes, n_frames, lambda raw: self.decode(info, None, raw.data_ptr(), n_frames, dst, 0))
 
     def submit_planar(self, view, nbytes, info, out, frame0, n_frames, first_channel):
         """submit for the planes of new_planar_output: channels first_channel .. first_channel + out.shape[0] - 1 of the piece go
-        to out[:, frame0 : frame0 + n_frames] (wseg_samples_to_planar_f32 with the whole recording's frame count as plane stride)."""
+        to out[:, frame0 : frame0 + n_frames] (the whole recording's frame count is the plane stride)."""
+        sel, dst = (first_channel, out.shape[0]), out.data_ptr() + 4 * int(frame0)
+        return self._submit(view, nbytes, n_frames, lambda raw: self.decode(info, sel, raw.data_ptr(), n_frames, dst, out.shape[1]))
+
+    def decode(self, info, sel, raw, n_frames, dst, plane_stride):
+        """THE choice among libwseg's four decode entry points, launched on the current stream -> the call's status.  `n_frames`
+        frames from the start of a piece at device address `raw` go to float32 address `dst`: their mono mix for sel None
+        (wseg_samples_to_mono_f32; the blocks of an IMA ADPCM file: wseg_ima_adpcm_to_mono_f32), else the sel[1] planes from
+        channel sel[0] on, `plane_stride` floats apart (wseg_samples_to_planar_f32 / wseg_ima_adpcm_to_planar_f32)."""
+        lib, n, channels = self.lib, int(n_frames), int(info.channels)
         if info.format == ENC_IMA_ADPCM:
-            return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_ima_adpcm_to_planar_f32(
-                raw.data_ptr(), -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames),
-                int(first_channel), int(out.shape[0]), out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
-        return self._submit(view, nbytes, n_frames, lambda raw: self.lib.wseg_samples_to_planar_f32(
-            raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(first_channel), int(out.shape[0]),
-            out.data_ptr() + 4 * int(frame0), int(out.shape[1]), self._lib.stream_ptr()))
+            mono, planar = lib.wseg_ima_adpcm_to_mono_f32, lib.wseg_ima_adpcm_to_planar_f32
+            piece = raw, -(-n // info.block_frames), int(info.block_bytes), channels, n
+        else:
+            mono, planar = lib.wseg_samples_to_mono_f32, lib.wseg_samples_to_planar_f32
+            piece = raw, n, channels, int(info.format)
+        if sel is None:
+            return mono(*piece, dst, self._lib.stream_ptr())
+        return planar(*piece, int(sel[0]), int(sel[1]), dst, int(plane_stride), self._lib.stream_ptr())
 
     def resample(self, out, sr_in, sr_out):
         """whisperseg_amd.resample.resample of a decoded tensor ([n_frames] or planes) on the current stream, i.e. behind the decode
@@ -570,8 +555,8 @@ class StreamResampler:
     rate — [n_out], or [planes, n_out] for a planar selection — and ONE segment buffer of resample.stream_capacity frames per plane
     (plus up to 3 floats in front and a stride rounded up to four: see below).
     submit(), per piece and in the file's order, on the current stream and without a host synchronisation: the frames the next
-    outputs still need move to the front of the segment, the piece is decoded behind them (wseg_samples_to_mono_f32 /
-    wseg_samples_to_planar_f32 with the segment's stride as plane stride), and ONE wseg_resample_planar_range_f32 launch writes the
+    outputs still need move to the front of the segment, the piece is decoded behind them (DeviceIngest.decode
+    with the segment's stride as plane stride), and ONE wseg_resample_planar_range_f32 launch writes the
     outputs that have become computable, all planes at once (resample.stream_plan says which; a piece may add none).  Every output
     has the bits resample() gives it on the whole decoded recording.  result(): the output, once the last piece has been submitted.
     "The front" is 0 to 3 floats into the segment, such that the PIECE starts on a multiple of 16 bytes however many frames are
@@ -604,28 +589,15 @@ class StreamResampler:
         src, lead = self.lead + step["x_first"] - self.first, -kept % 4
         if kept + n_frames > self.capacity:
             raise RuntimeError(f"{kept} retained frames + a piece of {n_frames} exceed the segment's {self.capacity}")
-        lib, stream_ptr = ingest.lib, ingest._lib.stream_ptr
 
         def decode_and_resample(raw):
-            dst = seg.data_ptr() + 4 * (lead + kept)
-            if info.format == ENC_IMA_ADPCM:
-                blocks = -(-int(n_frames) // info.block_frames), int(info.block_bytes), int(info.channels), int(n_frames)
-                if self.sel is None:
-                    status = lib.wseg_ima_adpcm_to_mono_f32(raw.data_ptr(), *blocks, dst, stream_ptr())
-                else:
-                    status = lib.wseg_ima_adpcm_to_planar_f32(raw.data_ptr(), *blocks, int(self.sel[0]), int(seg.shape[0]), dst, self.stride,
-                                                          stream_ptr())
-            elif self.sel is None:
-                status = lib.wseg_samples_to_mono_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), dst, stream_ptr())
-            else:
-                status = lib.wseg_samples_to_planar_f32(raw.data_ptr(), int(n_frames), int(info.channels), int(info.format), int(self.sel[0]),
-                                                    int(seg.shape[0]), dst, self.stride, stream_ptr())
+            status = ingest.decode(info, self.sel, raw.data_ptr(), n_frames, seg.data_ptr() + 4 * (lead + kept), self.stride)
             if status or not step["m_count"]:
                 return status
-            return lib.wseg_resample_planar_range_f32(
+            return ingest.lib.wseg_resample_planar_range_f32(
                 seg.data_ptr() + 4 * lead, step["x_first"], kept + n_frames, self.stride, int(seg.shape[0]), int(info.n_frames),
                 self.taps.data_ptr(), int(self.taps.numel()), p["up"], p["down"], p["pre_pad"], p["pre_remove"], self.out.data_ptr(),
-                step["m_first"], step["m_count"], p["n_out"], stream_ptr())
+                step["m_first"], step["m_count"], p["n_out"], ingest._lib.stream_ptr())
 
         with ingest.torch.cuda.device(ingest.device):
             if kept and src != lead:
@@ -645,28 +617,21 @@ class StreamResampler:
 
 
 def chunk_plan(info, buffer_bytes, chunk_frames=None):
-    """Frames per piece of a data chunk that goes through buffers of `buffer_bytes`: a multiple of 16 frames, so that every
-    piece starts on a multiple of 16 bytes (and of 16 output floats) whatever the frame size.  Of a block file (IMA ADPCM) a piece
-    is a multiple of 16 BLOCKS: a multiple of 16 raw bytes, the block size being one of 4, and of 16 frames; a file that fits the
+    """Frames per piece of a data chunk that goes through buffers of `buffer_bytes`: a multiple of a UNIT of 16 frames, so that
+    every piece starts on a multiple of 16 bytes (and of 16 output floats) whatever the frame size.  Of a block file (IMA ADPCM)
+    the unit is 16 BLOCKS: a multiple of 16 raw bytes, the block size being one of 4, and of 16 frames; such a file that fits the
     buffer whole is one piece even where the buffer holds fewer than 16 blocks."""
-    if info.block_bytes:
-        unit = 16 * info.block_frames
-        fit = buffer_bytes // (16 * info.block_bytes) * unit
-        if piece_bytes(info, info.n_frames) <= buffer_bytes:
-            fit = max(fit, -(-max(info.n_frames, 1) // unit) * unit)
-        if fit < unit:
-            raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 blocks of {info.block_bytes} bytes")
-        if chunk_frames is not None:
-            if chunk_frames <= 0 or chunk_frames % unit:
-                raise ValueError(f"chunk_frames must be a positive multiple of 16 blocks = {unit} frames")
-            fit = min(fit, int(chunk_frames))
-        return fit
-    fit = buffer_bytes // info.frame_bytes // 16 * 16
-    if fit < 16:
-        raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 frames of {info.frame_bytes} bytes")
+    blocks = bool(info.block_bytes)
+    unit = 16 * info.block_frames if blocks else 16
+    name, size = ("blocks", info.block_bytes) if blocks else ("frames", info.frame_bytes)
+    fit = buffer_bytes // (16 * size) * unit
+    if blocks and piece_bytes(info, info.n_frames) <= buffer_bytes:
+        fit = max(fit, -(-max(info.n_frames, 1) // unit) * unit)
+    if fit < unit:
+        raise ValueError(f"a staging buffer of {buffer_bytes} bytes does not hold 16 {name} of {size} bytes")
     if chunk_frames is not None:
-        if chunk_frames <= 0 or chunk_frames % 16:
-            raise ValueError("chunk_frames must be a positive multiple of 16")
+        if chunk_frames <= 0 or chunk_frames % unit:
+            raise ValueError("chunk_frames must be a positive multiple of 16" + (f" blocks = {unit} frames" if blocks else ""))
         fit = min(fit, int(chunk_frames))
     return fit
 
@@ -679,7 +644,8 @@ def check_channels(info, name="wav"):
 def select_channels(info, channel_id):
     """What a caller's `channel_id` asks of a file -> None: the mono decode (channel_id None, or a one-channel file, whose
     `channel_id` is ignored as upstream's `if len(audio.shape) == 2` does), else (first_channel, n_channels) for the planar
-    decode: "all" is every channel, an int one channel by Python's indexing (IndexError when out of range)."""
+    decode: "all" is every channel (two or more, then), an int one channel by Python's indexing (IndexError when out of range):
+    a selection of ONE plane is an integer's, which is what FileOutput.result picks the single row by."""
     if channel_id is None or info.channels == 1:
         return None
     if isinstance(channel_id, str):
@@ -701,6 +667,43 @@ def check_rate(sr):
     return int(sr)
 
 
+class FileOutput:
+    """Where the pieces of ONE file go (load_wav_device and FilePipeline make one when a file's first piece is at hand, `target`
+    the rate asked for and `piece_frames` that piece's frame count, a file's longest): the choice among the ingest's stream
+    resampler — ingest.open_resampled(info, sel, target, piece_frames), for a file of frames that changes rate —, its mono output
+    (sel None: new_output / submit) and its planes (new_planar_output / submit_planar).  submit() hands every piece on, in the
+    file's order, and returns the event after which the piece's buffer may be rewritten.  result(), behind the last piece: the
+    tensor at the target rate — [n] for the mono mix and for the one plane an integer channel_id selected (select_channels gives
+    one plane to nothing else), otherwise the planes that were decoded.  An ingest without open_resampled has the file decoded
+    whole at its native rate and result() calls ingest.resample(decoded, native, target) once, all its planes in one call."""
+
+    def __init__(self, ingest, info, sel, target, piece_frames):
+        self.ingest, self.info, self.sel, self.stream = ingest, info, sel, None
+        self.rates = (info.sr, target) if target != info.sr and info.n_frames else None
+        if self.rates and hasattr(ingest, "open_resampled"):
+            self.stream = ingest.open_resampled(info, sel, target, piece_frames)
+        elif sel is None:
+            self.out = ingest.new_output(info.n_frames)
+        else:
+            self.out = ingest.new_planar_output(sel[1], info.n_frames)
+
+    def submit(self, view, nbytes, frame0, n):
+        if self.stream is not None:
+            return self.stream.submit(view, nbytes, frame0, n)
+        if self.sel is None:
+            return self.ingest.submit(view, nbytes, self.info, self.out, frame0, n)
+        return self.ingest.submit_planar(view, nbytes, self.info, self.out, frame0, n, self.sel[0])
+
+    def result(self):
+        out = self.out if self.stream is None else self.stream.result()
+        if self.sel is not None and self.sel[1] == 1:
+            out = out[0]
+        if self.stream is None and self.rates:
+            self.out = None                                   # (the native-rate tensor is let go of here)
+            out = self.ingest.resample(out, *self.rates)
+        return out
+
+
 _INGEST = {}
 
 
@@ -715,13 +718,12 @@ def device_ingest(device="cuda"):
 
 def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, channel_id=None, sr=None):
     """load_audio on the GPU (any container of scan_audio) -> (float32 device tensor [n_frames], sampling_rate), the same samples bit
-    for bit: sample bytes ->
-    pinned staging -> non_blocking copy -> wseg_samples_to_mono_f32 on the current stream.  A data chunk larger than the staging
-    buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.  An IMA ADPCM file goes through as
-    its blocks (wseg_ima_adpcm_to_mono_f32 / _planar_f32), in pieces of a multiple of 16 blocks (`chunk_frames`: of 16 * block_frames).
-    mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded by
-    wseg_samples_to_planar_f32.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file
-    ignores it; negative k counts from the end, out of range raises IndexError.
+    for bit: sample bytes -> pinned staging -> non_blocking copy -> DeviceIngest.decode on the current stream.  A data chunk larger
+    than the staging buffer (or than `chunk_frames` frames, a multiple of 16: for tests) goes through in pieces.  An IMA ADPCM file
+    goes through as its blocks, in pieces of a multiple of 16 blocks (`chunk_frames`: of 16 * block_frames).
+    mono=False: load_wav(..., mono=False) as a device tensor ([channels, n_frames]; [n_frames] for a one-channel file), decoded to
+    planes.  channel_id=k (implies mono=False): row k of that array, only that plane decoded; a one-channel file ignores it;
+    negative k counts from the end, out of range raises IndexError.  channel_id="all" is mono=False.
     sr=N: `librosa.load(..., sr=N)` — every piece is resampled on the device as soon as it is decoded (StreamResampler: one launch
     per piece for all planes, the bits of resample() on the whole decoded file, which is never held at its native rate) and N is the
     rate returned; None, the native rate or a file of no frames: nothing is resampled."""
@@ -736,11 +738,7 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
         step = chunk_plan(info, len(views[0]), chunk_frames)
         sel = select_channels(info, channel_id if channel_id is not None or mono else "all")
         target = info.sr if sr is None else sr
-        stream = None                # a file that changes rate is resampled as its pieces arrive: no native-rate tensor
-        if target != info.sr and info.n_frames:
-            stream = ingest.open_resampled(info, sel, target, min(step, info.n_frames))
-        else:
-            out = ingest.new_output(info.n_frames) if sel is None else ingest.new_planar_output(sel[1], info.n_frames)
+        output = FileOutput(ingest, info, sel, target, min(step, info.n_frames))
         events = [None, None]        # the next piece is read while the copy of the one before is in flight
         f.seek(info.offset)
         for i, frame0 in enumerate(range(0, info.n_frames, step)):
@@ -749,21 +747,14 @@ def load_wav_device(path_or_file, device="cuda", chunk_frames=None, mono=True, c
                 ingest.done(events[i % 2], wait=True)
             nbytes = piece_bytes(info, n)
             _read_exact(f, views[i % 2][:nbytes])
-            if stream is not None:
-                events[i % 2] = stream.submit(views[i % 2], nbytes, frame0, n)
-            elif sel is None:
-                events[i % 2] = ingest.submit(views[i % 2], nbytes, info, out, frame0, n)
-            else:
-                events[i % 2] = ingest.submit_planar(views[i % 2], nbytes, info, out, frame0, n, sel[0])
+            events[i % 2] = output.submit(views[i % 2], nbytes, frame0, n)
         for event in events:         # the buffers belong to the next call
             if event is not None:
                 ingest.done(event, wait=True)
     finally:
         if ours:
             f.close()
-    if stream is not None:
-        out = stream.result()
-    return (out if sel is None or channel_id is None else out[0]), target
+    return output.result(), target
 
 
 def _named(exc, path):
@@ -786,16 +777,16 @@ class FilePipeline:
     file's name; close() — also called when the iteration ends, fails or is abandoned — stops and joins the thread.
     `channel_id`: None — the mono mix, as above; an int — that channel of every multi-channel file ([n_frames]; one-channel files
     give their samples; out of range: IndexError with the file's name); "all" — what load_wav(p, mono=False) gives.  The planes
-    come from the ingest's new_planar_output / submit_planar, which the mono mix never calls.
+    come from the ingest's new_planar_output / submit_planar, which the mono mix never calls (FileOutput makes the choice, per file).
     `sr`: None — every file at its native rate; an int — the target rate of every file; a sequence with one entry per path (None
     entries: the native rate).  A file whose native rate differs from its target is yielded with the target rate.  An ingest with
     open_resampled (DeviceIngest) resamples it piece by piece — ingest.open_resampled(info, sel, target, piece_frames) when the
     file's first piece arrives, .submit(view, nbytes, frame0, n) for every piece in place of submit / submit_planar, .result()
     behind the last — so the file never exists at its native rate and the resampler runs while the reader reads on.  An ingest
-    that offers only `resample` is served as before: the file is decoded whole and resampled once its LAST piece has been
-    submitted — ingest.resample(decoded, native, target), all its planes in one call — and the native-rate tensor is dropped
-    there.  Neither is called otherwise (no `sr`, a file already at its target, a file of no frames), so an ingest without them
-    serves a pipeline that never resamples."""
+    that offers only `resample` has the file decoded whole and resampled once its LAST piece has been submitted —
+    ingest.resample(decoded, native, target), all its planes in one call — and the native-rate tensor is dropped there.  Neither
+    is called otherwise (no `sr`, a file already at its target, a file of no frames), so an ingest without them serves a pipeline
+    that never resamples."""
 
     def __init__(self, paths, ingest, buffer_bytes=STAGING_BYTES, n_buffers=2, channel_id=None, sr=None):
         self.paths, self.ingest, self.channel_id = list(paths), ingest, channel_id
@@ -878,7 +869,7 @@ class FilePipeline:
 
     def __iter__(self):
         try:
-            out = stream = None
+            output = None
             while self.thread is not None:
                 item = self._next_item()
                 if item is None:
@@ -886,29 +877,13 @@ class FilePipeline:
                 index, info, view, frame0, n, sel = item
                 if isinstance(info, BaseException):
                     raise _named(info, self.paths[index]) from info
-                nbytes = piece_bytes(info, n)
                 target = self.rates[index] if self.rates[index] is not None else info.sr
-                if frame0 == 0 and target != info.sr and info.n_frames and hasattr(self.ingest, "open_resampled"):
-                    stream = self.ingest.open_resampled(info, sel, target, n)     # (a file's first piece is its longest)
-                if stream is not None:
-                    event = stream.submit(view, nbytes, frame0, n)
-                elif sel is None:
-                    if frame0 == 0:
-                        out = self.ingest.new_output(info.n_frames)
-                    event = self.ingest.submit(view, nbytes, info, out, frame0, n)
-                else:
-                    if frame0 == 0:
-                        out = self.ingest.new_planar_output(sel[1], info.n_frames)
-                    event = self.ingest.submit_planar(view, nbytes, info, out, frame0, n, sel[0])
-                self.pending.append((view, event))
+                if frame0 == 0:
+                    output = FileOutput(self.ingest, info, sel, target, n)
+                self.pending.append((view, output.submit(view, piece_bytes(info, n), frame0, n)))
                 if frame0 + n >= info.n_frames:
-                    if stream is not None:
-                        out = stream.result()
-                    out = out if sel is None or self.channel_id == "all" else out[0]
-                    if stream is None and target != info.sr and info.n_frames:
-                        out = self.ingest.resample(out, info.sr, target)      # (the native-rate tensor is let go of here)
-                    yield out, target
-                    out = stream = None
+                    yield output.result(), target
+                    output = None
         finally:
             self.close()
 
