@@ -217,6 +217,34 @@ int wseg_ima_adpcm_to_planar_f32(const void* raw, int64_t n_blocks, int32_t bloc
                                  float* out, int64_t plane_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-segment acoustic measurements from the resident PCM: the table a segmenter's users compute next (level, peak frequency,
+ * centroid, bandwidth per detected call), taken on the device from the float32 samples the front-end saw.
+ * whisperseg_amd/measure.py::measure_host is the definition (numpy, float64); the FFT here is fp32, every sum fp64 in a fixed order:
+ * the same input gives the same bits on every run and for every grid size.
+ * bounds_host: HOST int64 [n_seg][2], the sample range [s0, s1) of every segment, 0 <= s0 <= s1 <= n (overlaps allowed; all time
+ * arithmetic is the caller's).  pcm: device float32 [n]; only samples of [s0, s1) are ever read.  n_fft 512 | 1024 | 2048 | 4096 |
+ * 8192; frames of n_fft samples start at s0 and lie n_fft / 4 apart, zero-filled from s1 on: one frame up to n_fft samples, else
+ * 1 + ceil((s1 - s0 - n_fft) / hop).  window, twiddle: the log-mel descriptor's tables for that n_fft (device [n_fft] periodic
+ * Hann, device [n_fft / 2][2] (cos, -sin)(2 pi k / n_fft)).  The band is the bins k_lo .. k_hi, 1 <= k_lo <= k_hi <= n_fft / 2.
+ * out: device float32 [n_seg][8], a row per segment, RATE-FREE (no sampling rate enters the call):
+ *   0 max |x|   1 sqrt(mean x^2)   2 sign changes between neighbours inside the range, a count   3 lowest bin of the band's maximum
+ *   4 centroid, 5 / 6 the 5 % / 95 % points of the band's cumulated power interpolated inside the crossing bin, in bins
+ *   7 entropy of the band's normalised power / ln(bins of the band)
+ * s1 == s0: eight NaN; a band without power: NaN in 3..7.  Nothing outside the n_seg rows is written.
+ * scratch: device, 8-byte aligned, wseg_measure_scratch_bytes(bounds_host, n_seg, n_fft) bytes — host arithmetic, no device; it
+ * returns 0 with the reason in wseg_last_error() for invalid bounds (it knows no n: s1 up to 2^52), n_seg < 0 or another n_fft.
+ * The call copies what the kernels need of the bounds through a pinned buffer of the library's on the stream and waits for
+ * nothing: bounds_host may be reused on return.  n_seg == 0 returns 0 without a launch.  Every argument is validated on the host
+ * before a launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered.
+ * $WSEG_MEASURE_GRID: a TEST knob, the cap on the first kernel's grid (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_measure_scratch_bytes(const int64_t* bounds_host, int32_t n_seg, int32_t n_fft);
+int wseg_measure_segments_f32(const float* pcm, int64_t n, const int64_t* bounds_host, int32_t n_seg,
+                              int32_t n_fft, int32_t k_lo, int32_t k_hi, const float* window, const float* twiddle,
+                              void* scratch, size_t scratch_bytes, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

@@ -15,6 +15,8 @@ demo.py:76-78) segments one channel of multi-channel recordings instead of their
 of that channel (a one-channel file gives its samples) — or `all`: every channel, with a `channel` column behind `filename`.
 --sr N (`librosa.load(..., sr=N)` of the same entry points) resamples every recording to N Hz on the GPU before it is segmented,
 whatever --channel_id says; absent, recordings keep their native rate, as in the reference's CLI.
+--measure appends eight acoustic measurements of every row behind the existing columns (whisperseg_amd.measure.COLUMNS: level,
+zero-crossing rate, peak / centroid / 5 % / 95 % frequency, spectral entropy), taken on the GPU from the samples the rows were cut from.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -28,6 +30,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
+from whisperseg_amd.measure import COLUMNS as MEASURE_COLUMNS  # noqa: E402
 from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
 
 
@@ -61,6 +64,8 @@ def build_parser():
                    help="resample every recording to this rate (Hz) on the GPU before segmenting; absent: the native rate")
     p.add_argument("--audio_ext", default=None, nargs="+", metavar="EXT",
                    help="folder mode: the file extensions to look for, each as *.ext then *.EXT, in this order; absent: wav")
+    p.add_argument("--measure", action="store_true",
+                   help="append the eight per-segment measurements (peak_amplitude .. spectral_entropy) to every row")
     return p
 
 
@@ -79,16 +84,19 @@ def write_csv(columns, rows, dest):
         w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
-def table(results, names=None, all_channels=False):
+def table(results, names=None, all_channels=False, measure=False):
     """-> (columns, rows) of the CSV.  `results`: one prediction dict per recording, or with all_channels one LIST of dicts (one
     per channel) per recording, which adds the `channel` column; `names`: the recordings' file names for the `filename` column
-    (folder mode).  Rows run in file, channel, row order."""
+    (folder mode); `measure`: the dicts carry the eight measurement columns, appended behind `cluster`.  Rows run in file, channel,
+    row order."""
     columns = (["filename"] if names is not None else []) + (["channel"] if all_channels else []) + ["onset", "offset", "cluster"]
+    extra = list(MEASURE_COLUMNS) if measure else []
+    columns += extra
     rows = []
     for i, res in enumerate(results):
         for channel, r in enumerate(res if all_channels else [res]):
             head = ((names[i],) if names is not None else ()) + ((channel,) if all_channels else ())
-            rows += [head + (on, off, c) for on, off, c in zip(r["onset"], r["offset"], r["cluster"])]
+            rows += [head + row for row in zip(r["onset"], r["offset"], r["cluster"], *(r[name] for name in extra))]
     return columns, rows
 
 
@@ -113,7 +121,7 @@ def main(argv=None):
     except Exception:
         segmenter = WhisperSegmenter(args.model_path, device=args.device, device_ids=args.device_ids)
     kwargs = dict(min_frequency=args.min_frequency, spec_time_step=args.spec_time_step, num_trials=args.num_trials,
-                  batch_size=args.batch_size)
+                  batch_size=args.batch_size, **({"measure": True} if args.measure else {}))      # (absent: the calls as they were)
     rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
@@ -122,10 +130,10 @@ def main(argv=None):
         # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
         # a large folder needs no more memory than a small one
         results = segmenter.segment_files(paths, **({} if args.channel_id is None else {"channel_id": args.channel_id}), **rate, **kwargs)
-        columns, rows = table(results, [os.path.basename(p) for p in paths], args.channel_id == "all")
+        columns, rows = table(results, [os.path.basename(p) for p in paths], args.channel_id == "all", measure=args.measure)
     elif args.channel_id is None:
         audio, sr = stdin_wav(args.sr) if args.audio_path == "-" else load_wav_device(args.audio_path, **rate)
-        columns, rows = table([segmenter.segment(audio, sr, **kwargs)])
+        columns, rows = table([segmenter.segment(audio, sr, **kwargs)], measure=args.measure)
     else:
         if args.audio_path == "-":       # the channels kept apart on the host, and the reference's selection (`audio[channel_id]` of a 2-D array)
             audio, sr = stdin_wav(args.sr, args.channel_id)
@@ -134,9 +142,9 @@ def main(argv=None):
         else:
             audio, sr = load_wav_device(args.audio_path, channel_id=args.channel_id, **rate)
         if args.channel_id == "all":
-            columns, rows = table([segmenter.segment_channels(audio, sr, **kwargs)], all_channels=True)
+            columns, rows = table([segmenter.segment_channels(audio, sr, **kwargs)], all_channels=True, measure=args.measure)
         else:
-            columns, rows = table([segmenter.segment(audio, sr, **kwargs)])
+            columns, rows = table([segmenter.segment(audio, sr, **kwargs)], measure=args.measure)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()
         write_csv(columns, rows, buf)

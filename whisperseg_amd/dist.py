@@ -127,14 +127,23 @@ def _resolve(segmenter, min_frequency, spec_time_step, min_segment_length, eps, 
     return min_frequency, spec_time_step, min_segment_length, eps, frame
 
 
+def _refuse_measure(kwargs, name):
+    """The per-segment measurements of segment(measure=True) run on the device PCM the rows were cut from; here only rank 0
+    holds the rows and not every rank holds the PCM: not offered, and refused on every rank before any collective."""
+    if kwargs.get("measure"):
+        raise ValueError(f"{name} does not measure segments (measure=True): measure the returned rows with "
+                         "whisperseg_amd.measure.measure(audio, sr, prediction) on one device")
+
+
 def segment_distributed(segmenter, audio, sr, decode_shard=None, **kwargs):
     """segment() of one recording with its windows sharded over the ranks of the default group.
 
     Every rank must call this; rank 0 supplies `audio` (other ranks may pass None).  Returns the
     prediction dict on every rank.  `decode_shard(sliced_shard, **gen) -> (tokens, lengths)` defaults to
     the segmenter's engine (tests inject a CPU stand-in to exercise the collectives under gloo).  Keyword arguments are
-    segment()'s (model.py:397-470), with segment()'s None-defaults."""
+    segment()'s (model.py:397-470), with segment()'s None-defaults — except `measure`, see _refuse_measure."""
     from . import postprocess
+    _refuse_measure(kwargs, "segment_distributed")
     from .audio_utils import get_n_fft_given_sr
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -201,8 +210,10 @@ def segment_batch_distributed(segmenter, audios, srs=None, decode_shard=None, **
     rates, resolved parameters: a small pickled list, broadcast), (2) PCM point-to-point from rank 0 to the ranks whose
     windows read it, (3) all_gather of token ids + lengths.  Every rank then holds all tokens and parses every recording
     (host work, milliseconds); returns the list of prediction dicts on every rank, equal to per-file segment().
-    `pool_windows` (default model.POOL_WINDOWS): recordings are processed in groups of at most ~pool_windows x world windows."""
+    `pool_windows` (default model.POOL_WINDOWS): recordings are processed in groups of at most ~pool_windows x world windows.
+    `measure=True` is refused (_refuse_measure)."""
     from . import postprocess
+    _refuse_measure(kwargs, "segment_batch_distributed")
     from .audio_utils import get_n_fft_given_sr
     from .model import _per_item
     from .windows import window_table

@@ -119,14 +119,17 @@ class SegmenterBase:
         self._ingest = None
 
     # ---- slicing + features (reference model.py:127-166), batched on the first device ------------
-    def get_sliced_audios_features(self, audio, sr, min_frequency, spec_time_step, num_trials):
+    def get_sliced_audios_features(self, audio, sr, min_frequency, spec_time_step, num_trials, pcm_out=None):
         """-> list of (trial_id, offset_time, features, clip_seconds); `features` is a float32 [80, 1000]
-        DEVICE tensor (a view into one batch tensor) instead of a numpy array."""
+        DEVICE tensor (a view into one batch tensor) instead of a numpy array.  `pcm_out`: a list that receives the device
+        PCM the front-end read (what measure=True measures the rows on)."""
         device = self.device_list[0]
         if torch.is_tensor(audio):      # already a tensor (e.g. straight out of whisperseg_amd.resample): no host round trip
             pcm = audio.to(device=device, dtype=torch.float32).contiguous()
         else:
             pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).to(device, non_blocking=True)
+        if pcm_out is not None:
+            pcm_out.append(pcm)
         out = self.sliced_features_from_device_pcm(pcm, sr, min_frequency, spec_time_step, num_trials)
         return out["shard"]
 
@@ -289,22 +292,34 @@ class SegmenterBase:
     @torch.no_grad()
     def segment(self, audio, sr, min_frequency=None, spec_time_step=None, min_segment_length=None, eps=None,
                 time_per_frame_for_voting=None, consolidation_method="clustering", max_length=448, batch_size=4,
-                num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None):
+                num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False):
+        """`measure=True`: every prediction dict additionally carries the eight columns of whisperseg_amd.measure.COLUMNS as
+        lists aligned with `onset` — level, peak frequency, centroid, 5 % / 95 % frequencies and entropy of every returned row,
+        measured on the GPU from the device PCM the front-end read, in the band min_frequency .. sr / 2."""
         min_frequency, spec_time_step, min_segment_length, eps, time_per_frame_for_voting = self.resolve_segmentation_params(
             min_frequency, spec_time_step, min_segment_length, eps, time_per_frame_for_voting)
-        sliced = self.get_sliced_audios_features(audio, sr, min_frequency, spec_time_step, num_trials)
+        held = [] if measure else None      # (absent: the call as it was)
+        sliced = self.get_sliced_audios_features(audio, sr, min_frequency, spec_time_step, num_trials,
+                                                 **({"pcm_out": held} if measure else {}))
         texts = self.generate_segment_text(sliced, batch_size, max_length, num_beams, top_k, top_p, length_penalty,
                                            status_monitor)
         prediction = self.parse_generation(texts, sliced, min_segment_length, len(audio) / sr, spec_time_step,
                                            num_trials, eps, time_per_frame_for_voting, consolidation_method)
         prediction = postprocess.correct_fft_blur(prediction, get_n_fft_given_sr(sr), sr)
-        return postprocess.drop_consecutive_duplicates(prediction)
+        prediction = postprocess.drop_consecutive_duplicates(prediction)
+        return self._measured(prediction, held[0], sr, min_frequency) if measure else prediction
+
+    @staticmethod
+    def _measured(prediction, pcm, sr, min_frequency):
+        """The final rows of a recording + their measurements on its device PCM (one launch pair; only the rows come back)."""
+        from . import measure as M
+        return M.with_columns(prediction, M.measure(pcm, sr, prediction, min_frequency=min_frequency))
 
     # ---- many recordings at once (SURVEY §8f rank 3: continuous batching across files) -----------------
     @torch.no_grad()
     def segment_batch(self, audios, srs=None, min_frequency=None, spec_time_step=None, min_segment_length=None, eps=None,
                       time_per_frame_for_voting=None, consolidation_method="clustering", max_length=448, batch_size=4,
-                      num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None):
+                      num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False):
         """segment() for a list of recordings with their windows POOLED into shared decode batches.
 
         The reference batches only inside one file (model.py:653) and its folder mode is a serial loop
@@ -319,6 +334,8 @@ class SegmenterBase:
         1 or 3 trials).  The front-end runs per recording with its own (sr, spec_time_step, min_frequency) filterbank; the
         windows of all recordings — every one a [80, 1000] log-mel image whatever its rate — share ONE pooled decode.
         The decode parameters (max_length, num_beams, top_k, top_p, length_penalty) are per call.
+        `measure=True` as in segment(): a group keeps the device PCM of its recordings until its rows exist, measures them there
+        and frees the PCM with the group (device memory stays bounded by POOL_WINDOWS; nothing is read twice).
         Returns a list of prediction dicts."""
         if srs is None:
             pairs = iter(audios)
@@ -342,16 +359,18 @@ class SegmenterBase:
                 pred = self.parse_generation(mine, g["windows"], g["min_segment_length"], g["duration"], g["spec_time_step"],
                                              g["num_trials"], g["eps"], g["frame"], g["method"])
                 pred = postprocess.correct_fft_blur(pred, get_n_fft_given_sr(g["sr"]), g["sr"])
-                out.append(postprocess.drop_consecutive_duplicates(pred))
+                pred = postprocess.drop_consecutive_duplicates(pred)
+                out.append(self._measured(pred, g["pcm"], g["sr"], g["min_frequency"]) if measure else pred)
             group, pending = [], 0
 
         # recordings are pooled in bounded groups (~POOL_WINDOWS windows): features of a group are freed before the next
         # group is cut, so a large folder needs no more device memory than a small one
         for (audio, sr), mf, sts, msl, e, tpf, nt, method in zip(pairs, *per_item):
             mf, sts, msl, e, tpf = self.resolve_segmentation_params(mf, sts, msl, e, tpf)
-            windows = self.get_sliced_audios_features(audio, sr, mf, sts, nt)
+            held = [] if measure else None
+            windows = self.get_sliced_audios_features(audio, sr, mf, sts, nt, **({"pcm_out": held} if measure else {}))
             group.append(dict(duration=len(audio) / sr, sr=sr, windows=windows, spec_time_step=sts, min_segment_length=msl, eps=e,
-                              frame=tpf, num_trials=nt, method=method))
+                              frame=tpf, num_trials=nt, method=method, **({"pcm": held[0], "min_frequency": mf} if measure else {})))
             pending += len(windows)
             if pending >= POOL_WINDOWS:
                 flush()
@@ -369,7 +388,8 @@ class SegmenterBase:
     def segment_channels(self, audio, sr, **segment_kwargs):
         """segment() of every channel of a recording kept apart (`librosa.load(..., mono=False)` upstream, wavio.load_wav(mono=False)
         / load_wav_device(mono=False) here): `audio` is [channels, n] (numpy or a device tensor) or 1-D -> a list with one
-        prediction dict per channel.  Computed as segment_batch over the rows: the windows of all channels share one pooled decode."""
+        prediction dict per channel.  Computed as segment_batch over the rows: the windows of all channels share one pooled decode.
+        `measure=True` (segment_batch's) measures every channel's rows on that channel's plane."""
         if getattr(audio, "ndim", None) not in (1, 2):
             raise ValueError("audio must be [n] or [channels, n]")
         return self.segment_batch([audio] if audio.ndim == 1 else list(audio), sr, **segment_kwargs)
@@ -388,7 +408,9 @@ class SegmenterBase:
         `sr` (`librosa.load(..., sr=sr)` upstream): the rate the files are segmented at — an int, or a list with one entry per
         FILE (None entries: the native rate), under every `channel_id`.  A file at another rate is resampled on the device piece by
         piece as it is decoded, all its planes in one launch per piece (wseg_resample_planar_range_f32: no native-rate copy of the
-        file), and the front-end sees the target rate."""
+        file), and the front-end sees the target rate.
+        `measure=True` (segment_batch's): the rows are measured on the decoded — with `sr`, the resampled — device PCM of their file,
+        or of their channel's plane; no file is read twice and no PCM comes back to the host."""
         paths = list(paths)
         if not paths:
             return []
