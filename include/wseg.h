@@ -245,6 +245,29 @@ int wseg_measure_segments_f32(const float* pcm, int64_t n, const int64_t* bounds
                               void* scratch, size_t scratch_bytes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-segment log-mel patches from the resident PCM: one fixed-size picture per detected call (clustering, embedding, thumbnails),
+ * time-normalised — `width` frames per segment at the segment's own spacing.  whisperseg_amd/patches.py::patches_host is the
+ * definition (numpy, float64): column c of the segment [s0, s1), L = s1 - s0, is the frame of n_fft samples centred on
+ * s0 + ((2c + 1) L) / (2 width) (integers), every index outside [0, n) read as zero (no reflection; the frame does see the
+ * recording outside the segment); periodic Hann -> |rfft|^2 -> the descriptor's mel bank -> log10(max(1e-10, .)) ->
+ * (max(v, V - 8) + 4) / 4 with V the picture's maximum.  FFT and mel projection are fp32 in a fixed order: the same bits on every
+ * run, for every grid size, and for a segment whatever other segments share the call.
+ * d: the log-mel descriptor (hop and n_cols are not read; n_fft 512 .. 8192, n_mels 1 .. 96).  bounds_host: HOST int64 [n_seg][2],
+ * 0 <= s0 <= s1 <= n (overlaps allowed; all time arithmetic is the caller's).  pcm: device float32 [n], may be null only when
+ * n == 0; no sample outside [0, n) is read.  width 1 .. 256.  out: device float32 [n_seg][n_mels][width]; nothing outside it is
+ * written.  scratch: device, 8-byte aligned, wseg_patches_scratch_bytes(n_seg, n_mels, width) bytes — host arithmetic, no device;
+ * 0 with the reason in wseg_last_error() for n_seg < 0 or n_mels / width out of range.
+ * The call copies the bounds through a pinned buffer of the library's on the stream and waits for nothing: bounds_host may be
+ * reused on return.  n_seg == 0 returns 0 without a launch.  Every argument is validated on the host before a launch
+ * (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered.
+ * $WSEG_PATCH_GRID: a TEST knob, the cap on both kernels' grids (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_patches_scratch_bytes(int32_t n_seg, int32_t n_mels, int32_t width);
+int wseg_patches_f32(const wseg_logmel_desc* d, const float* pcm, int64_t n, const int64_t* bounds_host, int32_t n_seg,
+                     int32_t width, void* scratch, size_t scratch_bytes, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

@@ -17,6 +17,9 @@ of that channel (a one-channel file gives its samples) — or `all`: every chann
 whatever --channel_id says; absent, recordings keep their native rate, as in the reference's CLI.
 --measure appends eight acoustic measurements of every row behind the existing columns (whisperseg_amd.measure.COLUMNS: level,
 zero-crossing rate, peak / centroid / 5 % / 95 % frequency, spectral entropy), taken on the GPU from the samples the rows were cut from.
+--patches W --patches_save_path FILE.npz (each needs the other) saves one time-normalised log-mel picture of W columns per row
+(whisperseg_amd.patches, computed on the GPU from the same samples): `patch` float32 [rows, 80, W] in the CSV's row order, with `onset`,
+`offset`, `cluster` and, where the CSV has those columns, `filename` / `channel`.  The CSV is what it is without the flags.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -66,7 +69,23 @@ def build_parser():
                    help="folder mode: the file extensions to look for, each as *.ext then *.EXT, in this order; absent: wav")
     p.add_argument("--measure", action="store_true",
                    help="append the eight per-segment measurements (peak_amplitude .. spectral_entropy) to every row")
+    p.add_argument("--patches", default=None, type=int, metavar="W",
+                   help="save one log-mel picture of W columns (1 .. 256) per row to --patches_save_path")
+    p.add_argument("--patches_save_path", default=None, metavar="FILE.npz", help="where --patches W saves the pictures (numpy .npz)")
     return p
+
+
+def parse_args(argv=None):
+    """The parsed arguments; --patches and --patches_save_path without each other, or a width outside 1 .. 256, are argparse errors."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if (args.patches is None) != (args.patches_save_path is None):
+        parser.error("--patches W and --patches_save_path FILE.npz need each other")
+    if args.patches is not None and not 1 <= args.patches <= 256:
+        parser.error("--patches must be 1 .. 256 columns")
+    if args.patches_save_path is not None and not args.patches_save_path.endswith(".npz"):
+        parser.error("--patches_save_path must end with .npz")
+    return args
 
 
 def folder_patterns(audio_ext=None):
@@ -100,6 +119,21 @@ def table(results, names=None, all_channels=False, measure=False):
     return columns, rows
 
 
+def patch_archive(results, names=None, all_channels=False, width=0):
+    """-> {name: array} of the .npz: `patch` [rows, 80, W] and the CSV's identifying columns, in table()'s row order."""
+    import numpy as np
+    flat = [(i, channel, r) for i, res in enumerate(results) for channel, r in enumerate(res if all_channels else [res])]
+    out = {"patch": np.concatenate([r["patch"] for _, _, r in flat] or [np.zeros((0, 80, width), np.float32)], axis=0),
+           "onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
+           "offset": np.array([v for _, _, r in flat for v in r["offset"]], dtype=np.float64),
+           "cluster": np.array([str(v) for _, _, r in flat for v in r["cluster"]], dtype=str)}
+    if names is not None:
+        out["filename"] = np.array([names[i] for i, _, r in flat for _ in r["onset"]], dtype=str)
+    if all_channels:
+        out["channel"] = np.array([channel for _, channel, r in flat for _ in r["onset"]], dtype=np.int64)
+    return out
+
+
 def stdin_wav(sr=None, channel_id=None):
     """The audio file on stdin, decoded on the host -> (audio, rate): the mono mix, or with `channel_id` the channels kept apart and the
     reference's selection (`audio[channel_id]` of a 2-D array; "all" keeps them).  `sr`: resampled to it on the GPU, 1-D or planes."""
@@ -113,7 +147,7 @@ def stdin_wav(sr=None, channel_id=None):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     assert args.csv_save_path.endswith(".csv") or args.csv_save_path == "buffer", \
         "csv_save_path must ends with .csv or be 'buffer'"
     try:
@@ -121,7 +155,8 @@ def main(argv=None):
     except Exception:
         segmenter = WhisperSegmenter(args.model_path, device=args.device, device_ids=args.device_ids)
     kwargs = dict(min_frequency=args.min_frequency, spec_time_step=args.spec_time_step, num_trials=args.num_trials,
-                  batch_size=args.batch_size, **({"measure": True} if args.measure else {}))      # (absent: the calls as they were)
+                  batch_size=args.batch_size, **({"measure": True} if args.measure else {}),      # (absent: the calls as they were)
+                  **({} if args.patches is None else {"patches": args.patches}))
     rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
@@ -130,10 +165,10 @@ def main(argv=None):
         # are read by a second thread while the GPU works and their samples are decoded on the device, group by group, so
         # a large folder needs no more memory than a small one
         results = segmenter.segment_files(paths, **({} if args.channel_id is None else {"channel_id": args.channel_id}), **rate, **kwargs)
-        columns, rows = table(results, [os.path.basename(p) for p in paths], args.channel_id == "all", measure=args.measure)
+        tabled = (results, [os.path.basename(p) for p in paths], args.channel_id == "all")
     elif args.channel_id is None:
         audio, sr = stdin_wav(args.sr) if args.audio_path == "-" else load_wav_device(args.audio_path, **rate)
-        columns, rows = table([segmenter.segment(audio, sr, **kwargs)], measure=args.measure)
+        tabled = ([segmenter.segment(audio, sr, **kwargs)], None, False)
     else:
         if args.audio_path == "-":       # the channels kept apart on the host, and the reference's selection (`audio[channel_id]` of a 2-D array)
             audio, sr = stdin_wav(args.sr, args.channel_id)
@@ -142,9 +177,13 @@ def main(argv=None):
         else:
             audio, sr = load_wav_device(args.audio_path, channel_id=args.channel_id, **rate)
         if args.channel_id == "all":
-            columns, rows = table([segmenter.segment_channels(audio, sr, **kwargs)], all_channels=True, measure=args.measure)
+            tabled = ([segmenter.segment_channels(audio, sr, **kwargs)], None, True)
         else:
-            columns, rows = table([segmenter.segment(audio, sr, **kwargs)], measure=args.measure)
+            tabled = ([segmenter.segment(audio, sr, **kwargs)], None, False)
+    columns, rows = table(*tabled, measure=args.measure)
+    if args.patches is not None:
+        import numpy as np
+        np.savez(args.patches_save_path, **patch_archive(*tabled, width=args.patches))
     if args.csv_save_path == "buffer":
         buf = io.StringIO()
         write_csv(columns, rows, buf)

@@ -22,10 +22,10 @@
 // measure_finish_kernel   one workgroup per segment: adds the chunks' partials in chunk order, then block reductions and one block
 //   prefix sum over the band's bins, all fp64, give the row.
 // The row is rate-free — the kernels never see a sampling rate: crossings as a count, frequencies in bins; measure.py scales.
-#include <mutex>
 #include <vector>
 #include "wseg_common.h"
 #include "wseg_measure_plan.h"
+#include "wseg_staging.h"
 
 namespace wseg {
 
@@ -242,61 +242,7 @@ __global__ __launch_bounds__(kMeasureLanes) void measure_finish_kernel(const lon
   }
 }
 
-// ---- the table's way to the device ----------------------------------------------------------------------------------------------
-// The bounds arrive as a host array and the call must not wait for the stream: the table (bounds + chunk prefix) is written into a
-// pinned buffer the library owns and copied from there on the stream; an event behind the copy says when the buffer is free again.
-// A call takes a free buffer that is large enough or makes a new one; the pool lives as long as the process.
-struct Staging {
-  void* host;
-  size_t cap;
-  hipEvent_t done;
-  int device;                                        // the event's
-  bool taken;
-};
-static std::mutex g_staging_mutex;
-static std::vector<Staging> g_staging;
-
-static int staging_take(size_t bytes, int* index) {
-  int device = 0;
-  WSEG_HIP_CHECK(hipGetDevice(&device));
-  std::lock_guard<std::mutex> lock(g_staging_mutex);
-  for (size_t i = 0; i < g_staging.size(); ++i) {
-    Staging& s = g_staging[i];
-    if (!s.taken && s.device == device && s.cap >= bytes && hipEventQuery(s.done) == hipSuccess) {
-      s.taken = true;
-      *index = (int)i;
-      return WSEG_OK;
-    }
-  }
-  (void)hipGetLastError();                           // (hipErrorNotReady of a query is no error of this call)
-  Staging s;
-  s.cap = align_up(bytes, (size_t)65536);
-  s.taken = true;
-  s.device = device;
-  WSEG_HIP_CHECK(hipHostMalloc(&s.host, s.cap, hipHostMallocDefault));
-  hipError_t e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    (void)hipHostFree(s.host);
-    set_error("hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
-    return WSEG_ERR_HIP;
-  }
-  g_staging.push_back(s);
-  *index = (int)g_staging.size() - 1;
-  return WSEG_OK;
-}
-static void* staging_host(int index) {
-  std::lock_guard<std::mutex> lock(g_staging_mutex);
-  return g_staging[index].host;
-}
-// Records the event behind the copy (enqueued == false: no copy was started, the buffer is free at once) and gives the buffer back.
-static hipError_t staging_release(int index, hipStream_t stream, bool enqueued) {
-  std::lock_guard<std::mutex> lock(g_staging_mutex);
-  Staging& s = g_staging[index];
-  const hipError_t e = enqueued ? hipEventRecord(s.done, stream) : hipSuccess;
-  s.taken = false;
-  return e;
-}
-
+// ---- the table's way to the device: bounds + chunk prefix through the library's pinned staging pool (wseg_staging.h) ----------------
 static int measure_grid_cap() {
   // TEST knob (the same bits for every value: tests/test_measure_gpu.py compares): the cap of measure_chunk_kernel's grid
   const char* e = getenv("WSEG_MEASURE_GRID");
