@@ -434,6 +434,67 @@ int wseg_debug_sched_trace(int32_t n_windows, int32_t n_slots, int32_t kv_units,
                            int32_t refill_min, int32_t lookahead, const int32_t* done_after, wseg_generate_stats* stats,
                            int32_t* trace, int64_t trace_cap, int64_t* trace_len);
 
+/* Model-free tap of ONE decode step's token selection (tests/test_decode_step_gpu.py): on caller-provided device memory it runs
+ * exactly what a decode step of wseg_generate runs after the LM head has written its logits, with the library's own launchers:
+ *   1. the suppress mask from the two lists (ids < 0 or >= vocab are ignored);
+ *   2. per row: log-softmax, suppression (-inf; the begin list only when the row's length equals prompt_len), + running beam
+ *      score, top-Kc (Kc = 2 num_beams; greedy: 1, sampling: top_k, and then the RAW processed logits, no log-softmax).  The
+ *      vocabulary is cut into clamp(ceil(512 / (n_slots * num_beams)), 1, 16) slices of ceil(vocab / slices) ids.  Equal values:
+ *      the lower id wins, within a slice, across slices and across beams;
+ *   3. HF's _beam_search bookkeeping (num_beams > 1) or the greedy choice / the sampler (num_beams == 1);
+ *   4. when out_tokens / out_lengths are given: the retirement of the slots this step finished (done 0 -> 1), into row win[slot].
+ * The sampler (num_beams == 1, top_k > 1), so that a reference can restate it: pr[j] = expf(v[j] - v[0]) over the top_k candidates,
+ * best first (fp32; a suppressed candidate has weight 0); candidates are kept from j = 0 while pr[j] > 0 and (with 0 < top_p < 1)
+ * the weight before j is < top_p * sum(pr); x = seed + 0x9E3779B97F4A7C15 * (window * 4096 + cur_len + 1) mod 2^64, cur_len = pos + 1
+ * tokens present; the splitmix64 finaliser x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB,
+ * x ^= x >> 31; u = float(x >> 40) * 2^-24 * (kept weight); the drawn candidate is the first whose cumulated weight (fp32, in
+ * order) exceeds u, the last kept one if none does.
+ * State arrays (device, read and written in place; S = n_slots, R = S * num_beams rows, row = slot * num_beams + beam,
+ * L = max_length), as wseg_generate keeps them:
+ *   int32 [S]     pos (position of the token the slot fed: pos + 1 tokens are present), done (1: idle, every kernel skips the slot),
+ *                 win (window index: the sampler's key and the output row), wmax (cap on the total length), unsat
+ *   [R]           int32 tokens_in, float run_score, float fin_score, int32 fin_flag, int32 fin_len
+ *   [R][L]        int32 run_seq, int32 fin_seq, uint8 anc
+ *   [R][Kc]       float cand_val, int32 cand_tok: the step's candidates per row, best first (room for [R][16] always suffices)
+ * logits: device fp32 [rows][ldv], 16-byte aligned, columns >= vocab are never read.  list == NULL: rows = R, every slot that is not
+ * done is stepped.  list != NULL (device, n_list distinct slots; the admission's form): only those slots, logits row i is the ONE
+ * row of slot list[i] shared by its beams, and the vocabulary is sliced as for the whole population of n_slots.
+ * scratch: device, 256-byte aligned, wseg_debug_decode_step_scratch_bytes (0 for an unsupported geometry).  out_tokens
+ * [n_out_rows][L] / out_lengths [n_out_rows]: both or neither (then n_out_rows = 0).
+ * Every argument is checked on the host before anything is launched (WSEG_ERR_INVALID, the argument's name in wseg_last_error());
+ * then pos / done / win and the list are read back and refused alike when a stepped slot's pos + 1 >= max_length, its win is
+ * negative or past the output rows, or a list entry is no slot or repeats.  The call synchronises the stream.  Not covered by this
+ * tap: the LM head, the slot scheduler and the replay of the step graph. */
+typedef struct {
+  int32_t n_slots, num_beams;     /* num_beams 1..8 */
+  int32_t max_length;             /* L: total length incl. prompt, capacity of the sequence arrays */
+  int32_t vocab, ldv;             /* ldv >= vocab, ldv % 4 == 0 */
+  int32_t prompt[8];
+  int32_t prompt_len;             /* 1..8, < max_length */
+  int32_t eos_token_id, pad_token_id;
+  float length_penalty;
+  int32_t top_k;                  /* 0..16; used when num_beams == 1: 0 / 1 argmax, else sample */
+  float top_p;
+  uint64_t seed;
+  const int32_t* suppress_tokens; /* device [n_suppress] */
+  const int32_t* begin_suppress_tokens; /* device [n_begin_suppress] */
+  int32_t n_suppress, n_begin_suppress;
+} wseg_decode_step_params;
+typedef struct {
+  int32_t *pos, *done, *win, *wmax, *unsat;
+  int32_t* tokens_in;
+  float *run_score, *fin_score;
+  int32_t *fin_flag, *fin_len;
+  int32_t *run_seq, *fin_seq;
+  uint8_t* anc;
+  float* cand_val;
+  int32_t* cand_tok;
+} wseg_decode_step_state;
+size_t wseg_debug_decode_step_scratch_bytes(int32_t n_slots, int32_t num_beams, int32_t vocab);
+int wseg_debug_decode_step(const wseg_decode_step_params* p, const wseg_decode_step_state* state, const float* logits,
+                           const int32_t* list, int32_t n_list, void* scratch, size_t scratch_bytes, int32_t* out_tokens,
+                           int32_t* out_lengths, int32_t n_out_rows, void* stream);
+
 /* Per-stage device time (ms) of the last wseg_generate call on this model, measured with HIP events
  * on the call's stream: [0]=encoder passes, [1]=cross-K/V passes, [2]=everything else (the decode steps),
  * [3]=number of decode steps. */

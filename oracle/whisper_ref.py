@@ -26,6 +26,7 @@ through the reference's own WhisperSegmenterForEval (tools/make_golden.py).
 import math
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -61,6 +62,10 @@ class GenParams:
     length_penalty: float = 1.0
     suppress_tokens: list = field(default_factory=list)
     begin_suppress_tokens: list = field(default_factory=list)
+    top_k: int = 1                      # num_beams == 1: > 1 samples among the top_k processed logits
+    top_p: float = 1.0
+    seed: int = 0
+    window_max_length: list = None      # per-window caps on the total length (clamped to [len(prompt) + 1, max_length])
 
 
 def _lin(x, sd, prefix, bias=True):
@@ -172,122 +177,459 @@ class Decoder:
         return logits if self.keep_dtype else logits.float()
 
 
-def _process(scores, cur_len, gp):
-    """SuppressTokens (every step) + SuppressTokensAtBegin (only when cur_len == len(prompt))."""
-    if gp.suppress_tokens:
-        scores[:, gp.suppress_tokens] = float("-inf")
-    if gp.begin_suppress_tokens and cur_len == len(gp.prompt):
-        scores[:, gp.begin_suppress_tokens] = float("-inf")
-    return scores
+# ------------------------------------------------------------------------------------------------
+# One decoding step, separated from the model: beam_step / greedy_step work on an explicit state and on logits of any origin;
+# generate() is a loop over them.  The state has the fields of the device's decode state (include/wseg.h,
+# wseg_debug_decode_step): S slots (windows being decoded), nb beams, R = S * nb rows (row = slot * nb + beam), L = max_length.
+#
+# Arithmetic: log-softmax in float64, rounded to float32; HF's masking and merging in float32, literally
+# (generation/utils.py:3374-3452); the (cur_len + 1 - P) ** length_penalty denominators as Python floats.
+# Selection: every choice is made with an explicit stable rule — on equal values the lower flat index wins (beam * V + token,
+# then candidate rank, then "already finished before new") — never with torch.topk's order on ties.  Within one row the
+# candidates are ranked by their processed logits (log-softmax and the row's running score are a shift of the whole row): where
+# two distinct logits round to one float32 sum, HF's order is unspecified and the larger logit is taken.
+_F32 = np.float32
+_NEG = _F32(-1.0e9)
+MAX_CAND = 16
 
 
-def _gather(t, idx):
-    while idx.dim() < t.dim():
-        idx = idx.unsqueeze(-1)
-    return torch.take_along_dim(t, idx, dim=1)
+class StepTrace:
+    """What the reference decided in a step, for tests: `events` counts the paths taken, `decisions` lists every comparison
+    between neighbours of a ranking that the result depends on, as (kind, gap, scale, denom, safe): gap = difference of the two
+    float32 values (0: a tie, resolved by index), scale = the largest magnitude among the terms they were computed from (for a
+    finished score c / denom: the terms of c, before the division), denom = the length-penalty denominator they were divided by
+    (1 for the others), safe = both values are determined bit for bit
+    whatever the summation order of the log-sum-exp (see _Val)."""
+
+    def __init__(self):
+        from collections import Counter
+        self.events = Counter()
+        self.decisions = []
+        self.rows = []          # (row, token ids of its candidates best first + the next one, their processed logits)
+        self.largest = {}       # ("cand", row, rank) / ("run_score", row) -> largest term; ("fin_score", row) -> (largest term of the
+        #                         undivided score, denom, carried over unchanged)
+
+
+class _Val:
+    """A float32 score with what a margin check needs: `scale` (largest term), `denom`, and `src`: a key that is equal for two
+    values computed by the same operations from bit-equal inputs (then any implementation gives them equal bits), or None;
+    `exact`: the value does not depend on the rounding of the log-sum-exp at all."""
+    __slots__ = ("v", "scale", "denom", "src", "exact")
+
+    def __init__(self, v, scale, denom=1.0, src=None, exact=False):
+        self.v, self.scale, self.denom, self.src, self.exact = _F32(v), float(scale), float(denom), src, bool(exact)
+
+
+def _sticks_to_1e9(q):
+    """-1e9 + q in float32 (spacing 64 there) is the same multiple of 64 for every q' within 1 of q."""
+    d = (abs(float(q)) - 32.0) % 64.0
+    return min(d, 64.0 - d) >= 1.0
+
+
+def _rank(vals, k, trace, kind):
+    """Indices of the k best of `vals` (_Val), value descending, on equal values the lower index first; records the decisions."""
+    order = sorted(range(len(vals)), key=lambda i: (-float(vals[i].v), i))
+    if trace is not None:
+        for a, b in zip(order[:k], order[1:k + 1]):
+            x, y = vals[a], vals[b]
+            both_inf = np.isinf(x.v) and np.isinf(y.v)
+            gap = 0.0 if both_inf else float(x.v) - float(y.v)
+            safe = both_inf or (x.exact and y.exact) or (gap == 0.0 and x.src is not None and x.src == y.src)
+            trace.decisions.append((kind, gap, max(x.scale, y.scale), min(x.denom, y.denom), safe))
+            if gap == 0.0 and not both_inf:
+                trace.events["tie_" + kind] += 1
+    return order[:k]
+
+
+@dataclass
+class StepState:
+    pos: np.ndarray
+    done: np.ndarray
+    win: np.ndarray
+    wmax: np.ndarray
+    unsat: np.ndarray
+    tokens_in: np.ndarray
+    run_score: np.ndarray
+    fin_score: np.ndarray
+    fin_flag: np.ndarray
+    fin_len: np.ndarray
+    run_seq: np.ndarray
+    fin_seq: np.ndarray
+    anc: np.ndarray
+    cand_val: np.ndarray
+    cand_tok: np.ndarray
+
+    FIELDS = ("pos", "done", "win", "wmax", "unsat", "tokens_in", "run_score", "fin_score", "fin_flag", "fin_len", "run_seq",
+              "fin_seq", "anc", "cand_val", "cand_tok")
+
+    def copy(self):
+        return StepState(**{f: getattr(self, f).copy() for f in self.FIELDS})
+
+
+def new_state(n_slots, gp, wins=None, window_max_length=None, pos=None):
+    """Freshly admitted slots: the prompt is in place and the slot stands at its last prompt position (`pos`: another one)."""
+    S, nb, L, P = n_slots, gp.num_beams, gp.max_length, len(gp.prompt)
+    R = S * nb
+    seq = np.full((R, L), gp.pad_token_id, np.int32)
+    seq[:, :P] = np.asarray(gp.prompt, np.int32)
+    run_score = np.full((S, nb), _NEG, _F32)
+    run_score[:, 0] = 0.0
+    wins = np.arange(S, dtype=np.int32) if wins is None else np.asarray(wins, np.int32)
+    wmax = np.full(S, L, np.int32)
+    if window_max_length is not None:
+        wmax = np.maximum(P + 1, np.minimum(L, np.asarray(window_max_length, np.int32)[wins])).astype(np.int32)
+    p0 = P - 1 if pos is None else pos
+    return StepState(pos=np.full(S, p0, np.int32), done=np.zeros(S, np.int32), win=wins, wmax=wmax, unsat=np.ones(S, np.int32),
+                     tokens_in=np.full(R, gp.prompt[p0], np.int32), run_score=run_score.reshape(R),
+                     fin_score=np.full(R, _NEG, _F32), fin_flag=np.zeros(R, np.int32), fin_len=np.zeros(R, np.int32),
+                     run_seq=seq, fin_seq=seq.copy(), anc=np.tile(np.arange(nb, dtype=np.uint8).repeat(L), S).reshape(R, L),
+                     cand_val=np.zeros((R, MAX_CAND), _F32), cand_tok=np.zeros((R, MAX_CAND), np.int32))
+
+
+def _suppressed(V, cur_len, gp):
+    m = np.zeros(V, bool)
+    ids = list(gp.suppress_tokens) + (list(gp.begin_suppress_tokens) if cur_len == len(gp.prompt) else [])
+    for t in ids:
+        if 0 <= t < V:          # ids outside the vocabulary are ignored
+            m[t] = True
+    return m
+
+
+def _row_candidates(x, sup, k):
+    """Processed logits of one row (float32, suppressed -> -inf) and its k + 1 best ids, value descending, lower id first."""
+    proc = np.where(sup, _F32(-np.inf), x.astype(_F32))
+    n = min(k + 1, proc.shape[0])
+    part = np.argpartition(-proc, n - 1)[:n] if n < proc.shape[0] else np.arange(proc.shape[0])
+    kth = proc[part].min()
+    pool = np.flatnonzero(proc >= kth)          # every id that ties with the (k + 1)-th value takes part: the lower id wins
+    order = pool[np.lexsort((pool, -proc[pool].astype(np.float64)))][:n]
+    return proc, order
+
+
+def _log_softmax64(x):
+    z = x.astype(np.float64)
+    m = z.max()
+    return (z - m) - math.log(np.exp(z - m).sum())
+
+
+def _slots_of(state, slots):
+    return range(state.pos.shape[0]) if slots is None else [int(w) for w in slots]
+
+
+def beam_step(state, logits, gp, slots=None, trace=None, list_form=False):
+    """One step of HF's _beam_search for every slot that is not done (`slots`: only those), in place.  logits [R, V]; with `slots`
+    and list_form (the admission's form), [len(slots), V]: ONE row per listed slot, shared by its beams.
+    Returns the flat source row of every row (which row's cache the new row continues; identity where nothing moved)."""
+    nb, L, P, V = gp.num_beams, gp.max_length, len(gp.prompt), logits.shape[1]
+    Kc = 2 * nb
+    lp = float(gp.length_penalty)
+    src_rows = np.arange(state.tokens_in.shape[0])
+    for li, w in enumerate(_slots_of(state, slots)):
+        if state.done[w]:
+            continue
+        pos = int(state.pos[w])
+        cur_len = pos + 1
+        rows = range(w * nb, (w + 1) * nb)
+        if cur_len < P:                         # prompt phase: the next token is forced, nothing else changes
+            state.tokens_in[w * nb:(w + 1) * nb] = gp.prompt[cur_len]
+            state.pos[w] = pos + 1
+            if trace is not None:
+                trace.events["prompt_phase"] += 1
+            continue
+        sup = _suppressed(V, cur_len, gp)
+        # a. / b. per row: log_softmax, suppress, + running score -> its Kc best
+        cands = []                              # per beam: list of (_Val, token)
+        for j, r in enumerate(rows):
+            x = np.asarray(logits[li if list_form else r])
+            proc, order = _row_candidates(x, sup, Kc)
+            lsm = _log_softmax64(x)
+            base = state.run_score[r]
+            top2 = np.partition(x.astype(np.float64), -2)[-2:]
+            dominated = bool(top2[1] - top2[0] >= 40.0)      # sum(exp(x - max)) rounds to 1.0f in any order: log-sum-exp == max exactly
+            key = (x.tobytes(), float(base))
+            row = []
+            for t in order[:Kc]:
+                l32 = _F32(lsm[t]) if not sup[t] else _F32(-np.inf)
+                v = _F32(l32 + base)
+                exact = (dominated and x[t] == top2[1]) or np.isinf(v) or (abs(float(base)) >= 1.0e8 and _sticks_to_1e9(l32))
+                row.append((_Val(v, max(abs(float(l32)), abs(float(base)), abs(float(x[t]) - float(top2[1])), abs(float(v))), src=(key, float(x[t])), exact=exact), int(t)))
+            cands.append(row)
+            state.cand_val[r, :Kc] = [c[0].v for c in row]
+            state.cand_tok[r, :Kc] = [c[1] for c in row]
+            if trace is not None:
+                trace.rows.append((r, [int(t) for t in order], proc[order].copy()))
+                for rank, c in enumerate(row):
+                    trace.largest[("cand", r, rank)] = c[0].scale
+                if len(order) > Kc and sup[int(np.argmax(x))]:
+                    trace.events["suppressed_row_max"] += 1
+        # c. the Kc best continuations over the nb * V accumulated log-probs: flat index = beam * V + token
+        flat = [(c[0], j, c[1]) for j, row in enumerate(cands) for c in row]      # already in flat-index order within equal values
+        flat_vals = []
+        for val, j, t in flat:
+            fv = _Val(val.v, val.scale, src=None if val.src is None else (val.src[0], val.src[1]), exact=val.exact)
+            flat_vals.append(fv)
+        # two beams with bit-equal rows and scores give bit-equal candidates in any implementation: the tie is broken by the beam
+        order = sorted(range(len(flat)), key=lambda i: (-float(flat[i][0].v), flat[i][1], i))
+        if trace is not None:
+            _rank([flat_vals[i] for i in order], Kc, trace, "beams")
+        top = [flat[i] for i in order[:Kc]]
+        c_val = [t[0] for t in top]
+        c_beam = [t[1] for t in top]
+        c_tok = [t[2] for t in top]
+        if trace is not None:
+            trace.events["tie_two_beams"] += any(c_val[k].v == c_val[k + 1].v and c_beam[k] != c_beam[k + 1] and not np.isinf(c_val[k].v)
+                                                 for k in range(Kc - 1))
+        # d. stopping criteria
+        cap = cur_len + 1 >= int(state.wmax[w])
+        c_hit = [(t == gp.eos_token_id) or cap for t in c_tok]
+        # e. running beams for the next iteration
+        run_val = []
+        for k in range(Kc):
+            if c_hit[k]:
+                v = _F32(c_val[k].v + _F32(1.0) * _NEG)
+                run_val.append(_Val(v, 1.0e9, exact=(abs(float(c_val[k].v)) < 1.0e6 and _sticks_to_1e9(c_val[k].v)) or c_val[k].exact or np.isinf(v)))
+            else:
+                run_val.append(_Val(c_val[k].v, c_val[k].scale, src=c_val[k].src, exact=c_val[k].exact))
+        nxt = _rank(run_val, nb, trace, "running")
+        # f. finished beams
+        un = int(state.unsat[w])
+        n_gen = cur_len + 1 - P
+        denom = _F32(float(n_gen) ** lp)
+        lp_exact = float(_F32(lp)) == lp
+        merged = [_Val(state.fin_score[r], abs(float(state.fin_score[r])), exact=True) for r in rows]
+        for k in range(Kc):
+            did = c_hit[k] and k < nb
+            v = _F32(c_val[k].v / denom)
+            v = _F32(v + _F32(0.0) * _NEG)
+            v = _F32(v + (_F32(0.0) if un else _F32(1.0)) * _NEG)
+            v = _F32(v + (_F32(0.0) if did else _F32(1.0)) * _NEG)
+            if un and did:
+                merged.append(_Val(v, c_val[k].scale, denom=float(denom), exact=c_val[k].exact and lp_exact))      # scale: the terms of c, before the division
+            else:
+                merged.append(_Val(v, 1.0e9, exact=(abs(float(c_val[k].v) / float(denom)) < 1.0e6 and _sticks_to_1e9(float(c_val[k].v) / float(denom))) or np.isinf(v)))
+        mi = _rank(merged, nb, trace, "finished")
+        if trace is not None:
+            trace.events["tie_finished_scores"] += any(un and c_hit[k] and k < nb and state.fin_flag[r] and merged[nb + k].v == state.fin_score[r]
+                                                       for k in range(Kc) for r in rows)
+        n_fin_score = [merged[m].v for m in mi]
+        n_fin_flag = [int(state.fin_flag[w * nb + m]) if m < nb else int(c_hit[m - nb] and (m - nb) < nb) for m in mi]
+        n_fin_len = [int(state.fin_len[w * nb + m]) if m < nb else n_gen for m in mi]
+        # g. early-stop heuristic (early_stopping=False): can the best running beam still beat the worst finished one?
+        best = run_val[nxt[0]]
+        best_running = _F32(best.v / denom)
+        mn = min(n_fin_score)
+        improve = False
+        wi = merged[mi[int(np.argmin(n_fin_score))]]
+        for i in range(nb):
+            worst = mn if n_fin_flag[i] else _NEG
+            improve = improve or bool(best_running > worst)
+            if trace is not None and un:
+                safe = best.exact and lp_exact and (wi.exact or not n_fin_flag[i])
+                trace.decisions.append(("early_stop", abs(float(best_running) - float(worst)),
+                                        max(best.scale, wi.scale if n_fin_flag[i] else 0.0),
+                                        min(float(denom), wi.denom if n_fin_flag[i] else 1.0e30), safe))
+        un_new = int(bool(un) and improve)
+        if trace is not None:
+            ev = trace.events
+            eos_ranks = [k for k in range(Kc) if c_tok[k] == gp.eos_token_id]
+            ev["eos_rank_ge_nb_only"] += bool(eos_ranks) and min(eos_ranks) >= nb and not cap
+            ev["eos_rank_0"] += bool(eos_ranks) and eos_ranks[0] == 0
+            ev["eos_in_nb_rows"] += len([k for k in eos_ranks if k < nb]) >= nb
+            ev["several_finish"] += sum(1 for k in range(nb) if c_hit[k]) >= 2 and bool(un)
+            ev["cap_hit"] += cap
+            ev["cap_at_first_step"] += cap and cur_len == P
+            ev["unsat_already_0"] += not un
+            ev["early_stop_improves"] += bool(un) and improve and any(n_fin_flag)
+            ev["early_stop_stops"] += bool(un) and not improve and not cap
+            ev["finished_new"] += any(m >= nb for m in mi)
+            ev["begin_suppress_step"] += cur_len == P and bool(gp.begin_suppress_tokens)
+        # write back
+        old_run = state.run_seq[w * nb:(w + 1) * nb].copy()
+        old_fin = state.fin_seq[w * nb:(w + 1) * nb].copy()
+        old_anc = state.anc[w * nb:(w + 1) * nb].copy()
+        state.unsat[w] = un_new
+        if not un_new or cap:
+            state.done[w] = 1
+        else:
+            state.pos[w] = pos + 1
+        for i in range(nb):
+            r = w * nb + i
+            k = nxt[i]
+            state.run_score[r] = run_val[k].v
+            if trace is not None:
+                trace.largest[("run_score", r)] = run_val[k].scale
+                trace.largest[("fin_score", r)] = (merged[mi[i]].scale, merged[mi[i]].denom, mi[i] < nb)      # True: a stored score that was carried over
+            state.fin_score[r] = n_fin_score[i]
+            state.fin_flag[r] = n_fin_flag[i]
+            state.fin_len[r] = n_fin_len[i]
+            state.tokens_in[r] = c_tok[k]
+            src_rows[r] = w * nb + c_beam[k]
+            state.run_seq[r, :cur_len] = old_run[c_beam[k], :cur_len]
+            state.run_seq[r, cur_len] = c_tok[k]
+            state.run_seq[r, cur_len + 1:] = gp.pad_token_id
+            state.anc[r, :cur_len] = old_anc[c_beam[k], :cur_len]
+            state.anc[r, cur_len:] = i
+            m = mi[i]
+            if m < nb:
+                state.fin_seq[r] = old_fin[m]
+            else:
+                state.fin_seq[r, :cur_len] = old_run[c_beam[m - nb], :cur_len]
+                state.fin_seq[r, cur_len] = c_tok[m - nb]
+                state.fin_seq[r, cur_len + 1:] = gp.pad_token_id
+    return src_rows
+
+
+def sampler_uniform24(seed, window, cur_len):
+    """The counter-based generator of the sampler in Python integers: the top 24 bits of the splitmix64 finaliser of
+    seed + 0x9E3779B97F4A7C15 * (window * 4096 + cur_len + 1)  (include/wseg.h, wseg_debug_decode_step)."""
+    M = (1 << 64) - 1
+    x = (seed + 0x9E3779B97F4A7C15 * (window * 4096 + cur_len + 1)) & M
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & M
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & M
+    x ^= x >> 31
+    return x >> 40
+
+
+def sample_candidate(vals, top_p, u24, info=None):
+    """Index of the drawn candidate among `vals` (processed logits, best first, -inf = suppressed): HF's TopKLogitsWarper +
+    TopPLogitsWarper + a draw with the uniform u24 / 2^24 scaled by the kept mass, in float32 as the product states it.
+    info (dict): receives the distance of the uniform from the nearest cumulative boundary, relative to the kept mass."""
+    with np.errstate(invalid="ignore"):
+        pr = [_F32(np.exp(_F32(v - vals[0]))) if not np.isinf(v) else _F32(0.0) for v in vals]
+    z = _F32(0.0)
+    for q in pr:
+        z = _F32(z + q)
+    cut = 0.0 < top_p < 1.0
+    kept = before = _F32(0.0)
+    n_keep = 0
+    for j, q in enumerate(pr):
+        if j > 0 and (q <= 0.0 or (cut and before >= _F32(_F32(top_p) * z))):
+            break
+        kept = _F32(kept + q)
+        before = _F32(before + q)
+        n_keep += 1
+    u = _F32(_F32(_F32(u24) * _F32(1.0 / 16777216.0)) * kept)
+    acc = _F32(0.0)
+    choice = n_keep - 1
+    bounds = []
+    for j in range(n_keep):
+        acc = _F32(acc + pr[j])
+        bounds.append(float(acc))
+    for j in range(n_keep):
+        if u < _F32(bounds[j]):
+            choice = j
+            break
+    if info is not None:
+        info["distance"] = min(abs(float(u) - b) for b in bounds) / float(kept)
+        info["n_keep"] = n_keep
+        info["cut_margin"] = min([abs(float(b) - float(_F32(_F32(top_p) * z))) / float(z) for b in bounds] or [1.0]) if cut else 1.0
+    return choice
+
+
+def greedy_step(state, logits, gp, slots=None, trace=None, list_form=False):
+    """One greedy / sampling step (num_beams == 1) for every slot that is not done (`slots`: only those; list_form:
+    logits [len(slots), V]), in place.  top_k <= 1: argmax of the processed logits, the lower id on equal values."""
+    L, P, V = gp.max_length, len(gp.prompt), logits.shape[1]
+    top_k = gp.top_k if gp.top_k > 1 else 1
+    for li, w in enumerate(_slots_of(state, slots)):
+        if state.done[w]:
+            continue
+        pos = int(state.pos[w])
+        cur_len = pos + 1
+        if cur_len < P:
+            state.tokens_in[w] = gp.prompt[cur_len]
+            state.pos[w] = pos + 1
+            if trace is not None:
+                trace.events["prompt_phase"] += 1
+            continue
+        x = np.asarray(logits[li if list_form else w])
+        sup = _suppressed(V, cur_len, gp)
+        proc, order = _row_candidates(x, sup, top_k)
+        state.cand_val[w, :top_k] = proc[order[:top_k]]
+        state.cand_tok[w, :top_k] = order[:top_k]
+        if trace is not None:
+            trace.rows.append((w, [int(t) for t in order], proc[order].copy()))
+            if sup[int(np.argmax(x))]:
+                trace.events["suppressed_row_max"] += 1
+        tok = int(order[0])
+        if top_k > 1:
+            info = {} if trace is not None else None
+            tok = int(order[sample_candidate(list(proc[order[:top_k]]), gp.top_p, sampler_uniform24(gp.seed, int(state.win[w]), cur_len), info)])
+            if trace is not None:
+                trace.decisions.append(("sample", min(info["distance"], info["cut_margin"]), 1.0, 1.0, False))
+                trace.events["sample_cut"] += info["n_keep"] < top_k
+        state.run_seq[w, cur_len] = tok
+        state.anc[w, cur_len] = 0
+        state.tokens_in[w] = tok
+        cap = cur_len + 1 >= int(state.wmax[w])
+        if tok == gp.eos_token_id or cap:
+            state.unsat[w] = 0
+            state.fin_len[w] = cur_len + 1 - P
+            state.done[w] = 1
+            if trace is not None:
+                trace.events["cap_hit" if cap else "eos_rank_0"] += 1
+        else:
+            state.pos[w] = pos + 1
+    return np.arange(state.tokens_in.shape[0])
+
+
+def finalize(state, gp, slots=None):
+    """Best sequence of each slot: (tokens [n, L] pad-filled, lengths [n]) — the product's retirement of a slot."""
+    nb, L, P = gp.num_beams, gp.max_length, len(gp.prompt)
+    ws = list(_slots_of(state, slots))
+    toks = np.full((len(ws), L), gp.pad_token_id, np.int32)
+    lens = np.zeros(len(ws), np.int32)
+    for i, w in enumerate(ws):
+        src = (state.run_seq if nb == 1 else state.fin_seq)[w * nb]
+        lens[i] = P + int(state.fin_len[w * nb])
+        toks[i, :lens[i]] = src[:lens[i]]
+    return toks, lens
+
+
+def run_loop(logits_fn, n_slots, gp, window_max_length=None, max_steps=None):
+    """Steps freshly admitted slots until all are done.  logits_fn(state, src_rows) -> logits [R, V] for the rows' current
+    tokens_in (src_rows: which row each row continues, None at the first call).  Returns (tokens, lengths, final state)."""
+    state = new_state(n_slots, gp, window_max_length=window_max_length)
+    step = greedy_step if gp.num_beams == 1 else beam_step
+    src, n = None, 0
+    while not state.done.all():
+        src = step(state, logits_fn(state, src), gp)
+        n += 1
+        assert max_steps is None or n <= max_steps
+    toks, lens = finalize(state, gp)
+    return toks, lens, state
 
 
 @torch.no_grad()
 def generate(sd, cfg, feats, gp, return_first_logits=False):
     """feats [B,80,1000] -> int64 [B, L] token ids INCLUDING the prompt, padded with pad_token_id.
 
-    Follows HF generate as the reference calls it (model.py:609-619).
+    Follows HF generate as the reference calls it (model.py:609-619): a loop of greedy_step / beam_step over the model's logits.
+    A window that has finished is frozen while the others go on (HF stops stepping a batch once every item has finished).
     """
     B = feats.shape[0]
-    enc = encoder_forward(sd, cfg, feats)
-    P = len(gp.prompt)
-    prompt = torch.tensor(gp.prompt, dtype=torch.int64)
-    first_logits = None
-
-    if gp.num_beams == 1:
-        dec = Decoder(sd, cfg, enc)
-        seq = prompt[None].repeat(B, 1)
-        unfinished = torch.ones(B, dtype=torch.int64)
-        cur_len = P
-        inp = seq
-        while True:
-            logits = dec.step(inp)
-            if first_logits is None:
-                first_logits = logits.clone()
-            scores = _process(logits.clone(), cur_len, gp)
-            nxt = torch.argmax(scores, dim=-1)
-            nxt = nxt * unfinished + gp.pad_token_id * (1 - unfinished)
-            seq = torch.cat([seq, nxt[:, None]], dim=1)
-            cur_len += 1
-            unfinished = unfinished & (nxt != gp.eos_token_id).long()
-            if cur_len >= gp.max_length:
-                unfinished = unfinished * 0
-            if unfinished.max() == 0:
-                break
-            inp = nxt[:, None]
-        return (seq, first_logits) if return_first_logits else seq
-
     nb = gp.num_beams
-    V = cfg.vocab_size
-    K = 2 * nb  # one EOS id -> beams_to_keep = max(2, 1 + 1) * num_beams
-    max_length = gp.max_length
-    lp = gp.length_penalty
-    dec = Decoder(sd, cfg, enc.repeat_interleave(nb, dim=0))
-    running_sequences = torch.full((B, nb, max_length), gp.pad_token_id, dtype=torch.int64)
-    running_sequences[:, :, :P] = prompt
-    sequences = running_sequences.clone()
-    running_beam_scores = torch.zeros((B, nb), dtype=torch.float32)
-    running_beam_scores[:, 1:] = -1e9
-    beam_scores = torch.full((B, nb), -1e9, dtype=torch.float32)
-    is_sent_finished = torch.zeros((B, nb), dtype=torch.bool)
-    unsat = torch.ones((B, 1), dtype=torch.bool)  # is_early_stop_heuristic_unsatisfied
-    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(K - nb, dtype=torch.bool)])
-    gen_len = torch.zeros((B, nb), dtype=torch.int64)          # generated length of each finished slot
-    cur_len = P
-    inp = running_sequences[:, :, :P].reshape(B * nb, P)
-    while True:
+    enc = encoder_forward(sd, cfg, feats)
+    dec = Decoder(sd, cfg, enc if nb == 1 else enc.repeat_interleave(nb, dim=0))
+    P = len(gp.prompt)
+    first = []
+
+    def logits_fn(state, src):
+        if src is None:
+            inp = torch.from_numpy(state.run_seq[:, :P].astype(np.int64))
+        else:
+            dec.reorder(torch.from_numpy(src.astype(np.int64)))
+            inp = torch.from_numpy(state.tokens_in.astype(np.int64))[:, None]
         logits = dec.step(inp)
-        if first_logits is None:
-            first_logits = logits.clone()
-        log_probs = F.log_softmax(logits, dim=-1)
-        log_probs = _process(log_probs, cur_len, gp)
-        log_probs = log_probs.view(B, nb, V) + running_beam_scores[:, :, None]
-        log_probs = log_probs.reshape(B, nb * V)
-        topk_log_probs, topk_indices = torch.topk(log_probs, k=K)
-        topk_beam = topk_indices // V
-        topk_ids = topk_indices % V
-        topk_running_sequences = _gather(running_sequences, topk_beam)
-        topk_running_sequences[:, :, cur_len] = topk_ids
-        hits = (topk_ids == gp.eos_token_id) | (cur_len + 1 >= max_length)
-        # e. running beams for the next iteration
-        topk_running_log_probs = topk_log_probs + hits.to(torch.float32) * -1.0e9
-        next_idx = torch.topk(topk_running_log_probs, k=nb)[1]
-        running_sequences = _gather(topk_running_sequences, next_idx)
-        running_beam_scores = _gather(topk_running_log_probs, next_idx)
-        beam_src = _gather(topk_beam, next_idx)
-        # f. finished beams
-        did_finish = hits & top_mask[None, :]
-        fin_scores = topk_log_probs / ((cur_len + 1 - P) ** lp)
-        fin_scores = fin_scores + (~unsat).to(torch.float32) * -1.0e9
-        fin_scores = fin_scores + (~did_finish) * -1.0e9
-        merged_sequences = torch.cat((sequences, topk_running_sequences), dim=1)
-        merged_scores = torch.cat((beam_scores, fin_scores), dim=1)
-        merged_fin = torch.cat((is_sent_finished, did_finish), dim=1)
-        merged_len = torch.cat((gen_len, torch.full((B, K), cur_len + 1 - P, dtype=torch.int64)), dim=1)
-        mi = torch.topk(merged_scores, k=nb)[1]
-        sequences = _gather(merged_sequences, mi)
-        beam_scores = _gather(merged_scores, mi)
-        is_sent_finished = _gather(merged_fin, mi)
-        gen_len = _gather(merged_len, mi)
-        # g. cache reorder + stopping condition
-        flat_src = (beam_src + torch.arange(B)[:, None] * nb).reshape(-1)
-        dec.reorder(flat_src)
-        cur_len += 1
-        best_running = running_beam_scores[:, :1] / ((cur_len - P) ** lp)
-        worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0],
-                                     torch.tensor(-1.0e9))
-        unsat = unsat & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
-        if not (bool(torch.any(unsat)) and not bool(torch.all(hits))):
-            break
-        inp = running_sequences[:, :, cur_len - 1].reshape(B * nb, 1)
-    out_len = int((gen_len[:, 0]).max()) + P
-    out = sequences[:, 0, :out_len]
-    return (out, first_logits) if return_first_logits else out
+        if not first:
+            first.append(logits.clone())
+        return logits.numpy()
+
+    toks, lens, _ = run_loop(logits_fn, B, gp, window_max_length=gp.window_max_length)
+    out = torch.from_numpy(toks[:, :int(lens.max())].astype(np.int64))
+    return (out, first[0]) if return_first_logits else out
 
 
 @torch.no_grad()

@@ -30,7 +30,8 @@ def test_struct_layouts_match_header(tmp_path):
     import subprocess
     from whisperseg_amd import _lib
     structs = {"wseg_model_config": _lib.ModelConfig, "wseg_logmel_desc": _lib.LogmelDesc,
-               "wseg_generate_params": _lib.GenerateParams, "wseg_generate_stats": _lib.GenerateStats}
+               "wseg_generate_params": _lib.GenerateParams, "wseg_generate_stats": _lib.GenerateStats,
+               "wseg_decode_step_params": _lib.DecodeStepParams, "wseg_decode_step_state": _lib.DecodeStepState}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "wseg.h"', "int main(void) {"]
     for cname, ct in structs.items():
         lines.append(f'  printf("{cname} size %zu\\n", sizeof({cname}));')

@@ -66,6 +66,42 @@ def test_token_sequences_match_hf(tiny):
     assert n_checked >= 20
 
 
+@pytest.mark.parametrize("num_beams", [2, 4])
+@pytest.mark.parametrize("length_penalty", [0.0, 2.0, -1.0])
+def test_length_penalty_matches_installed_transformers(tiny, golden_dir, num_beams, length_penalty):
+    """The pow() denominators of the finished-beam scores and of the early-stop comparison against the installed HF `generate` on
+    the tiny trained model (every recorded golden has length_penalty 1.0).  HF 5.x counts max_length without the prompt and returns
+    no prompt: the oracle's max_length = L is HF's L - 3.  Two recordings: tiny_recording(102, 4), where only (4 beams, 2.0) moves a
+    token, and tiny_recording(118, 4), where every one of the six settings gives other tokens than length_penalty 1.0 does — asserted
+    below, so that an oracle which ignored the penalty or misread its sign fails each case."""
+    transformers = pytest.importorskip("transformers")
+    sd, rc, _, _ = tiny
+    model = transformers.WhisperForConditionalGeneration.from_pretrained(os.path.join(golden_dir, "tiny_model")).float().eval()
+    hf_strips_prompt = int(transformers.__version__.split(".")[0]) >= 5
+    lengths = set()
+    for rec, Ls in ((102, (40, 12)), (118, (40,))):
+        audio = GI.tiny_recording(rec, 4)
+        feats = torch.from_numpy(np.stack([s[2] for s in F.sliced_audio_features(audio, TM.SR, 0, TM.STS, 1)]))
+        assert feats.shape[0] == 4
+        for L in Ls:
+            gp = W.GenParams(prompt=TM.PROMPT, eos_token_id=TM.EOT, pad_token_id=TM.EOT, max_length=L, num_beams=num_beams,
+                             length_penalty=length_penalty, suppress_tokens=TM.SUPPRESS, begin_suppress_tokens=TM.BEGIN_SUPPRESS)
+            got = W.generate(sd, rc, feats, gp)
+            with torch.no_grad():
+                want = model.generate(input_features=feats, decoder_input_ids=torch.tensor([TM.PROMPT] * feats.shape[0]), pad_token_id=TM.EOT,
+                                      eos_token_id=TM.EOT, max_length=L - 3 if hf_strips_prompt else L, num_beams=num_beams,
+                                      do_sample=False, length_penalty=length_penalty, suppress_tokens=TM.SUPPRESS,
+                                      begin_suppress_tokens=TM.BEGIN_SUPPRESS)
+            for i in range(feats.shape[0]):
+                assert content(got[i].tolist()) == content(want[i].tolist()), (rec, L, i)
+                lengths.add(len(content(got[i].tolist())))
+            if rec == 118:          # the penalty is live here: length_penalty 1.0 decodes something else
+                gp.length_penalty = 1.0
+                neutral = W.generate(sd, rc, feats, gp)
+                assert [content(r.tolist()) for r in neutral] != [content(r.tolist()) for r in got], (num_beams, length_penalty)
+    assert len(lengths) >= 3
+
+
 def test_eos_fires_at_varied_lengths(tiny):
     _, _, runs, _ = tiny
     lengths = {len(content(row)) for run in runs for b in run["token_batches"] for row in b}

@@ -37,6 +37,19 @@ class GenerateStats(C.Structure):
                 ("kv_units_total", C.c_int32), ("kv_units_peak", C.c_int32), ("n_preemptions", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class DecodeStepParams(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("num_beams", C.c_int32), ("max_length", C.c_int32), ("vocab", C.c_int32), ("ldv", C.c_int32),
+                ("prompt", C.c_int32 * 8), ("prompt_len", C.c_int32), ("eos_token_id", C.c_int32), ("pad_token_id", C.c_int32),
+                ("length_penalty", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64),
+                ("suppress_tokens", C.c_void_p), ("begin_suppress_tokens", C.c_void_p),
+                ("n_suppress", C.c_int32), ("n_begin_suppress", C.c_int32)]
+
+
+class DecodeStepState(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "done", "win", "wmax", "unsat", "tokens_in", "run_score", "fin_score", "fin_flag",
+                                          "fin_len", "run_seq", "fin_seq", "anc", "cand_val", "cand_tok")]
+
+
 # name -> (restype, argtypes); every symbol include/wseg.h declares.
 SYMBOLS = {
     "wseg_abi_version": (C.c_int, []),
@@ -85,6 +98,9 @@ SYMBOLS = {
     "wseg_debug_step_snapshot_result": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "wseg_debug_sched_trace": (C.c_int, [C.c_int32] * 8 + [C.c_void_p, C.POINTER(GenerateStats), C.c_void_p, C.c_int64,
                                          C.POINTER(C.c_int64)]),
+    "wseg_debug_decode_step_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "wseg_debug_decode_step": (C.c_int, [C.POINTER(DecodeStepParams), C.POINTER(DecodeStepState), C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "wseg_last_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 4)]),
     "wseg_last_stats": (C.c_int, [C.c_void_p, C.POINTER(GenerateStats)]),
     "wseg_debug_gemm": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

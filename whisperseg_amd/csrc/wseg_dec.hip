@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
+#include <vector>
 #include "wseg_dec.h"
 
 namespace wseg {
@@ -1632,7 +1633,126 @@ int launch_finalize(const DecodeState& st, const int* slots, int n, int* out_tok
   return WSEG_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// wseg_debug_decode_step: what a decode step runs after the LM head, on the caller's state arrays (include/wseg.h).
+struct StepTapScratch { size_t part_val, part_idx, part_stat, mask, seed, fin, total; };
+static StepTapScratch step_tap_scratch(size_t S, size_t nb, size_t V) {
+  StepTapScratch l;
+  const size_t R = S * nb;
+  size_t used = 0;
+  auto take = [&](size_t bytes) { const size_t o = used; used += align_up(bytes, 256); return o; };
+  l.part_val = take(R * 16 * 16 * sizeof(float));
+  l.part_idx = take(R * 16 * 16 * sizeof(int));
+  l.part_stat = take(R * 16 * 2 * sizeof(float));
+  l.mask = take(align_up(V, 4));
+  l.seed = take(8);
+  l.fin = take(S * sizeof(int));
+  l.total = used;
+  return l;
+}
+static bool step_tap_geometry_ok(int S, int nb, int V) { return S >= 1 && S <= (1 << 16) && nb >= 1 && nb <= MAX_BEAMS && V >= 1 && V <= (1 << 24); }
+
+static int decode_step_tap(const wseg_decode_step_params* p, const wseg_decode_step_state* a, const float* logits, const int32_t* list,
+                           int32_t n_list, void* scratch, size_t scratch_bytes, int32_t* out_tokens, int32_t* out_lengths,
+                           int32_t n_out_rows, hipStream_t s) {
+#define WSEG_TRY(expr) do { int _s = (expr); if (_s != WSEG_OK) return _s; } while (0)
+#define WSEG_TAP_REQUIRE(COND, ...) do { if (!(COND)) { set_error("wseg_debug_decode_step: " __VA_ARGS__); return WSEG_ERR_INVALID; } } while (0)
+  WSEG_TAP_REQUIRE(p, "params is null");
+  WSEG_TAP_REQUIRE(a, "state is null");
+  const int S = p->n_slots, nb = p->num_beams, L = p->max_length, V = p->vocab, P = p->prompt_len;
+  WSEG_TAP_REQUIRE(S >= 1 && S <= (1 << 16), "n_slots %d unsupported (1..65536)", S);
+  WSEG_TAP_REQUIRE(nb >= 1 && nb <= MAX_BEAMS, "num_beams %d unsupported (1..%d)", nb, MAX_BEAMS);
+  WSEG_TAP_REQUIRE(p->top_k >= 0 && p->top_k <= MAX_CAND, "top_k %d unsupported (0..%d)", p->top_k, MAX_CAND);
+  const int top_k = (nb == 1 && p->top_k > 1) ? p->top_k : 1;
+  const int Kc = nb == 1 ? top_k : 2 * nb;
+  WSEG_TAP_REQUIRE(V >= Kc && V <= (1 << 24), "vocab %d unsupported (%d candidates per row .. 16777216)", V, Kc);
+  WSEG_TAP_REQUIRE(p->ldv >= V && p->ldv % 4 == 0, "ldv %d must be a multiple of 4 and at least vocab %d", p->ldv, V);
+  WSEG_TAP_REQUIRE(P >= 1 && P <= 8, "prompt_len %d unsupported (1..8)", P);
+  WSEG_TAP_REQUIRE(L > P && L <= 4096, "max_length %d must exceed prompt_len %d (and be at most 4096)", L, P);
+  WSEG_TAP_REQUIRE(p->n_suppress >= 0 && (p->n_suppress == 0 || p->suppress_tokens), "suppress_tokens is null with n_suppress %d", p->n_suppress);
+  WSEG_TAP_REQUIRE(p->n_begin_suppress >= 0 && (p->n_begin_suppress == 0 || p->begin_suppress_tokens),
+                   "begin_suppress_tokens is null with n_begin_suppress %d", p->n_begin_suppress);
+#define WSEG_TAP_PTR(F) WSEG_TAP_REQUIRE(a->F, "state array " #F " is null")
+  WSEG_TAP_PTR(pos); WSEG_TAP_PTR(done); WSEG_TAP_PTR(win); WSEG_TAP_PTR(wmax); WSEG_TAP_PTR(unsat); WSEG_TAP_PTR(tokens_in);
+  WSEG_TAP_PTR(run_score); WSEG_TAP_PTR(fin_score); WSEG_TAP_PTR(fin_flag); WSEG_TAP_PTR(fin_len); WSEG_TAP_PTR(run_seq);
+  WSEG_TAP_PTR(fin_seq); WSEG_TAP_PTR(anc); WSEG_TAP_PTR(cand_val); WSEG_TAP_PTR(cand_tok);
+#undef WSEG_TAP_PTR
+  WSEG_TAP_REQUIRE(logits, "logits is null");
+  WSEG_TAP_REQUIRE(((uintptr_t)logits & 15) == 0, "logits is not 16-byte aligned");
+  WSEG_TAP_REQUIRE(list ? (n_list >= 1 && n_list <= S) : n_list == 0, "n_list %d does not fit list (%s) and n_slots %d", n_list, list ? "given" : "null", S);
+  WSEG_TAP_REQUIRE(scratch, "scratch is null");
+  const StepTapScratch lay = step_tap_scratch((size_t)S, (size_t)nb, (size_t)V);
+  WSEG_TAP_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch is not 256-byte aligned");
+  WSEG_TAP_REQUIRE(scratch_bytes >= lay.total, "scratch of %zu bytes is short of the %zu that wseg_debug_decode_step_scratch_bytes asks for", scratch_bytes, lay.total);
+  WSEG_TAP_REQUIRE((out_tokens != nullptr) == (out_lengths != nullptr), "out_tokens and out_lengths go together");
+  WSEG_TAP_REQUIRE(out_tokens ? n_out_rows >= 1 : n_out_rows == 0, "n_out_rows %d does not fit out_tokens (%s)", n_out_rows, out_tokens ? "given" : "null");
+
+  // the state the kernels index with is checked before they run: a position past the sequences or a slot past the arrays is refused
+  std::vector<int> h_pos(S), h_done(S), h_win(S), h_list(list ? n_list : 0);
+  WSEG_HIP_CHECK(hipMemcpyAsync(h_pos.data(), a->pos, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, s));
+  WSEG_HIP_CHECK(hipMemcpyAsync(h_done.data(), a->done, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, s));
+  WSEG_HIP_CHECK(hipMemcpyAsync(h_win.data(), a->win, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (list) { WSEG_HIP_CHECK(hipMemcpyAsync(h_list.data(), list, (size_t)n_list * sizeof(int), hipMemcpyDeviceToHost, s)); }
+  WSEG_HIP_CHECK(hipStreamSynchronize(s));
+  std::vector<char> stepped(S, list ? 0 : 1);
+  for (int i = 0; i < (int)h_list.size(); ++i) {
+    WSEG_TAP_REQUIRE(h_list[i] >= 0 && h_list[i] < S, "list[%d] = %d is no slot of %d", i, h_list[i], S);
+    WSEG_TAP_REQUIRE(!stepped[h_list[i]], "list names slot %d twice", h_list[i]);
+    stepped[h_list[i]] = 1;
+  }
+  for (int w = 0; w < S; ++w) {
+    if (!stepped[w] || h_done[w]) continue;
+    WSEG_TAP_REQUIRE(h_pos[w] >= 0 && h_pos[w] + 1 < L, "pos[%d] = %d leaves no room in max_length %d", w, h_pos[w], L);
+    WSEG_TAP_REQUIRE(h_win[w] >= 0 && h_win[w] < (1 << 20), "win[%d] = %d unsupported", w, h_win[w]);
+    WSEG_TAP_REQUIRE(!out_tokens || h_win[w] < n_out_rows, "win[%d] = %d is past the %d output rows", w, h_win[w], n_out_rows);
+  }
+#undef WSEG_TAP_REQUIRE
+
+  char* base = (char*)scratch;
+  DecodeState st = DecodeState();
+  st.W = S; st.nb = nb; st.L = L; st.V = V; st.ldv = p->ldv; st.P = P;
+  st.eos = p->eos_token_id; st.pad = p->pad_token_id; st.max_length = L; st.length_penalty = p->length_penalty;
+  for (int i = 0; i < 8; ++i) st.prompt[i] = i < P ? p->prompt[i] : 0;
+  st.pos = a->pos; st.done = a->done; st.win = a->win; st.wmax = a->wmax; st.unsat = a->unsat; st.tokens_in = a->tokens_in;
+  st.run_seq = a->run_seq; st.fin_seq = a->fin_seq; st.run_score = a->run_score; st.fin_score = a->fin_score;
+  st.fin_flag = a->fin_flag; st.fin_len = a->fin_len; st.anc = a->anc; st.cand_val = a->cand_val; st.cand_tok = a->cand_tok;
+  st.top_k = top_k; st.top_p = p->top_p;
+  st.seed = (const unsigned long long*)(base + lay.seed);
+  st.sup_mask = (const unsigned char*)(base + lay.mask);
+  const unsigned long long seed = p->seed;
+  WSEG_HIP_CHECK(hipMemcpyAsync(base + lay.seed, &seed, 8, hipMemcpyHostToDevice, s));
+  WSEG_HIP_CHECK(hipMemsetAsync(base + lay.mask, 0, align_up((size_t)V, 4), s));
+  WSEG_TRY(launch_build_suppress_mask((unsigned char*)(base + lay.mask), V, p->suppress_tokens, p->n_suppress,
+                                      p->begin_suppress_tokens, p->n_begin_suppress, s));
+  WSEG_TRY(launch_row_topk(st, logits, (float*)(base + lay.part_val), (int*)(base + lay.part_idx), (float*)(base + lay.part_stat), s, list, n_list));
+  WSEG_TRY(nb > 1 ? launch_beam_step(st, s, list, n_list) : launch_greedy_step(st, s, list, n_list));
+  std::vector<int> fin;      // source of an asynchronous copy: lives until the synchronisation at the end
+  if (out_tokens) {      // retire the slots that this step finished
+    std::vector<int> after(S);
+    WSEG_HIP_CHECK(hipMemcpyAsync(after.data(), a->done, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, s));
+    WSEG_HIP_CHECK(hipStreamSynchronize(s));
+    for (int w = 0; w < S; ++w) if (stepped[w] && !h_done[w] && after[w]) fin.push_back(w);
+    if (!fin.empty()) {
+      WSEG_HIP_CHECK(hipMemcpyAsync(base + lay.fin, fin.data(), fin.size() * sizeof(int), hipMemcpyHostToDevice, s));
+      WSEG_TRY(launch_finalize(st, (const int*)(base + lay.fin), (int)fin.size(), out_tokens, out_lengths, s));
+    }
+  }
+  WSEG_HIP_CHECK(hipStreamSynchronize(s));      // `seed` and `fin` are host locals
+  return WSEG_OK;
+#undef WSEG_TRY
+}
+
 }  // namespace wseg
+
+extern "C" size_t wseg_debug_decode_step_scratch_bytes(int32_t n_slots, int32_t num_beams, int32_t vocab) {
+  if (!wseg::step_tap_geometry_ok(n_slots, num_beams, vocab)) return 0;
+  return wseg::step_tap_scratch((size_t)n_slots, (size_t)num_beams, (size_t)vocab).total;
+}
+extern "C" int wseg_debug_decode_step(const wseg_decode_step_params* p, const wseg_decode_step_state* state, const float* logits,
+                                      const int32_t* list, int32_t n_list, void* scratch, size_t scratch_bytes, int32_t* out_tokens,
+                                      int32_t* out_lengths, int32_t n_out_rows, void* stream) {
+  return wseg::decode_step_tap(p, state, logits, list, n_list, scratch, scratch_bytes, out_tokens, out_lengths, n_out_rows, (hipStream_t)stream);
+}
 
 #ifdef WSEG_STAMPS
 extern "C" int wseg_debug_stamps(unsigned long long* out) {
