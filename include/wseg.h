@@ -268,6 +268,31 @@ int wseg_patches_f32(const wseg_logmel_desc* d, const float* pcm, int64_t n, con
                      int32_t width, void* scratch, size_t scratch_bytes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * k nearest neighbours of every query row among the corpus rows (the graph clustering, embedding and "calls like this one" start
+ * from; over the patches above or any float32 rows) under the squared Euclidean distance.  whisperseg_amd/neighbors.py::
+ * neighbors_host is the definition (numpy, float64): d(i, j) = sum_c (q[i][c] - x[j][c])^2 in the direct form; the neighbours of
+ * row i are the k candidates that come first in the total order (d(i, j), j), ascending.  The m x n matrix never exists: a
+ * selection kernel forms |q|^2 + |x|^2 - 2 q.x tile by tile on the fp32 matrix cores (every term one c-ordered fmaf chain: the
+ * same bits for every tiling, grid and split) and keeps the k + 8 best per row; a finish kernel recomputes the direct form of
+ * those with fp64 accumulation, orders them by (that distance as float32, j) and writes the first k — the selection's
+ * cancellation error (<= 2 (d + 4) 2^-24 (|q|^2 + |x|^2)) only matters at the k-th boundary and shows in no reported distance.
+ * queries: device float32 [m][d]; corpus: device float32 [n][d] (may be queries); m, n 0 .. 2^31 - 1, d 1 .. 20480, k 1 .. 64.
+ * exclude_same_index 1: j == i is no candidate (queries == corpus; by index, not by value).  Inputs must be finite; with
+ * non-finite input the order is unspecified, and still nothing outside the outputs and scratch is written, nothing outside
+ * queries and corpus read.  index_out: device int32 [m][k]; distance_out: device float32 [m][k]; where a row has fewer than k
+ * candidates its tail is -1 / +inf.  scratch: device, 8-byte aligned, wseg_knn_scratch_bytes(m, n, d, k) bytes — host arithmetic,
+ * no device, monotone in every argument; 0 with the reason in wseg_last_error() for sizes out of range.
+ * m == 0 returns 0 without a launch; n == 0 only fills -1 / +inf.  Every argument is validated on the host before a launch
+ * (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * $WSEG_KNN_GRID: a TEST knob, the cap on the grids and with it the candidate splits (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_knn_scratch_bytes(int64_t m, int64_t n, int32_t d, int32_t k);
+int wseg_knn_f32(const float* queries, int64_t m, const float* corpus, int64_t n, int32_t d, int32_t k,
+                 int32_t exclude_same_index, void* scratch, size_t scratch_bytes, int32_t* index_out, float* distance_out,
+                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

@@ -20,6 +20,9 @@ zero-crossing rate, peak / centroid / 5 % / 95 % frequency, spectral entropy), t
 --patches W --patches_save_path FILE.npz (each needs the other) saves one time-normalised log-mel picture of W columns per row
 (whisperseg_amd.patches, computed on the GPU from the same samples): `patch` float32 [rows, 80, W] in the CSV's row order, with `onset`,
 `offset`, `cluster` and, where the CSV has those columns, `filename` / `channel`.  The CSV is what it is without the flags.
+--neighbors K (needs --patches and --patches_save_path) adds the K nearest neighbours of every row among all rows of the archive,
+found on the GPU (whisperseg_amd.neighbors): `neighbor_index` int32 [rows, K] — rows of the archive, which is the CSV's row order;
+-1 where fewer than K other rows exist — and `neighbor_distance` float32 [rows, K], the squared Euclidean distance of the pictures.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -72,11 +75,14 @@ def build_parser():
     p.add_argument("--patches", default=None, type=int, metavar="W",
                    help="save one log-mel picture of W columns (1 .. 256) per row to --patches_save_path")
     p.add_argument("--patches_save_path", default=None, metavar="FILE.npz", help="where --patches W saves the pictures (numpy .npz)")
+    p.add_argument("--neighbors", default=None, type=int, metavar="K",
+                   help="add the K (1 .. 64) nearest neighbours of every row among the saved pictures to --patches_save_path")
     return p
 
 
 def parse_args(argv=None):
-    """The parsed arguments; --patches and --patches_save_path without each other, or a width outside 1 .. 256, are argparse errors."""
+    """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors without them
+    or a K outside 1 .. 64 are argparse errors."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if (args.patches is None) != (args.patches_save_path is None):
@@ -85,6 +91,10 @@ def parse_args(argv=None):
         parser.error("--patches must be 1 .. 256 columns")
     if args.patches_save_path is not None and not args.patches_save_path.endswith(".npz"):
         parser.error("--patches_save_path must end with .npz")
+    if args.neighbors is not None and args.patches is None:
+        parser.error("--neighbors K needs --patches W and --patches_save_path FILE.npz")
+    if args.neighbors is not None and not 1 <= args.neighbors <= 64:
+        parser.error("--neighbors must be 1 .. 64")
     return args
 
 
@@ -183,7 +193,11 @@ def main(argv=None):
     columns, rows = table(*tabled, measure=args.measure)
     if args.patches is not None:
         import numpy as np
-        np.savez(args.patches_save_path, **patch_archive(*tabled, width=args.patches))
+        archive = patch_archive(*tabled, width=args.patches)
+        if args.neighbors is not None:
+            from whisperseg_amd.neighbors import patch_neighbors
+            archive.update(patch_neighbors(tabled[0], args.neighbors))
+        np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()
         write_csv(columns, rows, buf)
