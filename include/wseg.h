@@ -293,6 +293,34 @@ int wseg_knn_f32(const float* queries, int64_t m, const float* corpus, int64_t n
                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * One Boruvka round of the minimum spanning tree of the rows under the mutual-reachability distance — the N^2 D part of
+ * density-based clustering (HDBSCAN, DBSCAN*, robust single linkage) of the patches above or any float32 rows.
+ * whisperseg_amd/linkage.py::mst_host is the definition of the tree (numpy, float64) and linkage.py::mst drives the rounds:
+ * d32(i, j) = float32(sum_c (x[i][c] - x[j][c])^2) in the direct form, w(i, j) = max(core[i], core[j], d32(i, j)).
+ * For every row i the call writes index_out[i] = the j with component[j] != component[i] that comes first in the order
+ * (w(i, j), j) and weight_out[i] = w(i, j); -1 / +inf where no such j exists.  The n x n matrix never exists: a selection kernel
+ * forms max(core_i, core_j, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) tile by tile on the fp32 matrix cores (every term one c-ordered fmaf
+ * chain: the same bits for every tiling, grid and split) and keeps the 1 + 8 best per row; a finish kernel recomputes the direct
+ * form of those with fp64 accumulation (symmetric: d32(i, j) and d32(j, i) have the same bits) and writes the first under
+ * (exact w, j) — the selection's cancellation error (<= 2 (d + 4) 2^-24 (|x_i|^2 + |x_j|^2)) decides only which nine candidates
+ * are looked at and shows in no reported weight.
+ * rows: device float32 [n][d]; n 0 .. 2^31 - 1, d 1 .. 20480.  core: device float32 [n], finite, >= 0 (the caller's: for HDBSCAN
+ * the squared distance to the s-th nearest other row, wseg_knn_f32's column s - 1).  component: device int32 [n], any values,
+ * only compared for equality (a row is of its own component: it is never its own candidate).  Inputs must be finite; with
+ * non-finite input the choice is unspecified, and still nothing outside the outputs and scratch is written, nothing outside rows,
+ * core and component read.  index_out: device int32 [n]; weight_out: device float32 [n].  scratch: device, 8-byte aligned,
+ * wseg_mst_scratch_bytes(n, d) bytes — host arithmetic, no device, monotone in n and d; 0 with the reason in wseg_last_error()
+ * for sizes out of range.
+ * n == 0 returns 0 without a launch.  Every argument is validated on the host before a launch (WSEG_ERR_INVALID, the argument's
+ * name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * $WSEG_MST_GRID: a TEST knob, the cap on the grids and with it the candidate splits (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_mst_scratch_bytes(int64_t n, int32_t d);
+int wseg_mst_round_f32(const float* rows, int64_t n, int32_t d, const float* core, const int32_t* component, void* scratch,
+                       size_t scratch_bytes, int32_t* index_out, float* weight_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

@@ -23,6 +23,11 @@ zero-crossing rate, peak / centroid / 5 % / 95 % frequency, spectral entropy), t
 --neighbors K (needs --patches and --patches_save_path) adds the K nearest neighbours of every row among all rows of the archive,
 found on the GPU (whisperseg_amd.neighbors): `neighbor_index` int32 [rows, K] — rows of the archive, which is the CSV's row order;
 -1 where fewer than K other rows exist — and `neighbor_distance` float32 [rows, K], the squared Euclidean distance of the pictures.
+--clusters MIN_SIZE [--cluster_min_samples S] (needs --patches and --patches_save_path) groups the rows of the archive into call
+types by HDBSCAN over the pictures (whisperseg_amd.linkage; the mutual-reachability minimum spanning tree is built on the GPU):
+`patch_cluster` int32 [rows] — clusters of at least MIN_SIZE rows numbered by their first row, -1: noise (the archive's `cluster`
+stays the model's label) — with the tree itself, `mst_edges` int32 [rows - 1, 2] and `mst_weight` float32 [rows - 1] (squared
+distances), for a cut at another level (linkage.cut).  S (1 .. 64, default 5; lowered to rows - 1) counts OTHER rows.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -77,12 +82,17 @@ def build_parser():
     p.add_argument("--patches_save_path", default=None, metavar="FILE.npz", help="where --patches W saves the pictures (numpy .npz)")
     p.add_argument("--neighbors", default=None, type=int, metavar="K",
                    help="add the K (1 .. 64) nearest neighbours of every row among the saved pictures to --patches_save_path")
+    p.add_argument("--clusters", default=None, type=int, metavar="MIN_SIZE",
+                   help="add HDBSCAN clusters of at least MIN_SIZE (>= 2) rows over the saved pictures, and their spanning tree, to --patches_save_path")
+    p.add_argument("--cluster_min_samples", default=None, type=int, metavar="S",
+                   help="--clusters: the core distance of a row is the distance to its S-th nearest other row (1 .. 64, default 5)")
     return p
 
 
 def parse_args(argv=None):
-    """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors without them
-    or a K outside 1 .. 64 are argparse errors."""
+    """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors or --clusters
+    without them, a K outside 1 .. 64, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
+    errors."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if (args.patches is None) != (args.patches_save_path is None):
@@ -95,6 +105,16 @@ def parse_args(argv=None):
         parser.error("--neighbors K needs --patches W and --patches_save_path FILE.npz")
     if args.neighbors is not None and not 1 <= args.neighbors <= 64:
         parser.error("--neighbors must be 1 .. 64")
+    if args.clusters is not None and args.patches is None:
+        parser.error("--clusters MIN_SIZE needs --patches W and --patches_save_path FILE.npz")
+    if args.clusters is not None and args.clusters < 2:
+        parser.error("--clusters must be at least 2 rows")
+    if args.cluster_min_samples is not None and args.clusters is None:
+        parser.error("--cluster_min_samples S needs --clusters MIN_SIZE")
+    if args.cluster_min_samples is None:
+        args.cluster_min_samples = 5
+    elif not 1 <= args.cluster_min_samples <= 64:
+        parser.error("--cluster_min_samples must be 1 .. 64")
     return args
 
 
@@ -197,6 +217,10 @@ def main(argv=None):
         if args.neighbors is not None:
             from whisperseg_amd.neighbors import patch_neighbors
             archive.update(patch_neighbors(tabled[0], args.neighbors))
+        if args.clusters is not None:
+            from whisperseg_amd.linkage import patch_clusters
+            found = patch_clusters(tabled[0], args.clusters, args.cluster_min_samples)
+            archive.update(patch_cluster=found["cluster"], mst_edges=found["mst_edges"], mst_weight=found["mst_weight"])
         np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()
