@@ -321,6 +321,30 @@ int wseg_mst_round_f32(const float* rows, int64_t n, int32_t d, const float* cor
                        size_t scratch_bytes, int32_t* index_out, float* weight_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Layout epochs of the 2-D / 3-D embedding of the calls: a synchronous variant of UMAP's optimiser over a weighted graph in CSR
+ * form.  whisperseg_amd/embed.py::layout_host is the definition (numpy, float64: the schedule, the counter-based negative samples,
+ * a term and the order of an epoch's sums) and embed.py::layout the caller.  The call runs the epochs t0 .. t1 - 1 of total_epochs,
+ * one launch each: epoch t gives every vertex i  y[i] + lr (1 - t / total_epochs) G_i, G_i the sum IN CSR ORDER over the entries e
+ * of row i that are active in epoch t (((t + 1) rate[e]) >> 16 != (t rate[e]) >> 16) of the attraction term towards indices[e] and
+ * then the repulsion terms of n_neg negative samples, all read from the positions epoch t - 1 left — the epochs ping-pong between
+ * y_out and scratch and the last one writes y_out.  float64 throughout; with b == 1 (the instance without pow) the positions are
+ * the definition's bit for bit, with another b they differ by the two pow functions' difference.
+ * indptr: device int64 [n + 1]; indices: device int32 [nnz]; rate: device uint32 [nnz] (0 .. 65536); n 0 .. 2^31 - 1, nnz 0 .. 2^38,
+ * dim 2 or 3.  An entry whose index is outside 0 .. n - 1 and the part of a row outside 0 .. nnz contribute nothing, so nothing
+ * outside the inputs is read whatever they hold.  y_in, y_out: device float64 [n][dim]; scratch: device, 8-byte aligned,
+ * wseg_embed_scratch_bytes(n, dim) bytes — host arithmetic, no device; 0 with the reason in wseg_last_error() for sizes out of
+ * range; the three must not overlap.  0 <= t0 < t1 <= total_epochs <= 2^31 - 1; n_neg 0 .. 16; lr, gamma finite, a >= 0, b > 0.
+ * n == 0 returns 0 without a launch.  Every argument is validated on the host before a launch (WSEG_ERR_INVALID, the argument's
+ * name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_embed_scratch_bytes(int64_t n, int32_t dim);
+int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const uint32_t* rate, int64_t n, int64_t nnz, int32_t dim,
+                          const double* y_in, double* y_out, void* scratch, size_t scratch_bytes, int64_t t0, int64_t t1,
+                          int64_t total_epochs, double lr, double a, double b, double gamma, int32_t n_neg, uint64_t seed,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

@@ -28,6 +28,11 @@ types by HDBSCAN over the pictures (whisperseg_amd.linkage; the mutual-reachabil
 `patch_cluster` int32 [rows] — clusters of at least MIN_SIZE rows numbered by their first row, -1: noise (the archive's `cluster`
 stays the model's label) — with the tree itself, `mst_edges` int32 [rows - 1, 2] and `mst_weight` float32 [rows - 1] (squared
 distances), for a cut at another level (linkage.cut).  S (1 .. 64, default 5; lowered to rows - 1) counts OTHER rows.
+--embed DIM [--embed_neighbors K] [--embed_min_dist X] [--embed_seed S] (needs --patches and --patches_save_path) adds the map of
+the rows of the archive: `embedding` float32 [rows, DIM], DIM 2 or 3 — the UMAP layout (whisperseg_amd.embed; its epochs run on the
+GPU) of the fuzzy graph of the K (1 .. 64, default 15) nearest neighbours of every picture, with min_dist X (0 <= X < 1, default
+0.1) and the hash seed S (default 0): the same bits for the same rows on every run.  With --neighbors K of the same K the lists
+are computed once.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -86,13 +91,19 @@ def build_parser():
                    help="add HDBSCAN clusters of at least MIN_SIZE (>= 2) rows over the saved pictures, and their spanning tree, to --patches_save_path")
     p.add_argument("--cluster_min_samples", default=None, type=int, metavar="S",
                    help="--clusters: the core distance of a row is the distance to its S-th nearest other row (1 .. 64, default 5)")
+    p.add_argument("--embed", default=None, type=int, metavar="DIM",
+                   help="add the 2-D or 3-D UMAP layout of the saved pictures (`embedding` [rows, DIM]) to --patches_save_path")
+    p.add_argument("--embed_neighbors", default=None, type=int, metavar="K", help="--embed: neighbours a row of the graph (1 .. 64, default 15)")
+    p.add_argument("--embed_min_dist", default=None, type=float, metavar="X", help="--embed: UMAP's min_dist, 0 <= X < 1 (default 0.1)")
+    p.add_argument("--embed_seed", default=None, type=int, metavar="S", help="--embed: the seed of the start and the negative samples (default 0)")
     return p
 
 
 def parse_args(argv=None):
     """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors or --clusters
     without them, a K outside 1 .. 64, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
-    errors."""
+    errors; so are --embed without the patches, a DIM other than 2 or 3, --embed_neighbors outside 1 .. 64, --embed_min_dist outside
+    [0, 1), a negative --embed_seed and any of the three without --embed."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if (args.patches is None) != (args.patches_save_path is None):
@@ -115,6 +126,25 @@ def parse_args(argv=None):
         args.cluster_min_samples = 5
     elif not 1 <= args.cluster_min_samples <= 64:
         parser.error("--cluster_min_samples must be 1 .. 64")
+    if args.embed is not None and args.patches is None:
+        parser.error("--embed DIM needs --patches W and --patches_save_path FILE.npz")
+    if args.embed is not None and args.embed not in (2, 3):
+        parser.error("--embed must be 2 or 3 dimensions")
+    for name in ("embed_neighbors", "embed_min_dist", "embed_seed"):
+        if getattr(args, name) is not None and args.embed is None:
+            parser.error(f"--{name} needs --embed DIM")
+    if args.embed_neighbors is None:
+        args.embed_neighbors = 15
+    elif not 1 <= args.embed_neighbors <= 64:
+        parser.error("--embed_neighbors must be 1 .. 64")
+    if args.embed_min_dist is None:
+        args.embed_min_dist = 0.1
+    elif not 0 <= args.embed_min_dist < 1:
+        parser.error("--embed_min_dist must lie in [0, 1)")
+    if args.embed_seed is None:
+        args.embed_seed = 0
+    elif not 0 <= args.embed_seed < 2 ** 64:
+        parser.error("--embed_seed must be 0 .. 2^64 - 1")
     return args
 
 
@@ -216,11 +246,17 @@ def main(argv=None):
         archive = patch_archive(*tabled, width=args.patches)
         if args.neighbors is not None:
             from whisperseg_amd.neighbors import patch_neighbors
-            archive.update(patch_neighbors(tabled[0], args.neighbors))
+            lists = patch_neighbors(tabled[0], args.neighbors)
+            archive.update(lists)
         if args.clusters is not None:
             from whisperseg_amd.linkage import patch_clusters
             found = patch_clusters(tabled[0], args.clusters, args.cluster_min_samples)
             archive.update(patch_cluster=found["cluster"], mst_edges=found["mst_edges"], mst_weight=found["mst_weight"])
+        if args.embed is not None:
+            from whisperseg_amd.embed import patch_embedding
+            shared = args.neighbors == args.embed_neighbors          # the same K: the lists are computed once
+            archive.update(patch_embedding(tabled[0], args.embed_neighbors, args.embed, args.embed_min_dist, seed=args.embed_seed,
+                                           lists=(lists["neighbor_index"], lists["neighbor_distance"]) if shared else None))
         np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()

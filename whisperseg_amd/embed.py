@@ -1,0 +1,411 @@
+"""A map of the calls: the 2-D (or 3-D) UMAP layout of the per-segment patches (whisperseg_amd.patches) or any float32 rows, on which
+a folder's calls are looked at, coloured by their cluster (whisperseg_amd.linkage) and outliers picked.  Given the nearest-neighbour
+lists (whisperseg_amd.neighbors) the expensive part is the layout — epochs x active edges x (1 + negatives) force evaluations — and
+that is the part on the GPU (wseg_embed_epochs_f64: whisperseg_amd/csrc/wseg_embed.hip); the graph is O(N k) host work.
+
+`fuzzy_graph_host` and `layout_host` are THE definition (numpy, float64) and the oracle of every device test; `layout` runs the same
+epochs on the GPU; `embed` goes from rows to positions and `patch_embedding` takes what `segment*(..., patches=W)` returned.
+
+The layout is a SYNCHRONOUS variant of UMAP's optimiser (McInnes, Healy, Melville 2018): every epoch reads only the positions the
+epoch before it left, every vertex moves by the sum of its own terms, and the negative samples come from a counter-based hash — so a
+result is one function of its input: no races, no atomics, nothing that depends on a grid, a thread count or a run.  With
+(indptr, indices, weight) a symmetric CSR over N vertices, positions y float64 [N, dim], dim 2 or 3, and T epochs in all:
+
+  schedule       rate_e = floor(w_e / w_max * 65536 + 0.5) (uint32); entries of rate 0 are dropped from the CSR before anything
+                 runs and nnz counts the rest; entry e (its position in that CSR) is ACTIVE in epoch t iff
+                 ((t + 1) * rate_e) >> 16 != (t * rate_e) >> 16: rate 65536 every epoch, 32768 every second one
+  hash           mix(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31 (splitmix64's
+                 finaliser; uint64, wrapping); draw(c) = mix(seed * 0x9E3779B97F4A7C15 + c)
+  negatives      sample s = 0 .. n_neg - 1 of the active entry e of row i in epoch t is the vertex
+                 m = ((draw((t * nnz + e) * n_neg + s) >> 32) * N) >> 32; m == i is skipped and contributes nothing
+  init           None: y0[i][c] = -10 + 20 * ((draw(2^63 + i * dim + c) >> 11) * 2^-53); or an array [N, dim], used as given
+  a term         delta = y_i - y_j per component; d2 = the left-to-right sum of delta_c * delta_c; P = d2 if b == 1.0 else
+                 pow(d2, b) (numpy's float64 power)
+                 attraction (j = indices[e]):   coef = ((-2 a) b P) / (d2 (1 + a P)), 0 where d2 == 0
+                 repulsion (j = a negative m):  coef = ((2 gamma) b) / ((0.001 + d2) (1 + a P))
+                 g_c = min(4, max(-4, coef * delta_c))
+  an epoch       for vertex i: G = 0; for its entries in CSR order, if the entry is active: G += its attraction term, then G += the
+                 repulsion term of each of its negatives in the order of s; y_out[i] = y_in[i] + alpha_t * G with
+                 alpha_t = lr * (1 - t / T)
+  conventions    positions must stay small enough that d2 and P are finite (a clipped term moves a coordinate by at most 4 lr);
+                 a dim other than 2 or 3, fewer than 1 epoch, an n_neg outside 0 .. 16, a min_dist outside [0, spread) or an init
+                 that is not finite [N, dim]: ValueError before anything runs
+
+What the device may differ by: nothing where b == 1 — float64 + - * / are correctly rounded on both sides and nothing is contracted,
+so every coordinate has the definition's bits after any number of epochs; with another b a term differs by what the device's pow and
+numpy's differ by (tests/embed_cases.py derives the bound of one epoch).
+"""
+import numpy as np
+
+from . import neighbors as NB
+
+MAX_NEG = 16                           # negative samples of an active entry (csrc/wseg_embed_plan.h::kEmbedMaxNeg)
+MASK = (1 << 64) - 1
+GOLDEN = 0x9E3779B97F4A7C15
+INIT_COUNTER = 1 << 63
+BISECTION_STEPS = 64
+_M1, _M2 = np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+# ---- the graph (host) ----------------------------------------------------------------------------------------------------------------
+def fuzzy_graph_host(index, distance):
+    """The fuzzy graph of UMAP from the nearest-neighbour lists `index` int [N, k] and `distance` [N, k] exactly as
+    neighbors.neighbors returns them (SQUARED float32 distances; entries of index -1 are ignored, and so is a row's own index)
+    -> (indptr int64 [N + 1], indices int32 [nnz] ascending within a row, weight float64 [nnz]): a symmetric CSR without a diagonal.
+
+    Per row i, over its entries j in list order, in float64:
+      d_j    = sqrt(float64(distance[i, j]))
+      rho    = the smallest d_j > 0, or 0 if there is none
+      sigma  : lo = 0, hi = inf, mid = 1; exactly 64 times: psum = sum_j exp(-max(0, d_j - rho) / mid) (left to right);
+               if psum > log2(k): hi = mid, mid = (lo + hi) / 2; else: lo = mid, mid = 2 mid while hi is inf, (lo + hi) / 2 after.
+               sigma = mid — umap-learn's bisection without its early exit, so that the result is one function of the input
+      floor  : sigma = max(sigma, 1e-3 * mean_j d_j); where that is 0 every weight of the row is 1
+      p(i→j) = exp(-max(0, d_j - rho) / sigma)
+    and w(i, j) = min(1, p + q - p q) with p = p(i→j), q = p(j→i), each 0 where the other row does not list this one (the min takes
+    back a last-bit excess of the rounded sum).  Entries whose weight underflowed to 0 are left out, so every weight lies in (0, 1]."""
+    index, distance = np.asarray(index), np.asarray(distance)
+    if index.ndim != 2 or index.shape != distance.shape or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"index (integer) and distance must both be [N, k] (got {index.shape} and {distance.shape})")
+    n, k = index.shape
+    if n and (index.max(initial=-1) >= n or index.min(initial=0) < -1):
+        raise ValueError("an index names a row outside 0 .. N - 1")
+    if n == 0 or k == 0:
+        return np.zeros(n + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64)
+    valid = (index >= 0) & (index != np.arange(n)[:, None])
+    if not np.isfinite(np.asarray(distance, np.float64)[valid]).all() or (np.asarray(distance, np.float64)[valid] < 0).any():
+        raise ValueError("the distances of the listed neighbours must be finite and not negative")
+    d = np.sqrt(np.where(valid, distance, 0).astype(np.float64))
+    rho = np.where(valid & (d > 0), d, np.inf).min(axis=1)
+    rho = np.where(np.isinf(rho), 0.0, rho)
+    over = np.maximum(0.0, d - rho[:, None])
+
+    def row_sum(terms):                                  # left to right over the list; an entry that is not there adds 0
+        total = np.zeros(n)
+        for c in range(k):
+            total = total + np.where(valid[:, c], terms[:, c], 0.0)
+        return total
+
+    target = np.log2(float(k))
+    lo, hi, mid = np.zeros(n), np.full(n, np.inf), np.ones(n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for _ in range(BISECTION_STEPS):
+            above = row_sum(np.exp(-over / mid[:, None])) > target
+            hi = np.where(above, mid, hi)
+            lo = np.where(above, lo, mid)
+            mid = np.where(np.isinf(hi), mid * 2.0, (lo + hi) / 2.0)
+    count = valid.sum(axis=1)
+    mean = row_sum(d) / np.maximum(count, 1)
+    sigma = np.maximum(mid, 1e-3 * mean)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(sigma[:, None] == 0, 1.0, np.exp(-over / sigma[:, None]))
+    # symmetrise over the union of (i, j) and (j, i); a pair a row lists twice counts once (its first entry)
+    i_of = np.repeat(np.arange(n, dtype=np.int64), k)[valid.ravel()]
+    j_of = index.astype(np.int64).ravel()[valid.ravel()]
+    key, first = np.unique(i_of * n + j_of, return_index=True)
+    p_of = p.ravel()[valid.ravel()][first]
+    back = (key % n) * n + key // n
+    pairs = np.union1d(key, back)
+    fwd, bwd = np.zeros(len(pairs)), np.zeros(len(pairs))
+    fwd[np.searchsorted(pairs, key)] = p_of
+    bwd[np.searchsorted(pairs, back)] = p_of
+    weight = np.minimum(1.0, fwd + bwd - fwd * bwd)
+    keep = weight > 0
+    pairs, weight = pairs[keep], weight[keep]
+    indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(pairs // n, minlength=n), out=indptr[1:])
+    return indptr, (pairs % n).astype(np.int32), weight
+
+
+def curve_ab(min_dist, spread=1.0):
+    """(a, b) of the curve 1 / (1 + a x^(2 b)) that fits umap-learn's target in the least-squares sense: at x = linspace(0, 3 spread,
+    300) the value 1 below min_dist and exp(-(x - min_dist) / spread) above it.  Levenberg-Marquardt from a = b = 1 in float64."""
+    min_dist, spread = float(min_dist), float(spread)
+    if not (np.isfinite(spread) and spread > 0):
+        raise ValueError(f"spread must be positive (got {spread!r})")
+    if not 0 <= min_dist < spread:
+        raise ValueError(f"min_dist must lie in [0, spread = {spread}) (got {min_dist!r})")
+    x = np.linspace(0.0, 3.0 * spread, 300)
+    want = np.where(x < min_dist, 1.0, np.exp(-(x - min_dist) / spread))
+    log_x = np.log(x[1:])
+
+    def curve(a, b):                                     # the values and their derivatives by a and b (x = 0: 1, 0, 0)
+        xb = np.concatenate(([0.0], np.exp(2.0 * b * log_x)))
+        f = 1.0 / (1.0 + a * xb)
+        return f, np.stack([-xb * f * f, np.concatenate(([0.0], -a * xb[1:] * 2.0 * log_x * f[1:] * f[1:]))], axis=1)
+
+    ab, damp = np.array([1.0, 1.0]), 1e-3
+    f, jac = curve(*ab)
+    cost = float(((f - want) ** 2).sum())
+    for _ in range(200):
+        normal, grad = jac.T @ jac, jac.T @ (f - want)
+        step = np.linalg.solve(normal + damp * np.diag(np.diag(normal)), -grad)
+        trial = ab + step
+        f_new, jac_new = curve(*trial) if trial[0] > 0 and trial[1] > 0 else (None, None)
+        cost_new = np.inf if f_new is None else float(((f_new - want) ** 2).sum())
+        if cost_new <= cost:
+            small = np.abs(step).max() < 1e-12
+            ab, f, jac, cost, damp = trial, f_new, jac_new, cost_new, max(damp / 10.0, 1e-12)
+            if small:
+                break
+        else:
+            damp *= 10.0
+            if damp > 1e12:
+                break
+    return float(ab[0]), float(ab[1])
+
+
+# ---- the hash, the schedule, the init -------------------------------------------------------------------------------------------------
+def mix64(x):
+    """splitmix64's finaliser of a uint64 array (wrapping)."""
+    x = np.array(x, dtype=np.uint64, ndmin=1)
+    x ^= x >> np.uint64(30)
+    x *= _M1
+    x ^= x >> np.uint64(27)
+    x *= _M2
+    x ^= x >> np.uint64(31)
+    return x
+
+
+def draw(seed, counter):
+    """mix(seed * 0x9E3779B97F4A7C15 + counter) for a uint64 array of counters (wrapping) -> uint64 array."""
+    return mix64(np.array(counter, dtype=np.uint64, ndmin=1) + np.uint64((int(seed) * GOLDEN) & MASK))
+
+
+def negatives(seed, t, nnz, entries, n_neg, n):
+    """int64 [len(entries), n_neg]: the negative samples of the entries (positions in the CSR) in epoch t among n vertices."""
+    e = np.array(entries, dtype=np.uint64, ndmin=1)
+    base = (np.uint64((int(t) * int(nnz)) & MASK) + e) * np.uint64(n_neg)
+    h = draw(seed, base[:, None] + np.arange(n_neg, dtype=np.uint64)[None, :])
+    return (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def rates(weight):
+    """uint32: floor(w / w_max * 65536 + 0.5) of a float64 array of weights (empty: empty)."""
+    w = np.asarray(weight, dtype=np.float64)
+    if not len(w):
+        return np.zeros(0, np.uint32)
+    return np.floor(w / w.max() * 65536.0 + 0.5).astype(np.uint32)
+
+
+def active(rate, t):
+    """bool: which entries of these rates are active in epoch t."""
+    r = np.asarray(rate).astype(np.uint64)
+    return ((np.uint64(t + 1) * r) >> np.uint64(16)) != ((np.uint64(t) * r) >> np.uint64(16))
+
+
+def init_positions(n, dim, seed):
+    """float64 [n, dim]: the hashed start in [-10, 10)."""
+    h = draw(seed, np.uint64(INIT_COUNTER) + np.arange(n * dim, dtype=np.uint64))
+    return (-10.0 + 20.0 * ((h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53)).reshape(n, dim)
+
+
+def scheduled(graph):
+    """(indptr int64 [N + 1], indices int32 [nnz], rate uint32 [nnz]) of the CSR the epochs run on: the graph's entries whose rate is
+    not 0.  ValueError unless the graph is a CSR over N vertices with finite weights that are not negative."""
+    try:
+        indptr, indices, weight = graph
+    except (TypeError, ValueError):
+        raise ValueError("a graph is (indptr [N + 1], indices [nnz], weight [nnz])") from None
+    indptr, indices, weight = np.asarray(indptr), np.asarray(indices), np.asarray(weight, dtype=np.float64)
+    if indptr.ndim != 1 or len(indptr) < 1 or indices.ndim != 1 or weight.shape != indices.shape:
+        raise ValueError("a graph is (indptr [N + 1], indices [nnz], weight [nnz])")
+    n = len(indptr) - 1
+    if n > np.iinfo(np.int32).max:
+        raise ValueError("a graph has at most 2^31 - 1 vertices")
+    indptr = indptr.astype(np.int64)
+    if indptr[0] != 0 or indptr[-1] != len(indices) or (np.diff(indptr) < 0).any():
+        raise ValueError("indptr must ascend from 0 to nnz")
+    if len(indices) and (not np.issubdtype(indices.dtype, np.integer) or indices.min() < 0 or indices.max() >= n):
+        raise ValueError("an entry names a vertex outside 0 .. N - 1")
+    if not np.isfinite(weight).all() or (weight < 0).any():
+        raise ValueError("the weights must be finite and not negative")
+    rate = rates(weight)
+    keep = rate > 0
+    row = np.repeat(np.arange(n), np.diff(indptr))[keep]
+    out = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(row, minlength=n), out=out[1:])
+    return out, np.ascontiguousarray(indices[keep], dtype=np.int32), np.ascontiguousarray(rate[keep])
+
+
+class Run:
+    """The checked arguments of layout_host / layout: the scheduled CSR, the epochs (t0, t1) of T, the parameters and the start."""
+
+    def __init__(self, graph, dim, epochs, total, n_neg, gamma, lr, a, b, init, seed):
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim not in (2, 3):
+            raise ValueError(f"dim must be 2 or 3 (got {dim!r})")
+        whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if isinstance(epochs, (tuple, list)):
+            if len(epochs) != 2 or not all(whole(v) for v in epochs):
+                raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
+            t0, t1 = int(epochs[0]), int(epochs[1])
+            total = t1 if total is None else total
+        elif whole(epochs):
+            t0, t1 = 0, int(epochs)
+            total = t1 if total is None else total
+        else:
+            raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
+        if not whole(total) or not 1 <= int(total) <= 2 ** 31 - 1 or not 0 <= t0 < t1 <= int(total):
+            raise ValueError(f"epochs must be at least 1, and (t0, t1) must satisfy 0 <= t0 < t1 <= total (got {epochs!r} of {total!r})")
+        if not whole(n_neg) or not 0 <= int(n_neg) <= MAX_NEG:
+            raise ValueError(f"n_neg must be an integer in 0 .. {MAX_NEG} (got {n_neg!r})")
+        if not whole(seed) or not 0 <= int(seed) <= MASK:
+            raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1 (got {seed!r})")
+        if (a is None) != (b is None):
+            raise ValueError("give a and b together (curve_ab), or neither")
+        if a is None:
+            a, b = curve_ab(0.1)
+        a, b, gamma, lr = float(a), float(b), float(gamma), float(lr)
+        if not (np.isfinite(a) and a >= 0 and np.isfinite(b) and b > 0 and np.isfinite(gamma) and np.isfinite(lr)):
+            raise ValueError(f"a >= 0, b > 0, gamma and lr must be finite (got {a!r}, {b!r}, {gamma!r}, {lr!r})")
+        self.indptr, self.indices, self.rate = scheduled(graph)
+        self.n, self.nnz = len(self.indptr) - 1, len(self.indices)
+        self.dim, self.t0, self.t1, self.total, self.n_neg, self.seed = int(dim), t0, t1, int(total), int(n_neg), int(seed)
+        self.a, self.b, self.gamma, self.lr = a, b, gamma, lr
+        if init is None:
+            self.y0 = init_positions(self.n, self.dim, self.seed)
+        else:
+            y0 = np.array(init, dtype=np.float64, order="C")
+            if y0.shape != (self.n, self.dim) or not np.isfinite(y0).all():
+                raise ValueError(f"init must be finite [N, dim] = {(self.n, self.dim)} (got {y0.shape})")
+            self.y0 = y0
+
+    def alpha(self, t):
+        return self.lr * (1.0 - t / self.total)
+
+
+def _terms(run, delta, attraction):
+    """g [M, dim] of the differences delta [M, dim]: the clipped attraction or repulsion terms of the definition."""
+    d2 = delta[:, 0] * delta[:, 0]
+    for c in range(1, run.dim):
+        d2 = d2 + delta[:, c] * delta[:, c]
+    power = d2 if run.b == 1.0 else np.power(d2, run.b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if attraction:
+            coef = np.where(d2 == 0, 0.0, ((-2.0 * run.a) * run.b * power) / (d2 * (1.0 + run.a * power)))
+        else:
+            coef = ((2.0 * run.gamma) * run.b) / ((0.001 + d2) * (1.0 + run.a * power))
+    return np.minimum(4.0, np.maximum(-4.0, coef[:, None] * delta))
+
+
+def layout_host(graph, dim=2, epochs=200, total=None, n_neg=5, gamma=1.0, lr=1.0, a=None, b=None, init=None, seed=0):
+    """The definition -> positions float64 [N, dim] after the epochs.  `graph`: (indptr, indices, weight), as fuzzy_graph_host returns
+    it; `epochs`: T, or (t0, t1) of `total` (default t1) epochs to continue a run from `init`; a, b: default curve_ab(0.1).
+    All terms of an epoch are formed at once; the sums then run over the position of an entry within its row, which is the CSR order
+    of every vertex's own chain."""
+    return host_epochs(Run(graph, dim, epochs, total, n_neg, gamma, lr, a, b, init, seed))
+
+
+def host_epochs(run):
+    """The epochs of a checked Run in numpy -> positions float64 [N, dim]."""
+    y = run.y0.copy()
+    if run.nnz == 0:
+        for t in range(run.t0, run.t1):
+            y = y + run.alpha(t) * np.zeros_like(y)
+        return y
+    row = np.repeat(np.arange(run.n, dtype=np.int64), np.diff(run.indptr))
+    place = np.arange(run.nnz, dtype=np.int64) - run.indptr[row]
+    for t in range(run.t0, run.t1):
+        e = np.flatnonzero(active(run.rate, t))
+        i = row[e]
+        pull = _terms(run, y[i] - y[run.indices[e]], True)
+        if run.n_neg:
+            m = negatives(run.seed, t, run.nnz, e, run.n_neg, run.n)
+            push = _terms(run, np.repeat(y[i], run.n_neg, axis=0) - y[m.ravel()], False).reshape(len(e), run.n_neg, run.dim)
+            hit = m != i[:, None]
+        force = np.zeros_like(y)
+        order = np.argsort(place[e], kind="stable")
+        starts = np.searchsorted(place[e][order], np.arange(place[e].max(initial=-1) + 2))
+        for q in range(len(starts) - 1):                 # the q-th entry of every row that has one: distinct rows
+            sel = order[starts[q]:starts[q + 1]]
+            if not len(sel):
+                continue
+            force[i[sel]] += pull[sel]
+            for s in range(run.n_neg):
+                part = sel[hit[sel, s]]
+                force[i[part]] += push[part, s]
+        y = y + run.alpha(t) * force
+    return y
+
+
+# ---- the device path ---------------------------------------------------------------------------------------------------------------
+def scratch_bytes(n, dim):
+    """wseg_embed_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
+    from . import _lib
+    lib = _lib.load()
+    nbytes = lib.wseg_embed_scratch_bytes(int(n), int(dim))
+    if nbytes == 0:
+        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
+    return nbytes
+
+
+def layout_epochs(run, device="cuda"):
+    """The launches of a checked Run -> the positions as a DEVICE tensor float64 [N, dim].  Stream-ordered, no host synchronisation."""
+    import torch
+    from . import _lib
+    lib = _lib.load(require_device=True)
+    dev = torch.device(device)
+    indptr = torch.from_numpy(run.indptr).to(dev)
+    indices = torch.from_numpy(run.indices).to(dev)
+    rate = torch.from_numpy(run.rate.view(np.int32)).to(dev)
+    y_in = torch.from_numpy(run.y0).to(dev)
+    y_out = torch.empty_like(y_in)
+    if run.n == 0:
+        return y_out
+    scratch = torch.empty(scratch_bytes(run.n, run.dim), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.wseg_embed_epochs_f64(indptr.data_ptr(), indices.data_ptr() if run.nnz else None, rate.data_ptr() if run.nnz else None,
+                                             run.n, run.nnz, run.dim, y_in.data_ptr(), y_out.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                             run.t0, run.t1, run.total, run.lr, run.a, run.b, run.gamma, run.n_neg, run.seed, _lib.stream_ptr()))
+    return y_out
+
+
+def layout(graph, dim=2, epochs=200, total=None, n_neg=5, gamma=1.0, lr=1.0, a=None, b=None, init=None, seed=0, device="cuda"):
+    """layout_host's positions, with the epochs on the GPU -> float64 [N, dim] as numpy.  The arguments are layout_host's; the CSR and
+    the start are uploaded once and only the positions travel back.  epochs=(t0, t1) with init= the positions a run to t0 returned
+    continues that run: (0, s) then (s, T), both with total=T, give the bits of (0, T)."""
+    run = Run(graph, dim, epochs, total, n_neg, gamma, lr, a, b, init, seed)
+    return layout_epochs(run, device).cpu().numpy()
+
+
+def check_embed(k, dim, min_dist, spread, epochs):
+    """The checked arguments of embed / patch_embedding -> (k, a, b)."""
+    k = NB.check_k(k)
+    if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim not in (2, 3):
+        raise ValueError(f"dim must be 2 or 3 (got {dim!r})")
+    if isinstance(epochs, bool) or not isinstance(epochs, (int, np.integer)) or not 1 <= int(epochs) <= 2 ** 31 - 1:
+        raise ValueError(f"epochs must be an integer of at least 1 (got {epochs!r})")
+    return (k,) + curve_ab(min_dist, spread)
+
+
+def embed(rows, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", spread=1.0, n_neg=5, init=None, lists=None):
+    """float32 [N, dim]: the map of the rows (float32 [N, D]: numpy, or a device tensor, searched where it lies) — the k nearest
+    neighbours of every row (neighbors.neighbors), their fuzzy graph (fuzzy_graph_host), and `epochs` epochs of layout with
+    a, b = curve_ab(min_dist, spread).  `lists`: (index, distance) [N, k] where the caller already has them.  No rows: [0, dim];
+    one row: its start, for there is no edge."""
+    k, a, b = check_embed(k, dim, min_dist, spread, epochs)
+    n = int(rows.shape[0]) if hasattr(rows, "shape") and len(rows.shape) == 2 else len(np.asarray(rows))
+    nothing = (np.zeros(n + 1, np.int64), np.zeros(0, np.int32), np.zeros(0))
+    Run(nothing, dim, int(epochs), None, n_neg, 1.0, 1.0, a, b, init, seed)          # every argument is checked before the search runs
+    if lists is not None:
+        index, distance = np.asarray(lists[0]), np.asarray(lists[1])
+        if index.shape != (n, k) or distance.shape != (n, k):
+            raise ValueError(f"lists must be (index, distance) [N, k] = {(n, k)} (got {index.shape} and {distance.shape})")
+    elif n < 2:
+        index, distance = np.full((n, k), -1, np.int32), np.full((n, k), np.inf, np.float32)
+    else:
+        index, distance = NB.neighbors(rows, None, k, device=device)
+    run = Run(fuzzy_graph_host(index, distance), dim, int(epochs), None, n_neg, 1.0, 1.0, a, b, init, seed)
+    if n == 0:
+        return np.zeros((0, dim), np.float32)
+    return layout_epochs(run, device).cpu().numpy().astype(np.float32)
+
+
+def patch_embedding(predictions, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", lists=None):
+    """{"embedding": float32 [rows, dim]} of all the calls of `predictions` — what segment*(..., patches=W) returned, flattened as
+    neighbors.patch_rows_of does: the rows of the CLI's CSV.  `lists`: the (neighbor_index, neighbor_distance) of patch_neighbors with
+    this k, where the caller has them."""
+    check_embed(k, dim, min_dist, 1.0, epochs)
+    rows = NB.patch_rows_of(predictions)
+    if not len(rows):
+        return {"embedding": np.zeros((0, dim), np.float32)}
+    return {"embedding": embed(rows, k, dim, min_dist, epochs, seed, device, lists=lists)}
