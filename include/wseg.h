@@ -345,6 +345,37 @@ int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const u
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-segment fundamental frequency from the resident PCM: a YIN pitch contour of every row (what the spectral columns above do
+ * not give: they name the loudest partial of a harmonic stack, not its fundamental, and nothing inside the call).
+ * whisperseg_amd/pitch.py::frames_host is the definition (numpy, float64, every sum in a stated order); the kernel takes the same
+ * float64 steps in the same order: the output has the definition's bits, on every run, for every workgroup size and grid.
+ * bounds_host: HOST int64 [n_seg][2], the sample range [s0, s1) of every segment, 0 <= s0 <= s1 <= n (overlaps allowed; all time
+ * arithmetic is the caller's).  pcm: device float32 [n].  2 <= tau_min < tau_max <= 2048, hop >= 1, 0 < threshold < 1.
+ * Frame j of a segment starts at s0 + j hop and reads exactly 2 tau_max samples; a segment of len samples has 0 frames for
+ * len < 2 tau_max, else 1 + (len - 2 tau_max) / hop: no padding, nothing at or behind s1 and nothing in front of s0 is ever read.
+ * Per frame: d(tau) = sum_{i < tau_max} (x[i] - x[i + tau])^2 for tau = 1 .. tau_max, one sequential float64 chain per lag;
+ * d'(tau) = (d(tau) tau) / run(tau) (1 where run is 0), run the prefix sum of d in blocks of 64 lags (sequential inside a block,
+ * the bases the sequential sum of the block totals, run = base + inner); the lag is the first c in tau_min .. tau_max - 1 with
+ * d'(c) < threshold walked up while d' falls (voiced), else the lowest minimiser of d' (unvoiced); period = lag + the vertex of the
+ * parabola through d'(lag - 1 .. lag + 1), clamped to +-0.5 (0 where it has no minimum).
+ * out: device float32 [total_frames][3], the frames of segment 0, then of segment 1, ...: (period in samples, d'(lag), voiced 0 / 1)
+ * — RATE-FREE (no sampling rate enters the call).  Silence gives (tau_min, 1, 0).  Non-finite samples give unspecified values.
+ * Nothing outside the total_frames rows is written.
+ * scratch: device, 8-byte aligned, wseg_pitch_scratch_bytes(bounds_host, n_seg, tau_max, hop) bytes — host arithmetic, no device; it
+ * returns 0 with the reason in wseg_last_error() for invalid bounds (it knows no n: s1 up to 2^52), n_seg < 0, tau_max outside
+ * 3 .. 2048, hop < 1 or more than 2^40 frames.
+ * The call copies what the kernel needs of the bounds through a pinned buffer of the library's on the stream and waits for
+ * nothing: bounds_host may be reused on return.  n_seg == 0 or no frame at all returns 0 without a launch.  Every argument is
+ * validated on the host before a launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered.
+ * $WSEG_PITCH_GRID: a TEST knob, the cap on the grid (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_pitch_scratch_bytes(const int64_t* bounds_host, int32_t n_seg, int32_t tau_max, int32_t hop);
+int wseg_pitch_frames_f64(const float* pcm, int64_t n, const int64_t* bounds_host, int32_t n_seg,
+                          int32_t tau_min, int32_t tau_max, int32_t hop, double threshold,
+                          void* scratch, size_t scratch_bytes, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

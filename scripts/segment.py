@@ -33,6 +33,14 @@ the rows of the archive: `embedding` float32 [rows, DIM], DIM 2 or 3 — the UMA
 GPU) of the fuzzy graph of the K (1 .. 64, default 15) nearest neighbours of every picture, with min_dist X (0 <= X < 1, default
 0.1) and the hash seed S (default 0): the same bits for the same rows on every run.  With --neighbors K of the same K the lists
 are computed once.
+--pitch [--pitch_min_hz F] [--pitch_max_hz F] [--pitch_threshold X] appends seven pitch columns behind the measurement columns
+(whisperseg_amd.pitch.COLUMNS: mean, lowest, highest, first and last fundamental frequency of the row's YIN contour in Hz, the voiced
+fraction and the aperiodicity), tracked on the GPU in the samples the rows were cut from; F default to the widest range the
+estimator takes at the recording's rate (2 sr / n_fft .. sr / 8), X (0 < X < 1, default 0.1) is YIN's threshold.
+--pitch_save_path FILE.npz (needs --pitch) saves the contours themselves: `f0` (Hz, NaN where unvoiced), `aperiodicity` and
+`frame_time` (seconds), all float [frames], the frames of row 0, then of row 1, ... in the CSV's row order, `frame_offsets` int64
+[rows + 1] — row r owns the frames frame_offsets[r] .. frame_offsets[r + 1] — and `onset`, `offset`, `cluster`, `filename` / `channel`
+as --patches_save_path has them.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -47,6 +55,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
 from whisperseg_amd.measure import COLUMNS as MEASURE_COLUMNS  # noqa: E402
+from whisperseg_amd.pitch import COLUMNS as PITCH_COLUMNS  # noqa: E402
 from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
 
 
@@ -96,6 +105,12 @@ def build_parser():
     p.add_argument("--embed_neighbors", default=None, type=int, metavar="K", help="--embed: neighbours a row of the graph (1 .. 64, default 15)")
     p.add_argument("--embed_min_dist", default=None, type=float, metavar="X", help="--embed: UMAP's min_dist, 0 <= X < 1 (default 0.1)")
     p.add_argument("--embed_seed", default=None, type=int, metavar="S", help="--embed: the seed of the start and the negative samples (default 0)")
+    p.add_argument("--pitch", action="store_true",
+                   help="append the seven per-segment pitch columns (f0_mean .. aperiodicity) to every row")
+    p.add_argument("--pitch_min_hz", default=None, type=float, metavar="F", help="--pitch: the lowest fundamental looked for (default 2 sr / n_fft)")
+    p.add_argument("--pitch_max_hz", default=None, type=float, metavar="F", help="--pitch: the highest fundamental looked for (default sr / 8)")
+    p.add_argument("--pitch_threshold", default=None, type=float, metavar="X", help="--pitch: YIN's threshold, 0 < X < 1 (default 0.1)")
+    p.add_argument("--pitch_save_path", default=None, metavar="FILE.npz", help="--pitch: where to save the pitch contours (numpy .npz)")
     return p
 
 
@@ -103,7 +118,9 @@ def parse_args(argv=None):
     """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors or --clusters
     without them, a K outside 1 .. 64, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
     errors; so are --embed without the patches, a DIM other than 2 or 3, --embed_neighbors outside 1 .. 64, --embed_min_dist outside
-    [0, 1), a negative --embed_seed and any of the three without --embed."""
+    [0, 1), a negative --embed_seed and any of the three without --embed; and --pitch_min_hz, --pitch_max_hz, --pitch_threshold or
+    --pitch_save_path without --pitch, a frequency that is not positive, a range that is none, a threshold outside (0, 1) and a
+    --pitch_save_path that does not end with .npz."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if (args.patches is None) != (args.patches_save_path is None):
@@ -145,7 +162,30 @@ def parse_args(argv=None):
         args.embed_seed = 0
     elif not 0 <= args.embed_seed < 2 ** 64:
         parser.error("--embed_seed must be 0 .. 2^64 - 1")
+    for name in ("pitch_min_hz", "pitch_max_hz", "pitch_threshold", "pitch_save_path"):
+        if getattr(args, name) is not None and not args.pitch:
+            parser.error(f"--{name} needs --pitch")
+    for name in ("pitch_min_hz", "pitch_max_hz"):
+        if getattr(args, name) is not None and not 0 < getattr(args, name) < float("inf"):
+            parser.error(f"--{name} must be a positive frequency in Hz")
+    if args.pitch_min_hz is not None and args.pitch_max_hz is not None and args.pitch_min_hz > args.pitch_max_hz:
+        parser.error("--pitch_min_hz must not lie above --pitch_max_hz")
+    if args.pitch_threshold is not None and not 0 < args.pitch_threshold < 1:
+        parser.error("--pitch_threshold must lie in (0, 1)")
+    if args.pitch_save_path is not None and not args.pitch_save_path.endswith(".npz"):
+        parser.error("--pitch_save_path must end with .npz")
     return args
+
+
+def pitch_keyword(args):
+    """The `pitch=` of the segmenter calls for the parsed flags (None without --pitch): True, or the dict of what was given."""
+    if not args.pitch:
+        return None
+    given = {key: value for key, value in (("f_min", args.pitch_min_hz), ("f_max", args.pitch_max_hz), ("threshold", args.pitch_threshold))
+             if value is not None}
+    if args.pitch_save_path is not None:
+        given["contour"] = True
+    return given or True
 
 
 def folder_patterns(audio_ext=None):
@@ -163,13 +203,13 @@ def write_csv(columns, rows, dest):
         w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
-def table(results, names=None, all_channels=False, measure=False):
+def table(results, names=None, all_channels=False, measure=False, pitch=False):
     """-> (columns, rows) of the CSV.  `results`: one prediction dict per recording, or with all_channels one LIST of dicts (one
     per channel) per recording, which adds the `channel` column; `names`: the recordings' file names for the `filename` column
-    (folder mode); `measure`: the dicts carry the eight measurement columns, appended behind `cluster`.  Rows run in file, channel,
-    row order."""
+    (folder mode); `measure`: the dicts carry the eight measurement columns, appended behind `cluster`; `pitch`: the seven pitch
+    columns, behind those.  Rows run in file, channel, row order."""
     columns = (["filename"] if names is not None else []) + (["channel"] if all_channels else []) + ["onset", "offset", "cluster"]
-    extra = list(MEASURE_COLUMNS) if measure else []
+    extra = (list(MEASURE_COLUMNS) if measure else []) + (list(PITCH_COLUMNS) if pitch else [])
     columns += extra
     rows = []
     for i, res in enumerate(results):
@@ -184,6 +224,29 @@ def patch_archive(results, names=None, all_channels=False, width=0):
     import numpy as np
     flat = [(i, channel, r) for i, res in enumerate(results) for channel, r in enumerate(res if all_channels else [res])]
     out = {"patch": np.concatenate([r["patch"] for _, _, r in flat] or [np.zeros((0, 80, width), np.float32)], axis=0),
+           "onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
+           "offset": np.array([v for _, _, r in flat for v in r["offset"]], dtype=np.float64),
+           "cluster": np.array([str(v) for _, _, r in flat for v in r["cluster"]], dtype=str)}
+    if names is not None:
+        out["filename"] = np.array([names[i] for i, _, r in flat for _ in r["onset"]], dtype=str)
+    if all_channels:
+        out["channel"] = np.array([channel for _, channel, r in flat for _ in r["onset"]], dtype=np.int64)
+    return out
+
+
+def pitch_archive(results, names=None, all_channels=False):
+    """-> {name: array} of the pitch .npz: the contours of all rows back to back, their offsets and the CSV's identifying columns,
+    in table()'s row order."""
+    import numpy as np
+    flat = [(i, channel, r) for i, res in enumerate(results) for channel, r in enumerate(res if all_channels else [res])]
+
+    def joined(key, dtype):
+        return np.concatenate([np.asarray(a, dtype=dtype) for _, _, r in flat for a in r[key]] or [np.zeros(0, dtype)])
+
+    counts = [len(a) for _, _, r in flat for a in r["f0_contour"]]
+    out = {"f0": joined("f0_contour", np.float32), "aperiodicity": joined("aperiodicity_contour", np.float32),
+           "frame_time": joined("frame_time", np.float64),
+           "frame_offsets": np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64),
            "onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
            "offset": np.array([v for _, _, r in flat for v in r["offset"]], dtype=np.float64),
            "cluster": np.array([str(v) for _, _, r in flat for v in r["cluster"]], dtype=str)}
@@ -216,7 +279,8 @@ def main(argv=None):
         segmenter = WhisperSegmenter(args.model_path, device=args.device, device_ids=args.device_ids)
     kwargs = dict(min_frequency=args.min_frequency, spec_time_step=args.spec_time_step, num_trials=args.num_trials,
                   batch_size=args.batch_size, **({"measure": True} if args.measure else {}),      # (absent: the calls as they were)
-                  **({} if args.patches is None else {"patches": args.patches}))
+                  **({} if args.patches is None else {"patches": args.patches}),
+                  **({} if not args.pitch else {"pitch": pitch_keyword(args)}))
     rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
@@ -240,7 +304,10 @@ def main(argv=None):
             tabled = ([segmenter.segment_channels(audio, sr, **kwargs)], None, True)
         else:
             tabled = ([segmenter.segment(audio, sr, **kwargs)], None, False)
-    columns, rows = table(*tabled, measure=args.measure)
+    columns, rows = table(*tabled, measure=args.measure, pitch=args.pitch)
+    if args.pitch_save_path is not None:
+        import numpy as np
+        np.savez(args.pitch_save_path, **pitch_archive(*tabled))
     if args.patches is not None:
         import numpy as np
         archive = patch_archive(*tabled, width=args.patches)

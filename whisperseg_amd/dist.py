@@ -136,6 +136,9 @@ def _refuse_measure(kwargs, name):
     if kwargs.get("patches") is not None:      # (the same reason)
         raise ValueError(f"{name} does not cut patches (patches=W): take them of the returned rows with "
                          "whisperseg_amd.patches.patches(audio, sr, prediction, width=W) on one device")
+    if kwargs.get("pitch") is not None:        # (the same reason)
+        raise ValueError(f"{name} does not track pitch (pitch=...): take it of the returned rows with "
+                         "whisperseg_amd.pitch.pitch(audio, sr, prediction) on one device")
 
 
 def segment_distributed(segmenter, audio, sr, decode_shard=None, **kwargs):
