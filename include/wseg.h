@@ -363,7 +363,8 @@ int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const u
  * Nothing outside the total_frames rows is written.
  * scratch: device, 8-byte aligned, wseg_pitch_scratch_bytes(bounds_host, n_seg, tau_max, hop) bytes — host arithmetic, no device; it
  * returns 0 with the reason in wseg_last_error() for invalid bounds (it knows no n: s1 up to 2^52), n_seg < 0, tau_max outside
- * 3 .. 2048, hop < 1 or more than 2^40 frames.
+ * 3 .. 2048, hop < 1 or more than 2^40 frames.  (It holds the segment table the three per-segment calls share — int64 (s0, s1) of
+ * every segment, then the exclusive prefix of the frame counts: 3 n_seg + 1 entries, padded to 256 bytes.  Size it by the query.)
  * The call copies what the kernel needs of the bounds through a pinned buffer of the library's on the stream and waits for
  * nothing: bounds_host may be reused on return.  n_seg == 0 or no frame at all returns 0 without a launch.  Every argument is
  * validated on the host before a launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered.

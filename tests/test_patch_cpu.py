@@ -138,7 +138,7 @@ def test_the_cases_hold_what_they_promise():
 
 
 def test_plan_through_the_library():
-    """wseg_patches_scratch_bytes is host arithmetic: (s0, L) int64 pairs padded to 256 bytes, then one uint32 a segment padded to
+    """wseg_patches_scratch_bytes is host arithmetic: (s0, s1) int64 pairs padded to 256 bytes, then one uint32 a segment padded to
     256 bytes; the launch entry point validates on the host, before it touches a device, and names the argument."""
     import ctypes as C
     from whisperseg_amd import _lib

@@ -104,9 +104,9 @@ int main() {
       std::printf("  empty segments: %s\n", msg); ++fails;
     }
     // what must be refused
-    const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge[2] = {0, kMeasureMaxSamples + 1}, fine[2] = {0, 8};
+    const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge[2] = {0, kSegmentMaxSamples + 1}, fine[2] = {0, 8};
     std::vector<int64_t> many;
-    for (int i = 0; i < 8; ++i) { many.push_back(0); many.push_back(kMeasureMaxSamples); }
+    for (int i = 0; i < 8; ++i) { many.push_back(0); many.push_back(kSegmentMaxSamples); }
     if (!rejected(measure_plan(reversed, 1, n_fft, -1, kMeasureGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||
         !rejected(measure_plan(negative, 1, n_fft, -1, kMeasureGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||
         !rejected(measure_plan(huge, 1, n_fft, -1, kMeasureGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||

@@ -10,8 +10,8 @@
 // n_seg * width frames with less than one item to spare; both grids are 1 .. cap and never more than their work (0 without a
 // segment); the maxima follow the table on their alignment and the scratch holds exactly both; the offsets of the last table entry,
 // the last value of out and the last frame's last sample stay inside int64; every column centre lies in [s0, s1) (at s0 for an
-// empty segment) and never moves backwards from one column to the next, up to s1 = 2^52 at width 256; the table the plan writes is
-// (s0, L).  Invalid sizes, counts, widths and bounds must be rejected with the argument's name.  Prints one line per n_fft.
+// empty segment) and never moves backwards from one column to the next, up to s1 = 2^52 at width 256; the table written for the
+// device is (s0, s1).  Invalid sizes, counts, widths and bounds must be rejected with the argument's name.  Prints one line per n_fft.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -42,7 +42,7 @@ struct Synthetic {
 
 int main() {
   int bad = 0;
-  const int64_t top = kPatchMaxSamples;
+  const int64_t top = kSegmentMaxSamples;
   for (const int32_t n_fft : {512, 1024, 2048, 4096, 8192}) {
     int fails = 0;
     int64_t plans = 0;
@@ -92,31 +92,33 @@ int main() {
         }
       }
     }
-    // the whole call: a table of (s0, L) for a small call, then 2^31 - 1 synthetic segments up to 2^52 without a table
+    // the whole call: the device's table of (s0, s1) for a small call, then 2^31 - 1 synthetic segments up to 2^52 without a table
     {
       const Synthetic small{top, 1001};
-      std::vector<int64_t> table(2 * 1001);
+      std::vector<int64_t> table(2 * 1001), array(2 * 1001);
+      for (int32_t i = 0; i < 1001; ++i) small(i, &array[2 * i], &array[2 * i + 1]);
       PatchPlan p;
-      if (patch_plan(small, 1001, 80, 256, n_fft, top, kPatchGridCap, &p, table.data(), msg, sizeof(msg))) { std::printf("  rejected: %s\n", msg); ++fails; }
+      if (patch_plan(small, 1001, 80, 256, n_fft, top, kPatchGridCap, &p, msg, sizeof(msg))) { std::printf("  rejected: %s\n", msg); ++fails; }
+      segment_table_fill(table.data(), array.data(), 1001, nullptr);
       for (int32_t i = 0; i < 1001; ++i) {
         int64_t s0, s1;
         small(i, &s0, &s1);
-        if (table[2 * i] != s0 || table[2 * i + 1] != s1 - s0 || s0 < 0 || s1 < s0 || s1 > top) { std::printf("  the table of segment %d\n", (int)i); ++fails; break; }
+        if (table[2 * i] != s0 || table[2 * i + 1] != s1 || s0 < 0 || s1 < s0 || s1 > top) { std::printf("  the table of segment %d\n", (int)i); ++fails; break; }
       }
       if (n_fft == 512 || n_fft == 8192) {         // (two billion segments take a few seconds: the walk does not depend on n_fft)
         const Synthetic huge{top, INT32_MAX};
-        if (patch_plan(huge, INT32_MAX, 96, 256, n_fft, -1, kPatchGridCap, &p, nullptr, msg, sizeof(msg)) || p.total_frames != (int64_t)INT32_MAX * 256 ||
+        if (patch_plan(huge, INT32_MAX, 96, 256, n_fft, -1, kPatchGridCap, &p, msg, sizeof(msg)) || p.total_frames != (int64_t)INT32_MAX * 256 ||
             p.total_values != (int64_t)INT32_MAX * 256 * 96 || p.grid != kPatchGridCap) { std::printf("  2^31 - 1 segments: %s\n", msg); ++fails; }
-        if (!rejected(patch_plan(huge, INT32_MAX, 96, 256, n_fft, top - 1, kPatchGridCap, &p, nullptr, msg, sizeof(msg)), "bounds")) {
+        if (!rejected(patch_plan(huge, INT32_MAX, 96, 256, n_fft, top - 1, kPatchGridCap, &p, msg, sizeof(msg)), "bounds")) {
           std::printf("  2^31 - 1 segments: a segment behind the recording's end is accepted\n"); ++fails;
         }
       }
     }
     // what must be refused
-    const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge_one[2] = {0, kPatchMaxSamples + 1}, fine[2] = {0, 8};
+    const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge_one[2] = {0, kSegmentMaxSamples + 1}, fine[2] = {0, 8};
     PatchPlan p;
     auto plan = [&](const int64_t* b, int32_t n_seg, int32_t n_mels, int32_t width, int32_t nf, int64_t n) {
-      return patch_plan(PatchBoundsArray{b}, n_seg, n_mels, width, nf, n, kPatchGridCap, &p, nullptr, msg, sizeof(msg));
+      return patch_plan(SegmentBoundsArray{b}, n_seg, n_mels, width, nf, n, kPatchGridCap, &p, msg, sizeof(msg));
     };
     if (plan(fine, 1, 80, 32, n_fft, 8) || plan(fine, 1, 80, 32, n_fft, -1) || plan(nullptr, 0, 80, 32, n_fft, 0) ||
         !rejected(plan(reversed, 1, 80, 32, n_fft, -1), "bounds") || !rejected(plan(negative, 1, 80, 32, n_fft, -1), "bounds") ||

@@ -9,7 +9,7 @@
 // For every (tau_max, hop) it asks for the plan of segments whose lengths sit around every step of the frame count (no frame, one,
 // the second, 2^31 samples, 2^40 samples), alone and all together at odd starts, and fails unless: the frame count agrees with a
 // count made another way (the frames' starts, bisected); the last frame lies wholly inside the segment and no further frame would
-// — what pitch_frame_kernel's loads assume; the prefix is the running sum; the table is (2 n_seg + 1) int64 and the scratch its
+// — what pitch_frame_kernel's loads assume; the prefix is the running sum; the table is (3 n_seg + 1) int64 and the scratch its
 // padded size; the workgroup is 64, 128 or 256 lanes, a power of two, with a lane per lag group wherever 256 lanes suffice; the
 // blocks of the prefix sum number at most 32; the grid is 1 .. cap and never more than the frames; the byte offset of the last
 // output float stays inside int64.  The layout is checked for 2^31 - 1 segments and 2^40 frames without walking that many
@@ -85,7 +85,7 @@ int main() {
         if (pitch_plan(bounds.data(), n_seg, tau_max, hop, -1, cap, &p, prefix.data(), msg, sizeof(msg))) { std::printf("  rejected: %s\n", msg); ++fails; continue; }
         const int64_t top = cap < 1 ? 1 : cap > kPitchGridCap ? kPitchGridCap : cap;
         bool ok = p.tau_max == tau_max && p.hop == hop && p.n_seg == n_seg && p.total_frames == expected &&
-                  p.table_bytes == (2 * (int64_t)n_seg + 1) * 8 && p.scratch_bytes >= p.table_bytes && p.scratch_bytes % kPitchAlign == 0 &&
+                  p.table_bytes == (3 * (int64_t)n_seg + 1) * 8 && p.scratch_bytes >= p.table_bytes && p.scratch_bytes % kPitchAlign == 0 &&
                   p.scratch_bytes - p.table_bytes < kPitchAlign && p.out_floats == 3 * expected && p.grid >= 1 && p.grid <= top &&
                   p.grid <= p.total_frames && (p.grid == top || p.grid == p.total_frames);
         ok = ok && p.groups == (tau_max + 3) / 4 && p.groups * kPitchLagsPerLane >= tau_max && (p.groups - 1) * kPitchLagsPerLane < tau_max;
@@ -111,13 +111,13 @@ int main() {
           prefix[2] != 0) { std::printf("  empty segments: %s\n", msg); ++fails; }
       // the layout at the largest counts, without walking the bounds
       pitch_layout(INT32_MAX, kPitchMaxFrames, tau_max, hop, kPitchGridCap, &p);
-      if (p.table_bytes != (2 * (int64_t)INT32_MAX + 1) * 8 || p.scratch_bytes < p.table_bytes || p.scratch_bytes % kPitchAlign ||
+      if (p.table_bytes != (3 * (int64_t)INT32_MAX + 1) * 8 || p.scratch_bytes < p.table_bytes || p.scratch_bytes % kPitchAlign ||
           p.out_floats != 3 * kPitchMaxFrames || p.out_floats > INT64_MAX / 4 || p.grid != kPitchGridCap) {
         std::printf("  a broken layout at 2^31 - 1 segments\n"); ++fails;
       }
       // what must be refused
-      const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge[2] = {0, kPitchMaxSamples + 1}, fine[2] = {0, width};
-      const int64_t full[2] = {0, kPitchMaxSamples};
+      const int64_t reversed[2] = {9, 8}, negative[2] = {-1, 8}, huge[2] = {0, kSegmentMaxSamples + 1}, fine[2] = {0, width};
+      const int64_t full[2] = {0, kSegmentMaxSamples};
       if (!rejected(pitch_plan(reversed, 1, tau_max, hop, -1, kPitchGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||
           !rejected(pitch_plan(negative, 1, tau_max, hop, -1, kPitchGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||
           !rejected(pitch_plan(huge, 1, tau_max, hop, -1, kPitchGridCap, &p, nullptr, msg, sizeof(msg)), "bounds") ||

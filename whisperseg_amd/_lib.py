@@ -171,6 +171,13 @@ def check(status, lib=None):
     return status
 
 
+def size_or_raise(nbytes):
+    """The result of a wseg_*_scratch_bytes query: those return 0, with the reason in wseg_last_error(), for invalid input."""
+    if nbytes == 0:
+        raise WsegError("libwseg call failed: " + _lib.wseg_last_error().decode())
+    return nbytes
+
+
 def stream_ptr():
     """Current torch HIP stream as a raw hipStream_t."""
     import torch

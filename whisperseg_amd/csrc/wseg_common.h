@@ -9,7 +9,7 @@
 
 // The library reads no tuning environment variable.  What it does read are the TEST knobs that select an alternative path
 // computing the same bits (WSEG_F32_GEMM, WSEG_F32_ATTN, WSEG_CROSS_NO_PK, WSEG_NO_GRAPH, WSEG_NO_PROMPT_PASS,
-// WSEG_NO_FIRST_STEP_MERGE: tests compare both sides).
+// WSEG_NO_FIRST_STEP_MERGE, and the grid caps of grid_cap_env below: tests compare both sides).
 
 namespace wseg {
 
@@ -470,5 +470,15 @@ __device__ __forceinline__ float wave_max(float v) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The grid cap of a grid-striding kernel: default_cap, or the value of the environment variable `name` clamped to 1 .. max_cap —
+// a TEST knob ($WSEG_MEASURE_GRID, _PATCH_, _PITCH_, _KNN_, _MST_; read per call), the same bits for every value: each kernel's
+// device test compares.
+static inline int grid_cap_env(const char* name, int default_cap, int max_cap) {
+  const char* e = getenv(name);
+  if (!e || !*e) return default_cap;
+  const long v = strtol(e, nullptr, 10);
+  return v < 1 ? 1 : v > max_cap ? max_cap : (int)v;
+}
 
 }  // namespace wseg

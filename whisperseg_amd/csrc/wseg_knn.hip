@@ -286,14 +286,6 @@ __global__ __launch_bounds__(256) void knn_fill_kernel(int* __restrict__ index_o
   }
 }
 
-static int knn_grid_cap() {
-  // TEST knob (the same bits for every value: tests/test_knn_gpu.py compares): the cap of the grids, and with it the candidate splits
-  const char* e = getenv("WSEG_KNN_GRID");
-  if (!e || !*e) return kKnnGridCap;
-  const long v = strtol(e, nullptr, 10);
-  return v < 1 ? 1 : v > kKnnGridCap ? kKnnGridCap : (int)v;
-}
-
 }  // namespace wseg
 
 using namespace wseg;
@@ -314,7 +306,8 @@ extern "C" int wseg_knn_f32(const float* queries, int64_t m, const float* corpus
   hipStream_t stream = (hipStream_t)stream_;
   KnnPlan plan;
   char msg[200];
-  if (knn_plan(m, n, d, k, knn_grid_cap(), &plan, msg, sizeof(msg))) {
+  // (the grid cap — and with it the candidate splits — is a test knob)
+  if (knn_plan(m, n, d, k, grid_cap_env("WSEG_KNN_GRID", kKnnGridCap, kKnnGridCap), &plan, msg, sizeof(msg))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }

@@ -7,12 +7,9 @@
 // frame, tied to its mel stage) is left alone — the transform here is the workgroup's.
 //
 // measure_chunk_kernel    a work item is a (segment, chunk) pair, a chunk 64 consecutive frames of the segment (the last chunk the
-//   rest; wseg_measure_plan.h); the host's prefix table of chunks per segment maps an item to its segment by bisection, the grid
-//   is capped and strides over the items.  A workgroup of 256 lanes transforms one frame at a time in LDS: the n_fft windowed
-//   real samples are laid down as n_fft / 2 complex points z[m] = x[2m] + i x[2m + 1] (a flat copy), a radix-2
-//   decimation-in-frequency pass per power of two leaves Z in bit-reversed order, and the unpack step
-//       X[k] = E + W_n^k O,   E = (Z[k] + conj Z[M - k]) / 2,   O = (Z[k] - conj Z[M - k]) / 2i,   M = n_fft / 2
-//   reads Z[k] and Z[M - k] through the bit reversal — no reordering pass.  One code path for 512 .. 8192: 32 KiB of LDS at the
+//   rest; wseg_measure_plan.h); the segment table's prefix of chunks per segment maps an item to its segment (wseg_segments.h),
+//   the grid is capped and strides over the items.  A workgroup of 256 lanes transforms one frame at a time in LDS with the
+//   real FFT of wseg_rfft.h (decimation in frequency, unpacked through the bit reversal): one code path for 512 .. 8192, 32 KiB of LDS at the
 //   largest size, the twiddles (the log-mel descriptor's table, W_n^k for k < n_fft / 2) and the window read from global memory,
 //   where every frame of every workgroup finds them in cache.  Lane t owns bins t, t + 256, ...: at most 17 at 8192, kept as fp64
 //   registers over the chunk's frames and written once.  A sample is loaded with one guard, index < s1 (indices start at s0), by
@@ -62,11 +59,7 @@ __global__ __launch_bounds__(kMeasureLanes) void measure_chunk_kernel(const floa
   const long long chunk_doubles = M + 1 + kMeasureTimeSlots;
   float* const zf = reinterpret_cast<float*>(z);
   for (long long item = blockIdx.x; item < total_chunks; item += gridDim.x) {
-    int lo = 0, hi = n_seg;                          // prefix[lo] <= item < prefix[hi]: the segment is the last one that starts at or before the item
-    while (hi - lo > 1) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (prefix[mid] <= item) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of_item(prefix, n_seg, item);
     const long long s0 = table[2 * lo], len = table[2 * lo + 1] - s0;
     const long long c = item - prefix[lo], n_chunks = prefix[lo + 1] - prefix[lo];
     const long long n_frames = len <= n_fft ? 1 : 1 + (len - n_fft + hop - 1) / hop;
@@ -83,17 +76,8 @@ __global__ __launch_bounds__(kMeasureLanes) void measure_chunk_kernel(const floa
         zf[i] = p < len ? x[p] * window[i] : 0.0f;
       }
       __syncthreads();
-      // decimation in frequency: half-size h = 2^sh from M / 2 down to 1; butterfly b pairs z[i0], z[i0 + h] with W_{2h}^j = W_n^{j n / 2h}
-      for (int sh = log2_half - 1; sh >= 0; --sh) {
-        const int h = 1 << sh, tstep = n_fft >> (sh + 1);
-        for (int b = tid; b < (M >> 1); b += kMeasureLanes) {
-          const int j = b & (h - 1);
-          const int i0 = ((b >> sh) << (sh + 1)) + j, i1 = i0 + h;
-          const float2 a = z[i0], q = z[i1], w = twiddle[j * tstep];
-          const float dr = a.x - q.x, di = a.y - q.y;
-          z[i0] = make_float2(a.x + q.x, a.y + q.y);
-          z[i1] = make_float2(dr * w.x - di * w.y, dr * w.y + di * w.x);
-        }
+      for (int sh = log2_half - 1; sh >= 0; --sh) {   // decimation in frequency: half-size 2^sh from M / 2 down to 1
+        for (int b = tid; b < (M >> 1); b += kMeasureLanes) rfft_dif_butterfly(z, twiddle, n_fft, sh, b);
         __syncthreads();
       }
 #pragma unroll
@@ -101,18 +85,7 @@ __global__ __launch_bounds__(kMeasureLanes) void measure_chunk_kernel(const floa
         const int k = tid + kMeasureLanes * r;
         if (k <= M) {
           float re, im;
-          if (k == 0 || k == M) {                    // E[0] +- O[0], both real
-            const float2 a = z[0];
-            re = k == 0 ? a.x + a.y : a.x - a.y;
-            im = 0.0f;
-          } else {
-            const float2 a = z[__brev((unsigned)k) >> (32 - log2_half)], q = z[__brev((unsigned)(M - k)) >> (32 - log2_half)];
-            const float er = 0.5f * (a.x + q.x), ei = 0.5f * (a.y - q.y);
-            const float orr = 0.5f * (a.y + q.y), oi = -0.5f * (a.x - q.x);
-            const float2 w = twiddle[k];
-            re = er + (orr * w.x - oi * w.y);
-            im = ei + (orr * w.y + oi * w.x);
-          }
+          rfft_unpack_bin(z, twiddle, M, log2_half, k, re, im);
           P[r] += (double)re * (double)re + (double)im * (double)im;
         }
       }
@@ -242,15 +215,6 @@ __global__ __launch_bounds__(kMeasureLanes) void measure_finish_kernel(const lon
   }
 }
 
-// ---- the table's way to the device: bounds + chunk prefix through the library's pinned staging pool (wseg_staging.h) ----------------
-static int measure_grid_cap() {
-  // TEST knob (the same bits for every value: tests/test_measure_gpu.py compares): the cap of measure_chunk_kernel's grid
-  const char* e = getenv("WSEG_MEASURE_GRID");
-  if (!e || !*e) return kMeasureGridCap;
-  const long v = strtol(e, nullptr, 10);
-  return v < 1 ? 1 : v > 65535 ? 65535 : (int)v;
-}
-
 }  // namespace wseg
 
 using namespace wseg;
@@ -274,36 +238,22 @@ extern "C" int wseg_measure_segments_f32(const float* pcm, int64_t n, const int6
   MeasurePlan plan;
   char msg[200];
   std::vector<int64_t> prefix((size_t)(n_seg > 0 ? n_seg : 0) + 1);
-  if (measure_plan(bounds_host, n_seg, n_fft, n, measure_grid_cap(), &plan, prefix.data(), msg, sizeof(msg)) ||
+  if (measure_plan(bounds_host, n_seg, n_fft, n, grid_cap_env("WSEG_MEASURE_GRID", kMeasureGridCap, 65535), &plan, prefix.data(), msg, sizeof(msg)) ||
       measure_band_check(n_fft, k_lo, k_hi, msg, sizeof(msg))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }
   if (n_seg == 0) return WSEG_OK;
-  if ((n > 0 && !pcm) || ((uintptr_t)pcm & 3)) { set_error("%s: pcm must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
+  if (const int rc = device_buffers_check(fn, pcm, n, out, scratch, scratch_bytes, plan.scratch_bytes)) return rc;
   if (!window || !twiddle || ((uintptr_t)twiddle & 7)) { set_error("%s: window and twiddle (8-byte aligned) must be device pointers", fn); return WSEG_ERR_INVALID; }
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)plan.scratch_bytes) {
-    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)plan.scratch_bytes, scratch_bytes);
-    return WSEG_ERR_INVALID;
-  }
-  int slot = -1;
-  const int rc = staging_take((size_t)plan.table_bytes, &slot);
-  if (rc != WSEG_OK) return rc;
-  int64_t* host = static_cast<int64_t*>(staging_host(slot));
-  memcpy(host, bounds_host, (size_t)n_seg * 16);
-  memcpy(host + 2 * (size_t)n_seg, prefix.data(), ((size_t)n_seg + 1) * 8);
-  hipError_t e = hipMemcpyAsync(scratch, host, (size_t)plan.table_bytes, hipMemcpyHostToDevice, stream);
-  const hipError_t e2 = staging_release(slot, stream, e == hipSuccess);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { set_error("%s: the table's copy failed: %s", fn, hipGetErrorString(e)); return WSEG_ERR_HIP; }
+  if (const int rc = staging_upload((size_t)plan.table_bytes, scratch, stream, fn,
+                                    [&](void* host) { segment_table_fill(host, bounds_host, n_seg, prefix.data()); }))
+    return rc;
   const long long* table = static_cast<const long long*>(scratch);
   double* partial = reinterpret_cast<double*>(static_cast<char*>(scratch) + plan.partial_offset);
-  int log2_half = 0;
-  while ((2 << log2_half) < n_fft) ++log2_half;      // n_fft / 2 = 2^log2_half
   if (plan.grid > 0) {
     hipLaunchKernelGGL(measure_chunk_kernel, dim3((unsigned)plan.grid), dim3(kMeasureLanes), 0, stream, pcm, table, (int)n_seg,
-                       (long long)plan.total_chunks, (int)n_fft, log2_half, window, reinterpret_cast<const float2*>(twiddle), partial);
+                       (long long)plan.total_chunks, (int)n_fft, rfft_log2_half(n_fft), window, reinterpret_cast<const float2*>(twiddle), partial);
     WSEG_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(measure_finish_kernel, dim3((unsigned)n_seg), dim3(kMeasureLanes), 0, stream, table, (int)n_seg, (int)n_fft, (int)k_lo,

@@ -6,7 +6,7 @@
 //   J = 0 for len == 0, 1 for 0 < len <= n_fft, else 1 + ceil((len - n_fft) / hop)        (whisperseg_amd/measure.py::frame_count)
 // and its frames into CHUNKS of kMeasureChunkFrames = 64 (the last chunk holds the rest): ceil(J / 64) work items of
 // measure_chunk_kernel.  Scratch, in this order:
-//   int64  table[3 n_seg + 1]     s0, s1 of every segment, then the exclusive prefix of the chunk counts (n_seg + 1 entries)
+//   int64  table[3 n_seg + 1]     the segment table with the exclusive prefix of the chunk counts (wseg_segments.h)
 //   (padded to kMeasureAlign bytes)
 //   double partial[total_chunks][n_fft / 2 + 1 + kMeasureTimeSlots]
 //                                 a chunk's spectrum P[0 .. n_fft / 2] summed over its frames, then the partials of the samples it
@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "wseg_rfft.h"
+#include "wseg_segments.h"
 
 namespace wseg {
 
@@ -22,7 +24,6 @@ constexpr int kMeasureChunkFrames = 64;        // frames of a segment one work i
 constexpr int kMeasureTimeSlots = 3;           // sum x^2 | max |x| | crossings, behind a chunk's spectrum
 constexpr int kMeasureAlign = 256;             // bytes the partials start on behind the table
 constexpr int kMeasureGridCap = 2048;          // workgroups of measure_chunk_kernel: 8 per CU; more items take the grid stride
-constexpr int64_t kMeasureMaxSamples = (int64_t)1 << 52;      // of a recording (2^40 frames at the largest hop are 2^51): every product below stays inside int64
 constexpr int64_t kMeasureMaxChunks = (int64_t)1 << 40;       // of one call, all segments together (2^40 * 33 KiB < 2^56 bytes)
 
 struct MeasurePlan {
@@ -36,8 +37,6 @@ struct MeasurePlan {
   int32_t grid;                    // workgroups of measure_chunk_kernel (0: no chunk at all)
 };
 
-inline bool measure_n_fft_ok(int32_t n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096 || n_fft == 8192; }
-
 // Frames of a segment of len samples (len >= 0).
 inline int64_t measure_frames(int64_t len, int32_t n_fft) {
   const int64_t hop = n_fft / 4;
@@ -49,44 +48,26 @@ inline int64_t measure_chunks(int64_t len, int32_t n_fft) {
   return (measure_frames(len, n_fft) + kMeasureChunkFrames - 1) / kMeasureChunkFrames;
 }
 
-// Validates bounds[n_seg][2] (0 <= s0 <= s1 <= n; n < 0: no recording length is known, s1 <= kMeasureMaxSamples) and n_fft, fills
-// the plan and, where `prefix` is given (n_seg + 1 entries), the exclusive prefix of the chunk counts -> 0, or -1 with the
-// offending argument's name in msg.  n_seg == 0 is valid: no chunk, grid 0, scratch_bytes = the padded one-entry table.
+// Validates n_fft and bounds[n_seg][2] against n (wseg_segments.h::segment_prefix), fills the plan and, where `prefix` is given
+// (n_seg + 1 entries), the exclusive prefix of the chunk counts -> 0, or -1 with the offending argument's name in msg.
+// n_seg == 0 is valid: no chunk, grid 0, scratch_bytes = the padded one-entry table.
 inline int measure_plan(const int64_t* bounds, int32_t n_seg, int32_t n_fft, int64_t n, int64_t grid_cap, MeasurePlan* plan,
                         int64_t* prefix, char* msg, size_t msg_len) {
-  if (!measure_n_fft_ok(n_fft)) { snprintf(msg, msg_len, "n_fft must be 512, 1024, 2048, 4096 or 8192 (got %d)", (int)n_fft); return -1; }
-  if (n_seg < 0) { snprintf(msg, msg_len, "n_seg is negative (%d)", (int)n_seg); return -1; }
-  if (n_seg > 0 && !bounds) { snprintf(msg, msg_len, "bounds is null for n_seg = %d", (int)n_seg); return -1; }
-  if (n > kMeasureMaxSamples) { snprintf(msg, msg_len, "n must be at most 2^52 samples (got %lld)", (long long)n); return -1; }
-  const int64_t limit = n < 0 ? kMeasureMaxSamples : n;
   MeasurePlan p;
+  if (rfft_size_check(n_fft, msg, msg_len) ||      // (a segment holds at most 2^52 / (64 * 128) = 2^39 chunks)
+      segment_prefix(SegmentBoundsArray{bounds}, n_seg, n, [n_fft](int64_t len) { return measure_chunks(len, n_fft); }, kMeasureMaxChunks,
+                     "chunks", prefix, &p.total_chunks, msg, msg_len))
+    return -1;
   p.n_fft = n_fft;
   p.hop = n_fft / 4;
   p.n_bins = n_fft / 2 + 1;
   p.n_seg = n_seg;
-  int64_t total = 0;
-  for (int32_t i = 0; i < n_seg; ++i) {
-    const int64_t s0 = bounds[2 * (int64_t)i], s1 = bounds[2 * (int64_t)i + 1];
-    if (s0 < 0 || s1 < s0 || s1 > limit) {
-      snprintf(msg, msg_len, "bounds of segment %d must satisfy 0 <= s0 <= s1 <= %lld (got %lld, %lld)", (int)i, (long long)limit,
-               (long long)s0, (long long)s1);
-      return -1;
-    }
-    if (prefix) prefix[i] = total;
-    total += measure_chunks(s1 - s0, n_fft);      // at most 2^52 / (64 * 128) = 2^39 a segment; checked before it can pass 2^41
-    if (total > kMeasureMaxChunks) {
-      snprintf(msg, msg_len, "bounds hold more than 2^40 chunks of %d frames up to segment %d", kMeasureChunkFrames, (int)i);
-      return -1;
-    }
-  }
-  if (prefix) prefix[n_seg] = total;
-  p.total_chunks = total;
-  p.table_bytes = (3 * (int64_t)n_seg + 1) * 8;
+  p.table_bytes = segment_table_entries(n_seg, true) * 8;
   p.partial_offset = (p.table_bytes + kMeasureAlign - 1) / kMeasureAlign * kMeasureAlign;
   p.chunk_doubles = p.n_bins + kMeasureTimeSlots;
-  p.scratch_bytes = p.partial_offset + total * p.chunk_doubles * 8;
+  p.scratch_bytes = p.partial_offset + p.total_chunks * p.chunk_doubles * 8;
   if (grid_cap < 1) grid_cap = 1;
-  p.grid = (int32_t)(total < grid_cap ? total : grid_cap);
+  p.grid = (int32_t)(p.total_chunks < grid_cap ? p.total_chunks : grid_cap);
   *plan = p;
   return 0;
 }

@@ -289,14 +289,6 @@ __global__ __launch_bounds__(64) void mst_finish_kernel(MstArgs a, int vec) {
   }
 }
 
-static int mst_grid_cap() {
-  // TEST knob (the same bits for every value: tests/test_mst_gpu.py compares): the cap of the grids, and with it the candidate splits
-  const char* e = getenv("WSEG_MST_GRID");
-  if (!e || !*e) return kMstGridCap;
-  const long v = strtol(e, nullptr, 10);
-  return v < 1 ? 1 : v > kMstGridCap ? kMstGridCap : (int)v;
-}
-
 }  // namespace wseg
 
 using namespace wseg;
@@ -317,7 +309,8 @@ extern "C" int wseg_mst_round_f32(const float* rows, int64_t n, int32_t d, const
   hipStream_t stream = (hipStream_t)stream_;
   MstPlan plan;
   char msg[200];
-  if (mst_plan(n, d, mst_grid_cap(), &plan, msg, sizeof(msg))) {
+  // (the grid cap — and with it the candidate splits — is a test knob)
+  if (mst_plan(n, d, grid_cap_env("WSEG_MST_GRID", kMstGridCap, kMstGridCap), &plan, msg, sizeof(msg))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }

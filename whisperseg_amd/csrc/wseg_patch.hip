@@ -12,8 +12,8 @@
 //   long segment at width 256 spreads over the grid.  The grid is capped and strides over the items.  Per item: F lanes work out
 //   their frame's segment, column and centre (int64, the only divisions); the frames are laid down windowed as n_fft / 2 complex
 //   points z[m] = x[2m] + i x[2m + 1] with every index outside [0, n) read as zero — one guard, no sample outside the recording
-//   is loaded; a radix-2 decimation-in-frequency pass per power of two (2048 butterflies a pass, 8 a lane) leaves Z bit-reversed
-//   and the unpack step reads Z[k], Z[M - k] through the bit reversal (measure_chunk_kernel's transform, F frames side by side);
+//   is loaded; the real FFT of wseg_rfft.h, F frames side by side: a decimation-in-frequency pass per power of two (2048
+//   butterflies a pass, 8 a lane) leaves Z bit-reversed and the unpack step reads Z[k], Z[M - k] through the bit reversal;
 //   |X[k]|^2 goes to a second LDS array (F rows of n_fft / 2 + 1 floats: an odd stride, so lanes on consecutive frames of one
 //   filter hit distinct banks); lane (filter m, frame) then walks the filter's contiguous bins with one fmaf chain, writes log10
 //   into out[segment][m][c] and keeps the frame's maximum, which the workgroup folds to ONE atomic per frame.
@@ -41,7 +41,7 @@ struct PatchArgs {
   wseg_logmel_desc d;              // hop and n_cols are not read
   const float* pcm;
   long long n;
-  const long long* table;          // [n_seg][2]: s0, L
+  const long long* table;          // [n_seg][2]: s0, s1 (wseg_segments.h)
   int width;
   int log2_half;                   // n_fft / 2 = 2^log2_half
   int log2_fpi;                    // frames per item = 2^log2_fpi
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kPatchLanes) void patch_frames_kernel(PatchArgs a) 
       if (g < a.total_frames) {
         const long long seg = g / W;
         const long long c = g - seg * W;
-        const long long s0 = a.table[2 * seg], L = a.table[2 * seg + 1];
+        const long long s0 = a.table[2 * seg], L = a.table[2 * seg + 1] - s0;
         f_base[tid] = s0 + ((2 * c + 1) * L) / (2 * (long long)W) - M;
         f_out[tid] = seg * n_mels * W + c;
         f_seg[tid] = (int)seg;
@@ -86,38 +86,25 @@ __global__ __launch_bounds__(kPatchLanes) void patch_frames_kernel(PatchArgs a) 
       zf[idx] = (p >= 0 && p < a.n) ? a.pcm[p] * window[i] : 0.0f;
     }
     __syncthreads();
-    // decimation in frequency: half-size h = 2^sh from M / 2 down to 1; butterfly bb of a frame pairs z[i0], z[i0 + h] with W_{2h}^j = W_n^{j n / 2h}
-    for (int sh = lg - 1; sh >= 0; --sh) {
-      const int h = 1 << sh, tstep = n_fft >> (sh + 1);
+    for (int sh = lg - 1; sh >= 0; --sh) {           // decimation in frequency: half-size 2^sh from M / 2 down to 1; butterfly bb of frame fr
       for (int b = tid; b < kPatchFrameSlots / 2; b += kPatchLanes) {
         const int fr = b >> (lg - 1), bb = b & ((M >> 1) - 1);
-        const int j = bb & (h - 1);
-        const int i0 = (fr << lg) + ((bb >> sh) << (sh + 1)) + j, i1 = i0 + h;
-        const float2 p = z[i0], q = z[i1], w = twiddle[j * tstep];
-        const float dr = p.x - q.x, di = p.y - q.y;
-        z[i0] = make_float2(p.x + q.x, p.y + q.y);
-        z[i1] = make_float2(dr * w.x - di * w.y, dr * w.y + di * w.x);
+        rfft_dif_butterfly(z + (fr << lg), twiddle, n_fft, sh, bb);
       }
       __syncthreads();
     }
-    // X[k] = E + W_n^k O,  E = (Z[k] + conj Z[M - k]) / 2,  O = (Z[k] - conj Z[M - k]) / 2i;  the lane of k = 0 also writes k = M
+    // |X[k]|^2;  the lane of k = 0 also writes k = M
     for (int idx = tid; idx < kPatchFrameSlots; idx += kPatchLanes) {
       const int fr = idx >> lg, k = idx & (M - 1);
       const float2* __restrict__ zz = z + (fr << lg);
       float* __restrict__ pp = pw + fr * (M + 1);
-      if (k == 0) {                                  // E[0] +- O[0], both real
-        const float2 p = zz[0];
-        const float lo = p.x + p.y, hi = p.x - p.y;
-        pp[0] = lo * lo;
-        pp[M] = hi * hi;
-      } else {
-        const float2 p = zz[__brev((unsigned)k) >> (32 - lg)], q = zz[__brev((unsigned)(M - k)) >> (32 - lg)];
-        const float er = 0.5f * (p.x + q.x), ei = 0.5f * (p.y - q.y);
-        const float orr = 0.5f * (p.y + q.y), oi = -0.5f * (p.x - q.x);
-        const float2 w = twiddle[k];
-        const float re = er + (orr * w.x - oi * w.y);
-        const float im = ei + (orr * w.y + oi * w.x);
-        pp[k] = re * re + im * im;
+      float re, im;                                  // (bins 0 and M: im = 0, and adding + 0 to a square changes no bit)
+      __builtin_assume(k != M);                      // (k < M: the unpack's test for bin M is dead here)
+      rfft_unpack_bin(zz, twiddle, M, lg, k, re, im);
+      pp[k] = re * re + im * im;
+      if (k == 0) {
+        rfft_unpack_bin(zz, twiddle, M, lg, M, re, im);
+        pp[M] = re * re + im * im;
       }
     }
     __syncthreads();
@@ -166,14 +153,6 @@ __global__ __launch_bounds__(kPatchLanes) void patch_finish_kernel(const uint32_
   }
 }
 
-static int patch_grid_cap() {
-  // TEST knob (the same bits for every value: tests/test_patch_gpu.py compares): the cap of both kernels' grids
-  const char* e = getenv("WSEG_PATCH_GRID");
-  if (!e || !*e) return kPatchGridCap;
-  const long v = strtol(e, nullptr, 10);
-  return v < 1 ? 1 : v > 65535 ? 65535 : (int)v;
-}
-
 }  // namespace wseg
 
 using namespace wseg;
@@ -197,7 +176,8 @@ extern "C" int wseg_patches_f32(const wseg_logmel_desc* d, const float* pcm, int
   if (n_seg > 0 && !bounds_host) { set_error("%s: bounds_host is null for n_seg = %d", fn, (int)n_seg); return WSEG_ERR_INVALID; }
   PatchPlan plan;
   char msg[200];
-  if (patch_plan(PatchBoundsArray{bounds_host}, n_seg, d->n_mels, width, d->n_fft, n, patch_grid_cap(), &plan, nullptr, msg, sizeof(msg))) {
+  if (patch_plan(SegmentBoundsArray{bounds_host}, n_seg, d->n_mels, width, d->n_fft, n, grid_cap_env("WSEG_PATCH_GRID", kPatchGridCap, 65535), &plan, msg,
+                 sizeof(msg))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }
@@ -206,32 +186,17 @@ extern "C" int wseg_patches_f32(const wseg_logmel_desc* d, const float* pcm, int
     set_error("%s: d must hold device pointers to window, twiddle (8-byte aligned) and the four mel tables", fn);
     return WSEG_ERR_INVALID;
   }
-  if ((n > 0 && !pcm) || ((uintptr_t)pcm & 3)) { set_error("%s: pcm must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)plan.scratch_bytes) {
-    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)plan.scratch_bytes, scratch_bytes);
-    return WSEG_ERR_INVALID;
-  }
-  int slot = -1;
-  const int rc = staging_take((size_t)plan.table_bytes, &slot);
-  if (rc != WSEG_OK) return rc;
-  int64_t* host = static_cast<int64_t*>(staging_host(slot));
-  for (int64_t i = 0; i < n_seg; ++i) {
-    host[2 * i] = bounds_host[2 * i];
-    host[2 * i + 1] = bounds_host[2 * i + 1] - bounds_host[2 * i];
-  }
-  hipError_t e = hipMemcpyAsync(scratch, host, (size_t)plan.table_bytes, hipMemcpyHostToDevice, stream);
-  const hipError_t e2 = staging_release(slot, stream, e == hipSuccess);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { set_error("%s: the table's copy failed: %s", fn, hipGetErrorString(e)); return WSEG_ERR_HIP; }
+  if (const int rc = device_buffers_check(fn, pcm, n, out, scratch, scratch_bytes, plan.scratch_bytes)) return rc;
+  if (const int rc = staging_upload((size_t)plan.table_bytes, scratch, stream, fn,
+                                    [&](void* host) { segment_table_fill(host, bounds_host, n_seg, nullptr); }))
+    return rc;
   PatchArgs a;
   a.d = *d;
   a.pcm = pcm;
   a.n = n;
   a.table = static_cast<const long long*>(scratch);
   a.width = width;
-  a.log2_half = 0;
-  while ((2 << a.log2_half) < d->n_fft) ++a.log2_half;      // n_fft / 2 = 2^log2_half
+  a.log2_half = rfft_log2_half(d->n_fft);
   a.log2_fpi = 0;
   while ((1 << a.log2_fpi) < plan.frames_per_item) ++a.log2_fpi;
   a.total_frames = plan.total_frames;

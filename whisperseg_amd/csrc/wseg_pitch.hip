@@ -4,8 +4,8 @@
 // float64 steps in the same order, so the output has the definition's BITS — for every workgroup size and every grid.  No atomics,
 // no inline assembly.
 //
-// pitch_frame_kernel    a work item is a frame; the host's prefix table of frames per segment maps an item to its segment by
-//   bisection, the grid is capped and strides over the items.  The workgroup (64, 128 or 256 lanes, picked from tau_max in
+// pitch_frame_kernel    a work item is a frame; the segment table's prefix of frames per segment maps an item to its segment
+//   (wseg_segments.h), the grid is capped and strides over the items.  The workgroup (64, 128 or 256 lanes, picked from tau_max in
 //   wseg_pitch_plan.h) lays the frame down in LDS (2 tau_max float32, 16 KiB at the largest range), three floats in and with zeros
 //   around it, so that every wide read below is aligned and stays inside the array.
 //   difference    d(tau) = sum_i (x[i] - x[i + tau])^2, i = 0 .. tau_max - 1.  Lanes own lags: a lane carries the FOUR consecutive
@@ -43,19 +43,15 @@ __global__ __launch_bounds__(kPitchMaxLanes) void pitch_frame_kernel(const float
   __shared__ int first_below[kPitchMaxLanes];
   __shared__ PitchBest best[kPitchMaxLanes];
   const int tid = threadIdx.x, lanes = blockDim.x;
-  const long long* __restrict__ prefix = table + n_seg;
+  const long long* __restrict__ prefix = table + 2 * (long long)n_seg;
   const int width = 2 * tau_max;
   const int groups = (tau_max + kPitchLagsPerLane - 1) / kPitchLagsPerLane;
   const int blocks = (tau_max + kPitchBlock - 1) / kPitchBlock;
   const int full = tau_max & ~3;                     // the i taken four at a time
   double* const inner = reinterpret_cast<double*>(sh);
   for (long long item = blockIdx.x; item < total_frames; item += gridDim.x) {
-    int lo = 0, hi = n_seg;                          // prefix[lo] <= item < prefix[hi]: the segment is the last one that starts at or before the item
-    while (hi - lo > 1) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (prefix[mid] <= item) lo = mid; else hi = mid;
-    }
-    const float* __restrict__ x = pcm + table[lo] + (item - prefix[lo]) * hop;      // x[j], 0 <= j < width, is all this item may read
+    const int lo = segment_of_item(prefix, n_seg, item);
+    const float* __restrict__ x = pcm + table[2 * lo] + (item - prefix[lo]) * hop;      // x[j], 0 <= j < width, is all this item may read
     for (int j = tid; j < width + 16; j += lanes) {
       const int k = j - kPitchFront;
       sh[j] = (k >= 0 && k < width) ? x[k] : 0.0f;
@@ -165,14 +161,6 @@ __global__ __launch_bounds__(kPitchMaxLanes) void pitch_frame_kernel(const float
   }
 }
 
-static int pitch_grid_cap() {
-  // TEST knob (the same bits for every value: tests/test_pitch_gpu.py compares): the cap of the grid
-  const char* e = getenv("WSEG_PITCH_GRID");
-  if (!e || !*e) return kPitchGridCap;
-  const long v = strtol(e, nullptr, 10);
-  return v < 1 ? 1 : v > kPitchGridCap ? kPitchGridCap : (int)v;
-}
-
 }  // namespace wseg
 
 using namespace wseg;
@@ -196,27 +184,15 @@ extern "C" int wseg_pitch_frames_f64(const float* pcm, int64_t n, const int64_t*
   char msg[200];
   if (pitch_args_check(tau_min, tau_max, hop, threshold, msg, sizeof(msg))) { set_error("%s: %s", fn, msg); return WSEG_ERR_INVALID; }
   std::vector<int64_t> prefix((size_t)(n_seg > 0 ? n_seg : 0) + 1);
-  if (pitch_plan(bounds_host, n_seg, tau_max, hop, n, pitch_grid_cap(), &plan, prefix.data(), msg, sizeof(msg))) {
+  if (pitch_plan(bounds_host, n_seg, tau_max, hop, n, grid_cap_env("WSEG_PITCH_GRID", kPitchGridCap, kPitchGridCap), &plan, prefix.data(), msg, sizeof(msg))) {
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }
   if (n_seg == 0 || plan.total_frames == 0) return WSEG_OK;
-  if (!pcm || ((uintptr_t)pcm & 3)) { set_error("%s: pcm must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)plan.scratch_bytes) {
-    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)plan.scratch_bytes, scratch_bytes);
-    return WSEG_ERR_INVALID;
-  }
-  int slot = -1;
-  const int rc = staging_take((size_t)plan.table_bytes, &slot);
-  if (rc != WSEG_OK) return rc;
-  int64_t* host = static_cast<int64_t*>(staging_host(slot));
-  for (int32_t i = 0; i < n_seg; ++i) host[i] = bounds_host[2 * (size_t)i];
-  memcpy(host + (size_t)n_seg, prefix.data(), ((size_t)n_seg + 1) * 8);
-  hipError_t e = hipMemcpyAsync(scratch, host, (size_t)plan.table_bytes, hipMemcpyHostToDevice, stream);
-  const hipError_t e2 = staging_release(slot, stream, e == hipSuccess);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) { set_error("%s: the table's copy failed: %s", fn, hipGetErrorString(e)); return WSEG_ERR_HIP; }
+  if (const int rc = device_buffers_check(fn, pcm, n, out, scratch, scratch_bytes, plan.scratch_bytes)) return rc;      // (a frame: n > 0)
+  if (const int rc = staging_upload((size_t)plan.table_bytes, scratch, stream, fn,
+                                    [&](void* host) { segment_table_fill(host, bounds_host, n_seg, prefix.data()); }))
+    return rc;
   hipLaunchKernelGGL(pitch_frame_kernel, dim3((unsigned)plan.grid), dim3((unsigned)plan.lanes), 0, stream, pcm,
                      static_cast<const long long*>(scratch), (int)n_seg, (long long)plan.total_frames, (int)tau_min, (int)tau_max, (int)hop,
                      threshold, out);

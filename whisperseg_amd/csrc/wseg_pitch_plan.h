@@ -7,7 +7,7 @@
 // them wholly inside the segment:
 //   J = 0 for len < 2 tau_max, else 1 + (len - 2 tau_max) / hop                          (whisperseg_amd/pitch.py::frame_count)
 // A frame is a work item.  Scratch:
-//   int64  table[2 n_seg + 1]     s0 of every segment, then the exclusive prefix of the frame counts (n_seg + 1 entries)
+//   int64  table[3 n_seg + 1]     the segment table with the exclusive prefix of the frame counts (wseg_segments.h)
 //   (padded to kPitchAlign bytes)
 // A lane of the kernel owns kPitchLagsPerLane consecutive lags at a time ("a group": lags 4 g + 1 .. 4 g + 4); the workgroup is the
 // smallest power of two of lanes, 64 .. 256, that gives every group of tau_max a lane, or 256 lanes that take the groups in turns.
@@ -15,6 +15,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "wseg_segments.h"
 
 namespace wseg {
 
@@ -25,7 +26,6 @@ constexpr int kPitchLagsPerLane = 4;           // consecutive lags a lane carrie
 constexpr int kPitchMaxLanes = 256;
 constexpr int kPitchAlign = 256;               // bytes the scratch is padded to
 constexpr int kPitchGridCap = 2048;            // workgroups: 8 per CU; more frames take the grid stride
-constexpr int64_t kPitchMaxSamples = (int64_t)1 << 52;       // of a recording: every sum below stays inside int64
 constexpr int64_t kPitchMaxFrames = (int64_t)1 << 40;        // of one call, all segments together (2^40 * 12 bytes of output)
 
 struct PitchPlan {
@@ -35,7 +35,7 @@ struct PitchPlan {
   int32_t groups;                  // ceil(tau_max / 4): the lag groups of a frame
   int32_t blocks;                  // ceil(tau_max / 64): the blocks of the prefix sum
   int64_t total_frames;            // over all segments
-  int64_t table_bytes;             // (2 n_seg + 1) int64
+  int64_t table_bytes;             // (3 n_seg + 1) int64
   int64_t scratch_bytes;           // table_bytes rounded up to kPitchAlign
   int64_t out_floats;              // 3 total_frames
   int32_t grid;                    // workgroups (0: no frame at all)
@@ -69,7 +69,7 @@ inline void pitch_layout(int32_t n_seg, int64_t total_frames, int32_t tau_max, i
   p.lanes = 64;
   while (p.lanes < p.groups && p.lanes < kPitchMaxLanes) p.lanes *= 2;
   p.total_frames = total_frames;
-  p.table_bytes = (2 * (int64_t)n_seg + 1) * 8;
+  p.table_bytes = segment_table_entries(n_seg, true) * 8;
   p.scratch_bytes = (p.table_bytes + kPitchAlign - 1) / kPitchAlign * kPitchAlign;
   p.out_floats = 3 * total_frames;
   if (grid_cap < 1) grid_cap = 1;
@@ -78,33 +78,17 @@ inline void pitch_layout(int32_t n_seg, int64_t total_frames, int32_t tau_max, i
   *plan = p;
 }
 
-// Validates bounds[n_seg][2] (0 <= s0 <= s1 <= n; n < 0: no recording length is known, s1 <= kPitchMaxSamples), tau_max and hop, fills
-// the plan and, where `prefix` is given (n_seg + 1 entries), the exclusive prefix of the frame counts -> 0, or -1 with the
-// offending argument's name in msg.  n_seg == 0 is valid: no frame, grid 0, scratch_bytes = the padded one-entry table.
+// Validates tau_max, hop and bounds[n_seg][2] against n (wseg_segments.h::segment_prefix), fills the plan and, where `prefix` is
+// given (n_seg + 1 entries), the exclusive prefix of the frame counts -> 0, or -1 with the offending argument's name in msg.
+// n_seg == 0 is valid: no frame, grid 0, scratch_bytes = the padded one-entry table.
 inline int pitch_plan(const int64_t* bounds, int32_t n_seg, int32_t tau_max, int32_t hop, int64_t n, int64_t grid_cap, PitchPlan* plan,
                       int64_t* prefix, char* msg, size_t msg_len) {
   if (tau_max < 3 || tau_max > kPitchMaxLag) { snprintf(msg, msg_len, "tau_max must be 3 .. %d (got %d)", kPitchMaxLag, (int)tau_max); return -1; }
   if (hop < 1) { snprintf(msg, msg_len, "hop must be at least 1 (got %d)", (int)hop); return -1; }
-  if (n_seg < 0) { snprintf(msg, msg_len, "n_seg is negative (%d)", (int)n_seg); return -1; }
-  if (n_seg > 0 && !bounds) { snprintf(msg, msg_len, "bounds is null for n_seg = %d", (int)n_seg); return -1; }
-  if (n > kPitchMaxSamples) { snprintf(msg, msg_len, "n must be at most 2^52 samples (got %lld)", (long long)n); return -1; }
-  const int64_t limit = n < 0 ? kPitchMaxSamples : n;
-  int64_t total = 0;
-  for (int32_t i = 0; i < n_seg; ++i) {
-    const int64_t s0 = bounds[2 * (int64_t)i], s1 = bounds[2 * (int64_t)i + 1];
-    if (s0 < 0 || s1 < s0 || s1 > limit) {
-      snprintf(msg, msg_len, "bounds of segment %d must satisfy 0 <= s0 <= s1 <= %lld (got %lld, %lld)", (int)i, (long long)limit,
-               (long long)s0, (long long)s1);
-      return -1;
-    }
-    if (prefix) prefix[i] = total;
-    total += pitch_frames(s1 - s0, tau_max, hop);      // at most 2^52 a segment; checked before it can pass 2^53
-    if (total > kPitchMaxFrames) {
-      snprintf(msg, msg_len, "bounds hold more than 2^40 frames up to segment %d", (int)i);
-      return -1;
-    }
-  }
-  if (prefix) prefix[n_seg] = total;
+  int64_t total;
+  if (segment_prefix(SegmentBoundsArray{bounds}, n_seg, n, [tau_max, hop](int64_t len) { return pitch_frames(len, tau_max, hop); },
+                     kPitchMaxFrames, "frames", prefix, &total, msg, msg_len))
+    return -1;
   pitch_layout(n_seg, total, tau_max, hop, grid_cap, plan);
   return 0;
 }

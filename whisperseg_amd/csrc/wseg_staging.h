@@ -1,7 +1,7 @@
-// A host table's way to the device without waiting for the stream (wseg_measure.hip, wseg_patch.hip): the table arrives as a host
-// array and the call must not synchronise, so it is written into a pinned buffer the library owns and copied from there on the
-// stream; an event behind the copy says when the buffer is free again.  A call takes a free buffer that is large enough or makes
-// a new one; the pool — one for the whole library — lives as long as the process.
+// A host table's way to the device without waiting for the stream (wseg_measure.hip, wseg_patch.hip, wseg_pitch.hip): the table
+// arrives as a host array and the call must not synchronise, so it is written into a pinned buffer the library owns and copied
+// from there on the stream; an event behind the copy says when the buffer is free again.  A call takes a free buffer that is large
+// enough or makes a new one; the pool — one for the whole library — lives as long as the process.
 #pragma once
 #include <mutex>
 #include <vector>
@@ -19,7 +19,7 @@ struct Staging {
 inline std::mutex g_staging_mutex;
 inline std::vector<Staging> g_staging;
 
-inline int staging_take(size_t bytes, int* index) {
+inline int staging_take(size_t bytes, int* index, void** host) {
   int device = 0;
   WSEG_HIP_CHECK(hipGetDevice(&device));
   std::lock_guard<std::mutex> lock(g_staging_mutex);
@@ -28,6 +28,7 @@ inline int staging_take(size_t bytes, int* index) {
     if (!s.taken && s.device == device && s.cap >= bytes && hipEventQuery(s.done) == hipSuccess) {
       s.taken = true;
       *index = (int)i;
+      *host = s.host;
       return WSEG_OK;
     }
   }
@@ -45,19 +46,39 @@ inline int staging_take(size_t bytes, int* index) {
   }
   g_staging.push_back(s);
   *index = (int)g_staging.size() - 1;
+  *host = s.host;
   return WSEG_OK;
 }
-inline void* staging_host(int index) {
-  std::lock_guard<std::mutex> lock(g_staging_mutex);
-  return g_staging[index].host;
+
+// `bytes` that fill(host pointer) writes into a pinned buffer, copied to the device pointer dst on the stream -> WSEG_OK, or the
+// error with the calling function's name `fn` in wseg_last_error().
+template <class Fill>
+inline int staging_upload(size_t bytes, void* dst, hipStream_t stream, const char* fn, Fill fill) {
+  int slot = -1;
+  void* host = nullptr;
+  if (const int rc = staging_take(bytes, &slot, &host)) return rc;
+  fill(host);
+  hipError_t e = hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, stream);
+  {                                                  // the event behind the copy frees the buffer (no copy was started: free at once)
+    std::lock_guard<std::mutex> lock(g_staging_mutex);
+    if (e == hipSuccess) e = hipEventRecord(g_staging[slot].done, stream);
+    g_staging[slot].taken = false;
+  }
+  if (e != hipSuccess) { set_error("%s: the table's copy failed: %s", fn, hipGetErrorString(e)); return WSEG_ERR_HIP; }
+  return WSEG_OK;
 }
-// Records the event behind the copy (enqueued == false: no copy was started, the buffer is free at once) and gives the buffer back.
-inline hipError_t staging_release(int index, hipStream_t stream, bool enqueued) {
-  std::lock_guard<std::mutex> lock(g_staging_mutex);
-  Staging& s = g_staging[index];
-  const hipError_t e = enqueued ? hipEventRecord(s.done, stream) : hipSuccess;
-  s.taken = false;
-  return e;
+
+// pcm (float32 [n], may be null only when n == 0), out (float32) and scratch (8-byte aligned, at least `needed` bytes) of a call
+// that has segments -> WSEG_OK, or WSEG_ERR_INVALID with the argument's name.
+inline int device_buffers_check(const char* fn, const float* pcm, int64_t n, const float* out, const void* scratch, size_t scratch_bytes,
+                                int64_t needed) {
+  if ((n > 0 && !pcm) || ((uintptr_t)pcm & 3)) { set_error("%s: pcm must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
+  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
+  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)needed) {
+    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)needed, scratch_bytes);
+    return WSEG_ERR_INVALID;
+  }
+  return WSEG_OK;
 }
 
 }  // namespace wseg

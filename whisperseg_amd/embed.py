@@ -331,11 +331,7 @@ def host_epochs(run):
 def scratch_bytes(n, dim):
     """wseg_embed_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
     from . import _lib
-    lib = _lib.load()
-    nbytes = lib.wseg_embed_scratch_bytes(int(n), int(dim))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_embed_scratch_bytes(int(n), int(dim)))
 
 
 def layout_epochs(run, device="cuda"):

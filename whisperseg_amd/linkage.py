@@ -150,11 +150,7 @@ def mst_of_weights(w):
 def scratch_bytes(n, d):
     """wseg_mst_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
     from . import _lib
-    lib = _lib.load()
-    nbytes = lib.wseg_mst_scratch_bytes(int(n), int(d))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_mst_scratch_bytes(int(n), int(d)))
 
 
 def mst_round(rows, core, component, out_index=None, out_weight=None, scratch=None):

@@ -28,7 +28,9 @@ import math
 
 import numpy as np
 
+from . import _lib
 from .audio_utils import get_n_fft_given_sr
+from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch, sample_bounds  # noqa: F401 (bounds_of, sample_bounds: re-exported)
 
 COLUMNS = ("peak_amplitude", "rms", "zero_crossing_rate", "peak_frequency", "centroid_frequency", "freq_05", "freq_95",
            "spectral_entropy")
@@ -39,13 +41,6 @@ _FRAME_BLOCK = 256            # frames measure_host transforms at a time (bounds
 def hann_periodic(n):
     """The front-end's window (oracle.frontend.hann_periodic, HF window_function(n, 'hann')): np.hanning(n + 1)[:-1], float64."""
     return np.hanning(n + 1)[:-1]
-
-
-def sample_bounds(onset, offset, sr, n):
-    """(s0, s1) of a segment: half-sample rounding, clamped to the recording, never reversed."""
-    s0 = min(max(int(math.floor(onset * sr + 0.5)), 0), n)
-    s1 = max(s0, min(max(int(math.floor(offset * sr + 0.5)), 0), n))
-    return s0, s1
 
 
 def frame_count(length, n_fft):
@@ -68,12 +63,6 @@ def band_bins(sr, n_fft, min_frequency=0, max_frequency=None):
         raise ValueError(f"the band {min_frequency} .. {max_frequency} Hz holds no FFT bin at sr={sr}, n_fft={n_fft} "
                          f"(k_lo={k_lo} > k_hi={k_hi})")
     return k_lo, k_hi
-
-
-def bounds_of(prediction, sr, n):
-    """int64 [n_seg, 2]: sample_bounds of every row of a prediction dict."""
-    rows = [sample_bounds(float(on), float(off), sr, n) for on, off in zip(prediction["onset"], prediction["offset"])]
-    return np.asarray(rows, dtype=np.int64).reshape(-1, 2)
 
 
 def power_spectrum(x, s0, s1, n_fft, fft_dtype=np.float64):
@@ -176,36 +165,25 @@ def _device_tables(n_fft, device):
 
 def scratch_bytes(bounds, n_fft):
     """wseg_measure_scratch_bytes (host arithmetic, no device) of int64 bounds [n_seg, 2]; WsegError for invalid input."""
-    from . import _lib
-    lib = _lib.load()
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
-    nbytes = lib.wseg_measure_scratch_bytes(bounds.ctypes.data_as(C.c_void_p), len(bounds), int(n_fft))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_measure_scratch_bytes(bounds.ctypes.data_as(C.c_void_p), len(bounds), int(n_fft)))
 
 
 def measure_rows(pcm, bounds, n_fft, k_lo, k_hi, out=None):
     """The launch pair: rate-free rows, a float32 DEVICE tensor [n_seg, 8] (`out`, where given), of the int64 sample ranges
     `bounds` [n_seg, 2] (host) in the device tensor `pcm` (float32 [n], contiguous).  Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.WsegError("measure_rows needs a contiguous float32 device tensor [n] (no CPU path)")
+    check_pcm(pcm, "measure_rows")
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg = len(bounds)
-    if out is None:
-        out = torch.empty((n_seg, 8), dtype=torch.float32, device=pcm.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.shape == (n_seg, 8) and out.is_contiguous()):
-        raise _lib.WsegError("out must be a contiguous float32 device tensor [n_seg, 8]")
+    out = check_out(out, (n_seg, 8), "[n_seg, 8]", pcm.device)
     window, twiddle = _device_tables(n_fft, pcm.device)
-    nbytes = scratch_bytes(bounds, n_fft)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pcm.device)
+    scratch = new_scratch(scratch_bytes(bounds, n_fft), pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_measure_segments_f32(pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
                                                  bounds.ctypes.data_as(C.c_void_p), n_seg, int(n_fft), int(k_lo), int(k_hi),
-                                                 window.data_ptr(), twiddle.data_ptr(), scratch.data_ptr(), nbytes,
+                                                 window.data_ptr(), twiddle.data_ptr(), scratch.data_ptr(), scratch.numel(),
                                                  out.data_ptr(), _lib.stream_ptr()))
     return out
 
@@ -213,13 +191,7 @@ def measure_rows(pcm, bounds, n_fft, k_lo, k_hi, out=None):
 def measure(audio, sr, prediction, min_frequency=0, max_frequency=None, device="cuda"):
     """measure_host's columns, computed on the GPU: {column: float32 numpy [n_seg]}.  `audio`: numpy [n] (uploaded to `device`) or
     a device tensor, which is measured where it lies — no PCM travels back to the host, only the rows do."""
-    import torch
-    if torch.is_tensor(audio):
-        pcm = audio.to(dtype=torch.float32).contiguous() if audio.is_cuda else audio.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).to(device)
-    if pcm.dim() != 1:
-        raise ValueError("audio must be one mono recording [n]")
+    pcm = device_pcm(audio, device)
     n_fft = get_n_fft_given_sr(sr)
     k_lo, k_hi = band_bins(sr, n_fft, min_frequency, max_frequency)
     bounds = bounds_of(prediction, sr, int(pcm.numel()))

@@ -331,15 +331,13 @@ class SegmenterBase:
         return bool(measure) or patches is not None or pitch is not None
 
     @staticmethod
-    def _measured(prediction, pcm, sr, min_frequency):
-        """The final rows of a recording + their measurements on its device PCM (one launch pair; only the rows come back)."""
-        from . import measure as M
-        return M.with_columns(prediction, M.measure(pcm, sr, prediction, min_frequency=min_frequency))
-
-    @classmethod
-    def _finished(cls, prediction, pcm, sr, min_frequency, measure, patches, pitch=None):
-        """The final rows of a recording + what was asked for of its device PCM: the measurements, the pitch, the pictures, or all."""
-        out = cls._measured(prediction, pcm, sr, min_frequency) if measure else prediction
+    def _finished(prediction, pcm, sr, min_frequency, measure, patches, pitch=None):
+        """The final rows of a recording + what was asked for of its device PCM: the measurements, the pitch, the pictures, or all
+        (a launch or a launch pair each; only the rows come back)."""
+        out = prediction
+        if measure:
+            from . import measure as M
+            out = M.with_columns(out, M.measure(pcm, sr, prediction, min_frequency=min_frequency))
         if pitch is not None:
             from . import pitch as F0
             out = F0.with_columns(out, F0.pitch(pcm, sr, prediction, **F0.options(pitch, sr)))

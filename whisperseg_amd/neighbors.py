@@ -92,11 +92,7 @@ def neighbors_host(queries, corpus=None, k=15):
 def scratch_bytes(m, n, d, k):
     """wseg_knn_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
     from . import _lib
-    lib = _lib.load()
-    nbytes = lib.wseg_knn_scratch_bytes(int(m), int(n), int(d), int(k))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_knn_scratch_bytes(int(m), int(n), int(d), int(k)))
 
 
 def knn_rows(queries, corpus=None, k=15, out_index=None, out_distance=None):

@@ -25,8 +25,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import measure as M
+from . import _lib, measure as M
 from .audio_utils import N_MELS, get_n_fft_given_sr, slaney_mel_filters
+from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch
 
 MAX_WIDTH = 256                        # columns of a patch (csrc/wseg_patch_plan.h::kPatchMaxWidth)
 PATCH_BLOCK_BYTES = 256 << 20          # device output `patches` holds at a time: the rows go through in blocks of at most this
@@ -85,7 +86,7 @@ def patches_host(audio, sr, prediction, width=32, min_frequency=0, max_frequency
     fb = filterbank(sr, n_fft, min_frequency, max_frequency)
     if fft_dtype != np.float64:
         fb = fb.astype(np.float32).astype(np.float64)
-    bounds = M.bounds_of(prediction, sr, len(x))
+    bounds = bounds_of(prediction, sr, len(x))
     out = np.empty((len(bounds), fb.shape[1], width), dtype=np.float32)
     for row, (s0, s1) in zip(out, bounds):
         row[...] = normalise(log_mel_columns(x, column_centres(s0, s1, width), n_fft, fb, fft_dtype))
@@ -113,12 +114,7 @@ def device_tables(sr, min_frequency=0, max_frequency=None, device="cuda"):
 
 def scratch_bytes(n_seg, n_mels, width):
     """wseg_patches_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
-    lib = _lib.load()
-    nbytes = lib.wseg_patches_scratch_bytes(int(n_seg), int(n_mels), int(width))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_patches_scratch_bytes(int(n_seg), int(n_mels), int(width)))
 
 
 def patch_rows(pcm, bounds, tables, width, out=None):
@@ -126,24 +122,18 @@ def patch_rows(pcm, bounds, tables, width, out=None):
     [n_seg, 2] (host) in the device tensor `pcm` (float32 [n], contiguous), with the `tables` of device_tables.  Stream-ordered, no
     host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.WsegError("patch_rows needs a contiguous float32 device tensor [n] (no CPU path)")
+    check_pcm(pcm, "patch_rows")
     if tables.window.device != pcm.device:
         raise _lib.WsegError(f"the tables are on {tables.window.device}, the recording on {pcm.device}")
     width = check_width(width)
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg, n_mels = len(bounds), int(tables.desc.n_mels)
-    if out is None:
-        out = torch.empty((n_seg, n_mels, width), dtype=torch.float32, device=pcm.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.shape == (n_seg, n_mels, width) and out.is_contiguous()):
-        raise _lib.WsegError("out must be a contiguous float32 device tensor [n_seg, n_mels, width]")
-    nbytes = scratch_bytes(n_seg, n_mels, width)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pcm.device)
+    out = check_out(out, (n_seg, n_mels, width), "[n_seg, n_mels, width]", pcm.device)
+    scratch = new_scratch(scratch_bytes(n_seg, n_mels, width), pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_patches_f32(C.byref(tables.desc), pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
-                                        bounds.ctypes.data_as(C.c_void_p), n_seg, width, scratch.data_ptr(), nbytes,
+                                        bounds.ctypes.data_as(C.c_void_p), n_seg, width, scratch.data_ptr(), scratch.numel(),
                                         out.data_ptr() if out.numel() else None, _lib.stream_ptr()))
     return out
 
@@ -153,17 +143,11 @@ def patches(audio, sr, prediction, width=32, min_frequency=0, max_frequency=None
     a device tensor, which is measured where it lies — no PCM travels back to the host, only the pictures do.  The rows go through
     in blocks of at most PATCH_BLOCK_BYTES of device output (a recording with 100 000 rows needs no 2 GB tensor); a segment's bits
     do not depend on the block it falls into."""
-    import torch
     width = check_width(width)
-    if torch.is_tensor(audio):
-        pcm = audio.to(dtype=torch.float32).contiguous() if audio.is_cuda else audio.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).to(device)
-    if pcm.dim() != 1:
-        raise ValueError("audio must be one mono recording [n]")
+    pcm = device_pcm(audio, device)
     n_fft = get_n_fft_given_sr(sr)
     M.band_bins(sr, n_fft, min_frequency, max_frequency)
-    bounds = M.bounds_of(prediction, sr, int(pcm.numel()))
+    bounds = bounds_of(prediction, sr, int(pcm.numel()))
     out = np.empty((len(bounds), N_MELS, width), dtype=np.float32)
     if not len(bounds):
         return out

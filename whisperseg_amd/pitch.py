@@ -37,8 +37,9 @@ import math
 
 import numpy as np
 
-from . import measure as M
+from . import _lib
 from .audio_utils import get_n_fft_given_sr
+from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch
 
 COLUMNS = ("f0_mean", "f0_min", "f0_max", "f0_first", "f0_last", "voiced_fraction", "aperiodicity")
 CONTOUR_KEYS = ("f0_contour", "aperiodicity_contour", "frame_time")
@@ -271,7 +272,7 @@ def pitch_host(audio, sr, prediction, f_min=None, f_max=None, threshold=0.1, hop
     if x.ndim != 1:
         raise ValueError("audio must be one mono recording [n]")
     tau_min, tau_max, hop = _resolved(sr, f_min, f_max, threshold, hop)
-    bounds = M.bounds_of(prediction, sr, len(x))
+    bounds = bounds_of(prediction, sr, len(x))
     frames, offsets = frames_host(x, bounds, tau_min, tau_max, hop, threshold)
     return _result(frames, offsets, bounds, tau_max, hop, sr, contour)
 
@@ -306,13 +307,8 @@ def options(pitch, sr=None):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(bounds, tau_max, hop):
     """wseg_pitch_scratch_bytes (host arithmetic, no device) of int64 bounds [n_seg, 2]; WsegError for invalid input."""
-    from . import _lib
-    lib = _lib.load()
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
-    nbytes = lib.wseg_pitch_scratch_bytes(bounds.ctypes.data_as(C.c_void_p), len(bounds), int(tau_max), int(hop))
-    if nbytes == 0:
-        raise _lib.WsegError("libwseg call failed: " + lib.wseg_last_error().decode())
-    return nbytes
+    return _lib.size_or_raise(_lib.load().wseg_pitch_scratch_bytes(bounds.ctypes.data_as(C.c_void_p), len(bounds), int(tau_max), int(hop)))
 
 
 def pitch_rows(pcm, bounds, tau_min, tau_max, hop, threshold=0.1, out=None):
@@ -320,20 +316,15 @@ def pitch_rows(pcm, bounds, tau_min, tau_max, hop, threshold=0.1, out=None):
     voiced) per frame, rate-free, and the host int64 [n_seg + 1] offsets of every row's frames in it — of the int64 sample ranges
     `bounds` [n_seg, 2] (host) in the device tensor `pcm` (float32 [n], contiguous).  Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.WsegError("pitch_rows needs a contiguous float32 device tensor [n] (no CPU path)")
+    check_pcm(pcm, "pitch_rows")
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg = len(bounds)
     nbytes = scratch_bytes(bounds, tau_max, hop)      # (validates bounds, tau_max and hop: the frame counts below are then defined)
     offsets = frame_offsets_of(bounds, int(tau_max), int(hop))
     total = int(offsets[-1])
-    if out is None:
-        out = torch.empty((total, 3), dtype=torch.float32, device=pcm.device)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.shape == (total, 3) and out.is_contiguous()):
-        raise _lib.WsegError("out must be a contiguous float32 device tensor [total_frames, 3]")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pcm.device)
+    out = check_out(out, (total, 3), "[total_frames, 3]", pcm.device)
+    scratch = new_scratch(nbytes, pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_pitch_frames_f64(pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
                                              bounds.ctypes.data_as(C.c_void_p), n_seg, int(tau_min), int(tau_max), int(hop),
@@ -345,15 +336,9 @@ def pitch_rows(pcm, bounds, tau_min, tau_max, hop, threshold=0.1, out=None):
 def pitch(audio, sr, prediction, f_min=None, f_max=None, threshold=0.1, hop=None, contour=False, device="cuda"):
     """pitch_host's columns (and, with contour=True, its per-row contours), computed on the GPU: `audio` is numpy [n] (uploaded to
     `device`) or a device tensor, which is used where it lies — no PCM travels back to the host, only the frames do."""
-    import torch
     tau_min, tau_max, hop = _resolved(sr, f_min, f_max, threshold, hop)      # (before any device work)
-    if torch.is_tensor(audio):
-        pcm = audio.to(dtype=torch.float32).contiguous() if audio.is_cuda else audio.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).to(device)
-    if pcm.dim() != 1:
-        raise ValueError("audio must be one mono recording [n]")
-    bounds = M.bounds_of(prediction, sr, int(pcm.numel()))
+    pcm = device_pcm(audio, device)
+    bounds = bounds_of(prediction, sr, int(pcm.numel()))
     if not len(bounds):
         frames, offsets = np.zeros((0, 3), dtype=np.float32), np.zeros(1, dtype=np.int64)
     else:
