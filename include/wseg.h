@@ -345,6 +345,42 @@ int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const u
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * k nearest neighbours of every query row among the corpus rows under banded dynamic time warping, and the warping distance of
+ * a list of pairs: the warping-tolerant counterpart of wseg_knn_f32 over the patches above or any float32 rows.  A row is a
+ * sequence of `steps` columns of `channels` values, time fastest: row[ch * steps + t].  whisperseg_amd/dtw.py::dtw_host is the
+ * definition (numpy, float64): the local cost c(a, b) = sum_ch (q[ch][a] - x[ch][b])^2, one sequential chain in ch with the
+ * difference, the square and the addition each rounded once; G(0, 0) = c(0, 0), G(a, b) = c(a, b) + the least of G(a-1, b-1),
+ * G(a-1, b), G(a, b-1) inside the band |a - b| <= band; dtw = G(steps-1, steps-1), no step weights, no normalisation; the
+ * neighbours of row i are the k candidates that come first in the total order (dtw(i, j), j), ascending.  band == 0 is the squared
+ * Euclidean distance.  The m x n matrix never exists: a selection kernel forms the costs |q_a|^2 + |x_b|^2 - 2 q_a.x_b of a tile of
+ * pairs on the fp32 matrix cores (every term one channel-ordered fmaf chain: the same bits for every tiling, grid and split), runs
+ * the recurrence over them in float32 and keeps the k + 8 best per row; a finish kernel recomputes those by the definition in
+ * float64, orders them by (that distance as float32, j) and writes the first k — a reported distance has the definition's float32
+ * bits, and the selection's error (<= 2 (2 steps - 1)(channels + 2 steps + 4) 2^-24 (max_a |q_a|^2 + max_b |x_b|^2)) only matters
+ * at the k-th boundary.
+ * queries: device float32 [m][channels * steps]; corpus: device float32 [n][channels * steps] (may be queries); m, n 0 .. 2^31 - 1,
+ * channels 1 .. 128, steps 1 .. 64, band 0 .. steps - 1, k 1 .. 64.  exclude_same_index 1: j == i is no candidate (queries ==
+ * corpus; by index, not by value).  Inputs must be finite; with non-finite input the order is unspecified, and still nothing
+ * outside the outputs and scratch is written, nothing outside queries and corpus read.  index_out: device int32 [m][k];
+ * distance_out: device float32 [m][k]; where a row has fewer than k candidates its tail is -1 / +inf.  scratch: device, 8-byte
+ * aligned, wseg_dtw_scratch_bytes(m, n, channels, steps, k) bytes — host arithmetic, no device, monotone in m, n, steps and k; 0
+ * with the reason in wseg_last_error() for sizes out of range.  m == 0 returns 0 without a launch; n == 0 only fills -1 / +inf.
+ * wseg_dtw_pairs_f64: out[p] = float32(dtw(queries[pairs[p][0]], corpus[pairs[p][1]])) by the definition's float64 steps, for
+ * pairs: device int32 [count][2], out: device float32 [count], count 0 .. 2^31 - 1 (0: no launch); a pair with an index outside its
+ * rows reads nothing and gives NaN.
+ * Every argument is validated on the host before a launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).
+ * Stream-ordered, no host synchronisation, no atomics.
+ * $WSEG_DTW_GRID: a TEST knob, the cap on the grids and with it the candidate splits (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_dtw_scratch_bytes(int64_t m, int64_t n, int32_t channels, int32_t steps, int32_t k);
+int wseg_dtw_knn_f32(const float* queries, int64_t m, const float* corpus, int64_t n, int32_t channels, int32_t steps, int32_t band,
+                     int32_t k, int32_t exclude_same_index, void* scratch, size_t scratch_bytes, int32_t* index_out,
+                     float* distance_out, void* stream);
+int wseg_dtw_pairs_f64(const float* queries, int64_t m, const float* corpus, int64_t n, int32_t channels, int32_t steps, int32_t band,
+                       const int32_t* pairs, int64_t count, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-segment fundamental frequency from the resident PCM: a YIN pitch contour of every row (what the spectral columns above do
  * not give: they name the loudest partial of a harmonic stack, not its fundamental, and nothing inside the call).
  * whisperseg_amd/pitch.py::frames_host is the definition (numpy, float64, every sum in a stated order); the kernel takes the same

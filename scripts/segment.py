@@ -23,6 +23,11 @@ zero-crossing rate, peak / centroid / 5 % / 95 % frequency, spectral entropy), t
 --neighbors K (needs --patches and --patches_save_path) adds the K nearest neighbours of every row among all rows of the archive,
 found on the GPU (whisperseg_amd.neighbors): `neighbor_index` int32 [rows, K] — rows of the archive, which is the CSV's row order;
 -1 where fewer than K other rows exist — and `neighbor_distance` float32 [rows, K], the squared Euclidean distance of the pictures.
+--neighbors_metric dtw [--neighbors_band R] (needs --neighbors or --embed; --patches W up to 64) compares two pictures by banded
+dynamic time warping over their columns instead (whisperseg_amd.dtw, on the GPU): a warping path may leave the diagonal by up to R
+columns (0 .. W - 1, default max(1, W // 8); 0 is the Euclidean distance again).  The lists of --neighbors are then DTW lists and the
+archive also holds `neighbor_metric` ("dtw") and `neighbor_band`; --embed builds its graph from DTW lists of --embed_neighbors rows.
+--clusters stays Euclidean: the spanning tree computes its own distances.
 --clusters MIN_SIZE [--cluster_min_samples S] (needs --patches and --patches_save_path) groups the rows of the archive into call
 types by HDBSCAN over the pictures (whisperseg_amd.linkage; the mutual-reachability minimum spanning tree is built on the GPU):
 `patch_cluster` int32 [rows] — clusters of at least MIN_SIZE rows numbered by their first row, -1: noise (the archive's `cluster`
@@ -96,6 +101,11 @@ def build_parser():
     p.add_argument("--patches_save_path", default=None, metavar="FILE.npz", help="where --patches W saves the pictures (numpy .npz)")
     p.add_argument("--neighbors", default=None, type=int, metavar="K",
                    help="add the K (1 .. 64) nearest neighbours of every row among the saved pictures to --patches_save_path")
+    p.add_argument("--neighbors_metric", default=None, choices=("euclidean", "dtw"),
+                   help="--neighbors / --embed: the distance of two pictures — euclidean (default), or dtw: banded dynamic time warping over "
+                        "their columns (--patches up to 64)")
+    p.add_argument("--neighbors_band", default=None, type=int, metavar="R",
+                   help="--neighbors_metric dtw: columns a warping path may leave the diagonal by (0 .. W - 1, default max(1, W // 8))")
     p.add_argument("--clusters", default=None, type=int, metavar="MIN_SIZE",
                    help="add HDBSCAN clusters of at least MIN_SIZE (>= 2) rows over the saved pictures, and their spanning tree, to --patches_save_path")
     p.add_argument("--cluster_min_samples", default=None, type=int, metavar="S",
@@ -116,7 +126,8 @@ def build_parser():
 
 def parse_args(argv=None):
     """The parsed arguments; --patches and --patches_save_path without each other, a width outside 1 .. 256, --neighbors or --clusters
-    without them, a K outside 1 .. 64, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
+    without them, a K outside 1 .. 64, --neighbors_metric without --neighbors or --embed, --neighbors_band without the metric dtw or
+    outside 0 .. W - 1, the metric dtw with more than 64 columns, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
     errors; so are --embed without the patches, a DIM other than 2 or 3, --embed_neighbors outside 1 .. 64, --embed_min_dist outside
     [0, 1), a negative --embed_seed and any of the three without --embed; and --pitch_min_hz, --pitch_max_hz, --pitch_threshold or
     --pitch_save_path without --pitch, a frequency that is not positive, a range that is none, a threshold outside (0, 1) and a
@@ -133,6 +144,16 @@ def parse_args(argv=None):
         parser.error("--neighbors K needs --patches W and --patches_save_path FILE.npz")
     if args.neighbors is not None and not 1 <= args.neighbors <= 64:
         parser.error("--neighbors must be 1 .. 64")
+    if args.neighbors_metric is not None and args.neighbors is None and args.embed is None:
+        parser.error("--neighbors_metric needs --neighbors K or --embed DIM")
+    if args.neighbors_metric is None:
+        args.neighbors_metric = "euclidean"
+    if args.neighbors_band is not None and args.neighbors_metric != "dtw":
+        parser.error("--neighbors_band R needs --neighbors_metric dtw")
+    if args.neighbors_metric == "dtw" and args.patches is not None and args.patches > 64:
+        parser.error("--neighbors_metric dtw takes --patches of up to 64 columns")
+    if args.neighbors_band is not None and args.patches is not None and not 0 <= args.neighbors_band <= args.patches - 1:
+        parser.error("--neighbors_band must be 0 .. W - 1 columns")
     if args.clusters is not None and args.patches is None:
         parser.error("--clusters MIN_SIZE needs --patches W and --patches_save_path FILE.npz")
     if args.clusters is not None and args.clusters < 2:
@@ -311,10 +332,15 @@ def main(argv=None):
     if args.patches is not None:
         import numpy as np
         archive = patch_archive(*tabled, width=args.patches)
+        dtw = args.neighbors_metric == "dtw"
+        if dtw:
+            from whisperseg_amd.dtw import check_band, patch_dtw_neighbors
         if args.neighbors is not None:
             from whisperseg_amd.neighbors import patch_neighbors
-            lists = patch_neighbors(tabled[0], args.neighbors)
+            lists = patch_dtw_neighbors(tabled[0], args.neighbors, args.neighbors_band) if dtw else patch_neighbors(tabled[0], args.neighbors)
             archive.update(lists)
+            if dtw:                                              # (absent: the archive as it was)
+                archive.update(neighbor_metric=np.array("dtw"), neighbor_band=np.array(check_band(args.neighbors_band, args.patches), dtype=np.int64))
         if args.clusters is not None:
             from whisperseg_amd.linkage import patch_clusters
             found = patch_clusters(tabled[0], args.clusters, args.cluster_min_samples)
@@ -322,6 +348,8 @@ def main(argv=None):
         if args.embed is not None:
             from whisperseg_amd.embed import patch_embedding
             shared = args.neighbors == args.embed_neighbors          # the same K: the lists are computed once
+            if dtw and not shared:                                   # the graph of the map is the warping distance's
+                lists, shared = patch_dtw_neighbors(tabled[0], args.embed_neighbors, args.neighbors_band), True
             archive.update(patch_embedding(tabled[0], args.embed_neighbors, args.embed, args.embed_min_dist, seed=args.embed_seed,
                                            lists=(lists["neighbor_index"], lists["neighbor_distance"]) if shared else None))
         np.savez(args.patches_save_path, **archive)
