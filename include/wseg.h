@@ -345,6 +345,31 @@ int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const u
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Principal components of float32 rows: the two heavy steps of whisperseg_amd/pca.py on the fp64 matrix cores
+ * (v_mfma_f64_16x16x4_f64).  pca.py::moments_host and project_host are the definitions (numpy, float64); the covariance, the
+ * eigen-decomposition and the conventions are host work there.
+ *   wseg_pca_moments_f64   sum[c] = sum_n x[n][c] and gram[i][j] = sum_n x[n][i] x[n][j]: every product the exact float64 product
+ *                          of the two float32 values, every sum within (n - 1) 2^-53 sum|terms| of its exact value and exact where
+ *                          all partial sums are; gram is symmetric bit for bit (only the tiles on and above the diagonal are
+ *                          computed).  The rows are split as a function of (n, d) alone and the partial tiles added in ascending
+ *                          split order: no atomics, the same bits on every run.
+ *   wseg_pca_project_f64   out[n][j] = sum_c (float64(x[n][c]) - mean[c]) basis[c][j], within (d + 2) 2^-53 sum|terms|.
+ * rows: device float32 [n][d], finite; n 1 .. 2^31 - 1, d 1 .. 8192, r 1 .. 64.  sum: device float64 [d]; gram: device float64
+ * [d][d]; mean: device float64 [d]; basis: device float64 [d][r], row-major; out: device float64 [n][r].  scratch: device, 8-byte
+ * aligned, wseg_pca_scratch_bytes(n, d) bytes — host arithmetic, no device, monotone in n and d; 0 with the reason in
+ * wseg_last_error() for sizes out of range.  Outputs and scratch must not overlap the inputs or each other.  Nothing outside rows,
+ * mean and basis is read, nothing outside sum, gram, out and the scratch written.  Every argument is validated on the host before a
+ * launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * $WSEG_PCA_GRID: a TEST knob, the cap on the grids (the same bits for every value: the splits do not depend on it).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+size_t wseg_pca_scratch_bytes(int64_t n, int32_t d);
+int wseg_pca_moments_f64(const float* rows, int64_t n, int32_t d, double* sum, double* gram, void* scratch, size_t scratch_bytes,
+                         void* stream);
+int wseg_pca_project_f64(const float* rows, int64_t n, int32_t d, const double* mean, const double* basis, int32_t r, double* out,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * k nearest neighbours of every query row among the corpus rows under banded dynamic time warping, and the warping distance of
  * a list of pairs: the warping-tolerant counterpart of wseg_knn_f32 over the patches above or any float32 rows.  A row is a
  * sequence of `steps` columns of `channels` values, time fastest: row[ch * steps + t].  whisperseg_amd/dtw.py::dtw_host is the

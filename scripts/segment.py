@@ -38,6 +38,13 @@ the rows of the archive: `embedding` float32 [rows, DIM], DIM 2 or 3 — the UMA
 GPU) of the fuzzy graph of the K (1 .. 64, default 15) nearest neighbours of every picture, with min_dist X (0 <= X < 1, default
 0.1) and the hash seed S (default 0): the same bits for the same rows on every run.  With --neighbors K of the same K the lists
 are computed once.
+--embed_init pca (needs --embed) starts the layout from the first DIM principal-component scores of the pictures instead of the
+hashed cloud (whisperseg_amd.embed.pca_start): the global arrangement of the call types then comes from the data; absent or `hash`,
+the archive is what it is without the flag.
+--pca R (needs --patches and --patches_save_path) adds the first R (1 .. 64, at most 80 W and rows - 1) principal components of the
+pictures (whisperseg_amd.pca; the second moments and the scores are computed on the GPU in float64): `pca_mean` float64 [80 W],
+`pca_components` float64 [R, 80 W], `pca_variance` and `pca_variance_ratio` float64 [R], `pca_scores` float32 [rows, R] in the
+archive's row order; with no row or a single one the arrays are empty ([0], [0, 80 W], [0], [0], [0, R]) and nothing runs.
 --pitch [--pitch_min_hz F] [--pitch_max_hz F] [--pitch_threshold X] appends seven pitch columns behind the measurement columns
 (whisperseg_amd.pitch.COLUMNS: mean, lowest, highest, first and last fundamental frequency of the row's YIN contour in Hz, the voiced
 fraction and the aperiodicity), tracked on the GPU in the samples the rows were cut from; F default to the widest range the
@@ -115,6 +122,10 @@ def build_parser():
     p.add_argument("--embed_neighbors", default=None, type=int, metavar="K", help="--embed: neighbours a row of the graph (1 .. 64, default 15)")
     p.add_argument("--embed_min_dist", default=None, type=float, metavar="X", help="--embed: UMAP's min_dist, 0 <= X < 1 (default 0.1)")
     p.add_argument("--embed_seed", default=None, type=int, metavar="S", help="--embed: the seed of the start and the negative samples (default 0)")
+    p.add_argument("--embed_init", default=None, choices=("hash", "pca"),
+                   help="--embed: the start of the layout — hash (default): the hashed cloud; pca: the first DIM principal-component scores")
+    p.add_argument("--pca", default=None, type=int, metavar="R",
+                   help="add the first R (1 .. 64) principal components of the saved pictures and their scores to --patches_save_path")
     p.add_argument("--pitch", action="store_true",
                    help="append the seven per-segment pitch columns (f0_mean .. aperiodicity) to every row")
     p.add_argument("--pitch_min_hz", default=None, type=float, metavar="F", help="--pitch: the lowest fundamental looked for (default 2 sr / n_fft)")
@@ -129,7 +140,8 @@ def parse_args(argv=None):
     without them, a K outside 1 .. 64, --neighbors_metric without --neighbors or --embed, --neighbors_band without the metric dtw or
     outside 0 .. W - 1, the metric dtw with more than 64 columns, a MIN_SIZE below 2, an S outside 1 .. 64 or --cluster_min_samples without --clusters are argparse
     errors; so are --embed without the patches, a DIM other than 2 or 3, --embed_neighbors outside 1 .. 64, --embed_min_dist outside
-    [0, 1), a negative --embed_seed and any of the three without --embed; and --pitch_min_hz, --pitch_max_hz, --pitch_threshold or
+    [0, 1), a negative --embed_seed and any of the three, or --embed_init, without --embed; --pca without the patches or with an R outside
+    1 .. min(64, 80 W); and --pitch_min_hz, --pitch_max_hz, --pitch_threshold or
     --pitch_save_path without --pitch, a frequency that is not positive, a range that is none, a threshold outside (0, 1) and a
     --pitch_save_path that does not end with .npz."""
     parser = build_parser()
@@ -168,7 +180,7 @@ def parse_args(argv=None):
         parser.error("--embed DIM needs --patches W and --patches_save_path FILE.npz")
     if args.embed is not None and args.embed not in (2, 3):
         parser.error("--embed must be 2 or 3 dimensions")
-    for name in ("embed_neighbors", "embed_min_dist", "embed_seed"):
+    for name in ("embed_neighbors", "embed_min_dist", "embed_seed", "embed_init"):
         if getattr(args, name) is not None and args.embed is None:
             parser.error(f"--{name} needs --embed DIM")
     if args.embed_neighbors is None:
@@ -183,6 +195,10 @@ def parse_args(argv=None):
         args.embed_seed = 0
     elif not 0 <= args.embed_seed < 2 ** 64:
         parser.error("--embed_seed must be 0 .. 2^64 - 1")
+    if args.pca is not None and args.patches is None:
+        parser.error("--pca R needs --patches W and --patches_save_path FILE.npz")
+    if args.pca is not None and not 1 <= args.pca <= min(64, 80 * args.patches):
+        parser.error("--pca must be 1 .. 64 components, and at most the 80 W columns of a picture")
     for name in ("pitch_min_hz", "pitch_max_hz", "pitch_threshold", "pitch_save_path"):
         if getattr(args, name) is not None and not args.pitch:
             parser.error(f"--{name} needs --pitch")
@@ -351,7 +367,11 @@ def main(argv=None):
             if dtw and not shared:                                   # the graph of the map is the warping distance's
                 lists, shared = patch_dtw_neighbors(tabled[0], args.embed_neighbors, args.neighbors_band), True
             archive.update(patch_embedding(tabled[0], args.embed_neighbors, args.embed, args.embed_min_dist, seed=args.embed_seed,
-                                           lists=(lists["neighbor_index"], lists["neighbor_distance"]) if shared else None))
+                                           lists=(lists["neighbor_index"], lists["neighbor_distance"]) if shared else None,
+                                           **({"init": "pca"} if args.embed_init == "pca" else {})))       # (absent or hash: the call as it was)
+        if args.pca is not None:
+            from whisperseg_amd.pca import patch_pca
+            archive.update(patch_pca(tabled[0], args.pca))       # more components than rows - 1: pca's ValueError says so
         np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()

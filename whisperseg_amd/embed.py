@@ -19,6 +19,7 @@ result is one function of its input: no races, no atomics, nothing that depends 
   negatives      sample s = 0 .. n_neg - 1 of the active entry e of row i in epoch t is the vertex
                  m = ((draw((t * nnz + e) * n_neg + s) >> 32) * N) >> 32; m == i is skipped and contributes nothing
   init           None: y0[i][c] = -10 + 20 * ((draw(2^63 + i * dim + c) >> 11) * 2^-53); or an array [N, dim], used as given
+                 (embed(init="pca") builds one from the first dim principal-component scores of the rows: pca_start)
   a term         delta = y_i - y_j per component; d2 = the left-to-right sum of delta_c * delta_c; P = d2 if b == 1.0 else
                  pow(d2, b) (numpy's float64 power)
                  attraction (j = indices[e]):   coef = ((-2 a) b P) / (d2 (1 + a P)), 0 where d2 == 0
@@ -38,6 +39,7 @@ numpy's differ by (tests/embed_cases.py derives the bound of one epoch).
 import numpy as np
 
 from . import neighbors as NB
+from . import pca as PC
 
 MAX_NEG = 16                           # negative samples of an active entry (csrc/wseg_embed_plan.h::kEmbedMaxNeg)
 MASK = (1 << 64) - 1
@@ -373,15 +375,41 @@ def check_embed(k, dim, min_dist, spread, epochs):
     return (k,) + curve_ab(min_dist, spread)
 
 
+def pca_start(scores, seed):
+    """float64 [N, dim]: the start of the layout from the first dim principal-component scores Z [N, dim] of the rows —
+    y0 = Z * (10 / max|Z|) + 1e-5 * init_positions(N, dim, seed): the scores scaled into [-10, 10], as the hashed start is, plus a
+    deterministic jitter, without which two identical rows would start at one point and, every term between them being 0 at
+    d2 == 0, could never separate.  Where max|Z| == 0 or N < 3 it is init_positions alone."""
+    z = np.array(scores, dtype=np.float64, ndmin=2)
+    n, dim = z.shape
+    top = float(np.abs(z).max(initial=0.0))
+    if n < 3 or top == 0.0:
+        return init_positions(n, dim, seed)
+    return z * (10.0 / top) + 1e-5 * init_positions(n, dim, seed)
+
+
+def check_init(init):
+    """`init` of embed / patch_embedding: None, the string "pca" or an array; ValueError for another string."""
+    if isinstance(init, str) and init != "pca":
+        raise ValueError(f'init must be None, "pca" or an array [N, dim] (got {init!r})')
+    return init
+
+
 def embed(rows, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", spread=1.0, n_neg=5, init=None, lists=None):
     """float32 [N, dim]: the map of the rows (float32 [N, D]: numpy, or a device tensor, searched where it lies) — the k nearest
     neighbours of every row (neighbors.neighbors), their fuzzy graph (fuzzy_graph_host), and `epochs` epochs of layout with
-    a, b = curve_ab(min_dist, spread).  `lists`: (index, distance) [N, k] where the caller already has them.  No rows: [0, dim];
-    one row: its start, for there is no edge."""
+    a, b = curve_ab(min_dist, spread).  `lists`: (index, distance) [N, k] where the caller already has them.  `init`: None (the hashed
+    start), an array [N, dim], or "pca": pca_start of the first dim principal-component scores of the rows (pca.pca, on the GPU).
+    No rows: [0, dim]; one row: its start, for there is no edge."""
     k, a, b = check_embed(k, dim, min_dist, spread, epochs)
+    from_pca = isinstance(check_init(init), str)
+    if from_pca:
+        init = None
     n = int(rows.shape[0]) if hasattr(rows, "shape") and len(rows.shape) == 2 else len(np.asarray(rows))
     nothing = (np.zeros(n + 1, np.int64), np.zeros(0, np.int32), np.zeros(0))
     Run(nothing, dim, int(epochs), None, n_neg, 1.0, 1.0, a, b, init, seed)          # every argument is checked before the search runs
+    if from_pca and n > dim:                                 # (N - 1 < dim rows have no dim components: the hashed start, which init=None is)
+        init = pca_start(PC.pca(rows, dim, device=device)["scores"], seed)
     if lists is not None:
         index, distance = np.asarray(lists[0]), np.asarray(lists[1])
         if index.shape != (n, k) or distance.shape != (n, k):
@@ -396,12 +424,13 @@ def embed(rows, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", sp
     return layout_epochs(run, device).cpu().numpy().astype(np.float32)
 
 
-def patch_embedding(predictions, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", lists=None):
+def patch_embedding(predictions, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", lists=None, init=None):
     """{"embedding": float32 [rows, dim]} of all the calls of `predictions` — what segment*(..., patches=W) returned, flattened as
     neighbors.patch_rows_of does: the rows of the CLI's CSV.  `lists`: the (neighbor_index, neighbor_distance) of patch_neighbors with
-    this k, where the caller has them."""
+    this k, where the caller has them.  `init`: as embed's."""
     check_embed(k, dim, min_dist, 1.0, epochs)
+    check_init(init)
     rows = NB.patch_rows_of(predictions)
     if not len(rows):
         return {"embedding": np.zeros((0, dim), np.float32)}
-    return {"embedding": embed(rows, k, dim, min_dist, epochs, seed, device, lists=lists)}
+    return {"embedding": embed(rows, k, dim, min_dist, epochs, seed, device, init=init, lists=lists)}
