@@ -39,6 +39,9 @@ VGPR_CAPS = {
     r"prompt_self_attn_kernel<": 64,
     r"dec_cross_attn_pk_kernel<": 128,
     r"layernorm_kernel<": 128,
+    r"::select_kernel<(true|false), 24, ": 128,                    # 2 workgroups of 8 waves per CU: 4 waves per SIMD (wseg_select.h)
+    r"::select_kernel<(true|false), 72, ": 156,                    # 1 workgroup per CU; no more than when kNN had a kernel of its own
+    r"(mst|dtw)_select_kernel<": 128,                              # 2 workgroups of 8 waves per CU
 }
 
 

@@ -15,8 +15,10 @@ band = 4, k = 15.  Reported per N:
     kernel holds the matrix-core loop AND the float32 sweep (a trace does not split a kernel), the finish kernel the float64 re-rank;
   * how many rows carry the same index set under the two distances.
 Once, on the first --host_rows rows: dtw_neighbors_host (numpy, one thread), wall time, and that the device's lists are its lists.
-One warm-up of each, then five repetitions; all five are printed, the median is the figure."""
+One warm-up of each, then five repetitions; all five are printed, the median is the figure.  Per N one more line: the SHA-256 of the
+index and distance arrays, so that two builds of the library (WSEG_LIB) can be held together bit for bit."""
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -70,7 +72,7 @@ def main():
     lines = [f"k nearest neighbours under DTW, self-search, C = {C}, T = {T}, band = {BAND}, k = {K}, patch-like rows ({torch.cuda.get_device_name(0)}; "
              f"warm-up, then {REPS} repetitions; times in ms; TFLOP/s = 2 N^2 T^2 C / time, peak {PEAK_TFLOPS})"]
     med = statistics.median
-    fmt = lambda v: " ".join(f"{t:.1f}" for t in v)
+    fmt = lambda v: " ".join(f"{t:.3f}" for t in v)
     for n in args.sizes:
         print(f"N {n} ...", flush=True)
         host = rows_of(n)
@@ -101,6 +103,7 @@ def main():
         lines.append(f"N {n}: {work / 1e12:.2f} TFLOP of column products, scratch {DW.scratch_bytes(n, n, C, T, K) / 2 ** 20:.1f} MiB")
         lines.append(f"  wseg_dtw_knn_f32 (HIP events)   median {med(t_dtw):9.1f}   [{fmt(t_dtw)}]   {rate(med(t_dtw)):6.1f} TFLOP/s, "
                      f"{100 * rate(med(t_dtw)) / PEAK_TFLOPS:.0f} % of the fp32 matrix peak")
+        lines.append(f"  sha256(index, distance) {hashlib.sha256(out_i.cpu().numpy().tobytes() + out_d.cpu().numpy().tobytes()).hexdigest()}")
         lines.append(f"  wseg_knn_f32, Euclidean         median {med(t_knn):9.1f}   [{fmt(t_knn)}]")
         lines.append(f"  the price of warping: {med(t_dtw) / med(t_knn):.1f}x;  rows with the same index set under both distances: {100 * same:.2f} %")
         trace = kernel_trace(warped)

@@ -2,9 +2,10 @@
 """What the nearest-neighbour search costs on one MI355X (whisperseg_amd.neighbors: wseg_knn_f32 on rows that are resident in HBM),
 against what a user would write today on the same GPU and, at the small size, on the host.  Not on the product path.
 
-    python tools/knn_bench.py [--sizes 10000 100000] [--out profiles/knn_ab.txt]
+    python tools/knn_bench.py [--sizes 10000 100000] [--k 15] [--device_only] [--out profiles/knn_ab.txt]
 
-Self-search over N random rows of D = 2 560 (a patch at W = 32) with values uniform in the patches' range [-1.5, 0.5], k = 15.
+Self-search over N random rows of D = 2 560 (a patch at W = 32) with values uniform in the patches' range [-1.5, 0.5], k = 15
+(--k 64 times the selection kernel with the long lists).
 Reported per N:
   * the kernels: HIP-event time around the one call that enqueues the norms, the selection and the finish kernel, rows resident and
     the outputs allocated — ms per call, and 2 N^2 D / time against the 157.3 TFLOP/s fp32 matrix peak (the norms and the exact
@@ -14,8 +15,11 @@ Reported per N:
   * at N <= 10 000 only, blocked numpy float32 on the host's threads (sgemm, argpartition, a sort of the k kept), wall time;
   * how many rows of the torch result carry the same index set as the kernels' (float32 |q|^2 + |x|^2 - 2 q.x against the exact
     re-rank: they may differ at the k-th boundary).
-One warm-up of each, then five repetitions; all five are printed, the median is the figure."""
+One warm-up of each, then five repetitions; all five are printed, the median is the figure.  Per N one more line: the SHA-256 of the
+kernels' index and distance arrays, so that two builds of the library (WSEG_LIB) can be held together bit for bit.  --device_only
+skips the torch and numpy baselines: the kernels' times and the digest alone."""
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -26,7 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-D, K, REPS = 2560, 15, 5
+D, REPS = 2560, 5
 PEAK_TFLOPS = 157.3                    # fp32 matrix (= vector) peak of an MI355X
 SCORE_BLOCK_BYTES = 1 << 30
 HOST_MAX_N = 10000
@@ -34,6 +38,14 @@ HOST_MAX_N = 10000
 
 def rows_of(n, seed=11):
     return np.random.default_rng([seed, n]).uniform(-1.5, 0.5, size=(n, D)).astype(np.float32)
+
+
+def digest(*tensors):
+    """SHA-256 over the bytes of device tensors, in order"""
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.cpu().numpy().tobytes())
+    return h.hexdigest()
 
 
 def torch_blocked(x, k):
@@ -71,8 +83,11 @@ def numpy_blocked(x, k):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[10000, 100000])
+    ap.add_argument("--k", type=int, default=15)
+    ap.add_argument("--device_only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "knn_ab.txt"))
     args = ap.parse_args()
+    K = args.k
     import torch
     from whisperseg_amd import _lib, neighbors as NB
     _lib.load(require_device=True)
@@ -95,23 +110,28 @@ def main():
 
         kernels = lambda: timed(lambda: NB.knn_rows(x, None, K, out_index=out_i, out_distance=out_d))
         baseline = lambda: timed(lambda: torch_blocked(x, K))
-        kernels(), baseline()                            # warm-up: code objects, the allocator, the BLAS library's choice
+        kernels()                                        # warm-up: code objects, the allocator, the BLAS library's choice
+        if not args.device_only:
+            baseline()
         t_kernel, t_torch = [], []
         for _ in range(REPS):
             ms, _ = kernels()
             t_kernel.append(ms)
-            ms, (base_i, _) = baseline()
-            t_torch.append(ms)
+            if not args.device_only:
+                ms, (base_i, _) = baseline()
+                t_torch.append(ms)
         med = statistics.median
-        fmt = lambda v: " ".join(f"{t:.1f}" for t in v)
+        fmt = lambda v: " ".join(f"{t:.3f}" for t in v)
         rate = lambda ms: 2.0 * n * n * D / (ms * 1e-3) / 1e12
-        same = (torch.sort(out_i.long(), dim=1).values == torch.sort(base_i, dim=1).values).all(dim=1).float().mean().item()
         lines.append(f"N {n}: {2.0 * n * n * D / 1e12:.2f} TFLOP of products, scratch {NB.scratch_bytes(n, n, D, K) / 2 ** 20:.1f} MiB")
         lines.append(f"  wseg_knn_f32 (HIP events)       median {med(t_kernel):9.1f}   [{fmt(t_kernel)}]   {rate(med(t_kernel)):6.1f} TFLOP/s, "
                      f"{100 * rate(med(t_kernel)) / PEAK_TFLOPS:.0f} % of the fp32 matrix peak")
-        lines.append(f"  blocked torch (addmm + topk)    median {med(t_torch):9.1f}   [{fmt(t_torch)}]   {rate(med(t_torch)):6.1f} TFLOP/s")
-        lines.append(f"  torch / kernels: {med(t_torch) / med(t_kernel):.2f}x;  rows with the same index set: {100 * same:.2f} %")
-        if n <= HOST_MAX_N:
+        lines.append(f"  sha256(index, distance) {digest(out_i, out_d)}")
+        if not args.device_only:
+            same = (torch.sort(out_i.long(), dim=1).values == torch.sort(base_i, dim=1).values).all(dim=1).float().mean().item()
+            lines.append(f"  blocked torch (addmm + topk)    median {med(t_torch):9.1f}   [{fmt(t_torch)}]   {rate(med(t_torch)):6.1f} TFLOP/s")
+            lines.append(f"  torch / kernels: {med(t_torch) / med(t_kernel):.2f}x;  rows with the same index set: {100 * same:.2f} %")
+        if n <= HOST_MAX_N and not args.device_only:
             numpy_blocked(host, K)
             t_host = []
             for _ in range(REPS):

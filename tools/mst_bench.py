@@ -3,7 +3,7 @@
 wseg_mst_round_f32 on rows that are resident in HBM), against the one nearest-neighbour pass it starts from and, at the small size,
 against HDBSCAN on the host.  Not on the product path.
 
-    python tools/mst_bench.py [--sizes 10000 100000] [--out profiles/mst_ab.txt]
+    python tools/mst_bench.py [--sizes 10000 100000] [--device_only] [--out profiles/mst_ab.txt]
 
 Self-search rows as in tools/knn_bench.py: N random rows of D = 2 560 (a patch at W = 32) with values uniform in the patches' range
 [-1.5, 0.5], min_samples s = 5.  Reported per N:
@@ -14,8 +14,11 @@ Self-search rows as in tools/knn_bench.py: N random rows of D = 2 560 (a patch a
   * the round count for CLUSTERED rows of the same size (20 centres, 0.3 * normal noise, as tests/knn_cases.py) — one run;
   * at N <= 10 000 only, sklearn.cluster.HDBSCAN(min_samples = s + 1: it counts the row itself) on the host's threads, wall time,
     and hdbscan_labels on the device's tree for the same rows (the host part that follows the tree).
-One warm-up, then five repetitions; all five are printed, the median is the figure."""
+One warm-up, then five repetitions; all five are printed, the median is the figure.  Per N one more line: the SHA-256 of the first
+round's index and weight arrays and of the tree's edges and weights, so that two builds of the library (WSEG_LIB) can be held
+together bit for bit.  --device_only skips the sklearn baseline and the host's labels."""
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -47,6 +50,7 @@ def clustered_rows_of(n, seed=12):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[10000, 100000])
+    ap.add_argument("--device_only", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mst_ab.txt"))
     args = ap.parse_args()
     import torch
@@ -55,7 +59,7 @@ def main():
     lines = [f"mutual-reachability minimum spanning tree, D = {D}, min_samples = {S}, uniform [-1.5, 0.5] rows ({torch.cuda.get_device_name(0)}; warm-up, "
              f"then {REPS} repetitions; times in ms; TFLOP/s = 2 N^2 D / time, peak {PEAK_TFLOPS})"]
     med = statistics.median
-    fmt = lambda v: " ".join(f"{t:.1f}" for t in v)
+    fmt = lambda v: " ".join(f"{t:.3f}" for t in v)
     for n in args.sizes:
         print(f"N {n} ...", flush=True)
         host = rows_of(n)
@@ -79,16 +83,20 @@ def main():
             scratch = torch.empty(LK.scratch_bytes(n, D), dtype=torch.uint8, device=rows.device)
             out_i = torch.empty((n,), dtype=torch.int32, device=rows.device)
             out_w = torch.empty((n,), dtype=torch.float32, device=rows.device)
-            round_ms = []
+            round_ms, sha = [], hashlib.sha256()
 
             def device_round(labels):
                 component = torch.from_numpy(labels.astype(np.int32)).to(rows.device)
                 ms, _ = timed(lambda: LK.mst_round(rows, core, component, out_i, out_w, scratch))
                 round_ms.append(ms)
-                return out_i.cpu().numpy(), out_w.cpu().numpy()
+                got = out_i.cpu().numpy(), out_w.cpu().numpy()
+                if len(round_ms) == 1:
+                    sha.update(got[0].tobytes() + got[1].tobytes())
+                return got
 
             edges, weight = LK.boruvka(n, device_round)
-            return knn_ms, round_ms, (time.perf_counter() - t0) * 1e3, edges, weight
+            sha.update(edges.tobytes() + weight.tobytes())
+            return knn_ms, round_ms, (time.perf_counter() - t0) * 1e3, edges, weight, sha.hexdigest()
 
         def public_call():
             torch.cuda.synchronize()
@@ -99,7 +107,7 @@ def main():
         one_tree(x), public_call()                       # warm-up: code objects, the allocator
         t_knn, t_round, t_rounds_all, t_wall, t_public = [], [], [], [], []
         for _ in range(REPS):
-            knn_ms, round_ms, wall, edges, weight = one_tree(x)
+            knn_ms, round_ms, wall, edges, weight, sha = one_tree(x)
             t_knn.append(knn_ms)
             t_round.append(med(round_ms))
             t_rounds_all.append(round_ms)
@@ -115,6 +123,7 @@ def main():
         lines.append(f"  wseg_mst_round_f32, a round (HIP events)   median {med(t_round):9.1f}   [{fmt(t_round)}]   {rate(med(t_round)):6.1f} TFLOP/s, "
                      f"{100 * rate(med(t_round)) / PEAK_TFLOPS:.0f} % of the fp32 matrix peak; round / knn pass: {med(t_round) / med(t_knn):.2f}x")
         lines.append(f"  the rounds one by one (medians)            [{fmt(per_round)}]")
+        lines.append(f"  sha256(first round's index, weight; edges, weight) {sha}")
         lines.append(f"  linkage.mst(), resident rows (wall)        median {med(t_public):9.1f}   [{fmt(t_public)}]   of which knn + rounds on the device "
                      f"{med(t_knn) + sum(per_round):.1f}")
         del x
@@ -126,7 +135,7 @@ def main():
         c_edges, c_weight = LK.mst(c, S, stats=stats)
         c_ms = (time.perf_counter() - t0) * 1e3
         lines.append(f"  clustered rows (20 centres + 0.3 noise)    {stats['rounds']} rounds, linkage.mst() {c_ms:.1f} (one run)")
-        if n <= HOST_MAX_N:
+        if n <= HOST_MAX_N and not args.device_only:
             from sklearn.cluster import HDBSCAN
             t0 = time.perf_counter()
             labels = LK.hdbscan_labels(edges, weight, n, MIN_CLUSTER)

@@ -468,6 +468,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// float <-> unsigned whose integer order is the float order (-inf first, +inf last): atomicMax / atomicMin on floats, and the high
+// word of a selection key (wseg_select.h)
+__device__ __forceinline__ uint32_t f2ord(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

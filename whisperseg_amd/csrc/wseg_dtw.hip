@@ -3,8 +3,10 @@
 // fastest: row[ch * T + t].  whisperseg_amd/dtw.py::dtw_host is the definition (numpy, float64): the local cost c(a, b) =
 // sum_ch (q[ch, a] - x[ch, b])^2 as one sequential chain in ch, G(a, b) = c(a, b) + min(G(a-1, b-1), G(a-1, b), G(a, b-1)) over the
 // cells |a - b| <= band, dtw = G(T-1, T-1); the neighbours come in the total order (dtw, index).  The m x n matrix of distances
-// never exists.  The host arithmetic — padding, tiles, splits, grids, scratch — is wseg_dtw_plan.h.  No inline assembly, no atomics.
-// The tile body is a copy of knn_select_kernel's (wseg_knn.hip stays as it is).
+// never exists.  The host arithmetic — padding, tiles, splits, grids, scratch — is wseg_dtw_plan.h.  The keys, the sorted lists, the
+// finish's merge and ranking, the fill kernel and the entry points' checks are wseg_select.h's.  dtw_select_kernel keeps a tile loop
+// of its own — sel_tile_product's with a column loader: over the shared function a call measured 3 % slower (DESIGN.md §8,
+// profiles/select_refactor_ab.txt), so this body stays the one that was measured.  No inline assembly, no atomics.
 //
 // dtw_norms_kernel    |column|^2 of every column of every query and corpus row as ONE channel-ordered fmaf chain (a lane a column).
 // dtw_select_kernel   every column is a row of dimension C.  A work item is one tile of 128 query columns — 4 sequences padded to 32
@@ -31,13 +33,11 @@
 //   (float32 of that distance, j) — the value it reports — and writes the first k; -1 / +inf where candidates ran out.  The
 //   selection's error therefore only matters at the boundary of the k + 8 kept candidates and never shows in a distance.
 // dtw_pairs_kernel    a wave per pair of a caller's list: dtw_pair_f64, reported as float32.
-#include "wseg_common.h"
 #include "wseg_dtw_plan.h"
+#include "wseg_select.h"
 
 namespace wseg {
 
-constexpr unsigned long long kDtwNone = ~0ull;       // the key of "no candidate": behind every real key
-constexpr int kDtwSelectLanes = 512;                 // dtw_select_kernel: 4 x 2 waves, a wave owns 32 query columns x 64 candidate columns
 constexpr int kDtwCostLd = kDtwTile + 2;             // floats between two rows of the costs in LDS
 
 struct DtwArgs {
@@ -55,11 +55,6 @@ struct DtwArgs {
   float* distance_out;             // [m][k]
 };
 
-__device__ __forceinline__ unsigned dtw_f2ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // |column|^2 of the columns of q then of x: acc = fmaf(v, v, acc) over ch ascending — the chain the MFMA runs on a product
 __global__ __launch_bounds__(256) void dtw_norms_kernel(DtwArgs a) {
   const long long qcols = a.m * a.T, cols = (a.m + a.n) * a.T;
@@ -76,19 +71,6 @@ __global__ __launch_bounds__(256) void dtw_norms_kernel(DtwArgs a) {
     }
     if (isq) a.qnorm[cc] = acc; else a.xnorm[cc] = acc;
   }
-}
-
-// the row's sorted list (ascending, L entries) takes `key` if it beats the worst entry
-__device__ __forceinline__ void dtw_insert(volatile unsigned long long* row, int L, unsigned long long key) {
-  if (key >= row[L - 1]) return;
-  int p = L - 1;
-  while (p > 0) {
-    const unsigned long long prev = row[p - 1];
-    if (prev <= key) break;
-    row[p] = prev;
-    --p;
-  }
-  row[p] = key;
 }
 
 // The recurrence as an anti-diagonal sweep over the costs `crow[b]` = c(a, b) of this lane's row a: at step s the lane holds cell
@@ -115,7 +97,7 @@ __device__ __forceinline__ F dtw_sweep(const F* crow, int a, int T, int band) {
 }
 
 template <int TP>
-__global__ __launch_bounds__(kDtwSelectLanes, 2) void dtw_select_kernel(DtwArgs a) {
+__global__ __launch_bounds__(kSelLanes, 2) void dtw_select_kernel(DtwArgs a) {
   constexpr int BK = 16, LD = kDtwTile + 4, TJ = 2, S = kDtwTile / TP;
   static_assert(2 * 2 * BK * LD <= kDtwTile * kDtwCostLd, "the slabs lie inside the costs");
   __shared__ float sbuf[kDtwTile * kDtwCostLd];          // the slabs of the channel loop, then the tile's costs
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(kDtwSelectLanes, 2) void dtw_select_kernel(DtwArgs 
     const long long qt = item / a.splits;
     const int split = (int)(item - qt * a.splits);
     const long long m0 = qt * S;
-    for (int idx = tid; idx < S * L; idx += kDtwSelectLanes) lists[idx] = kDtwNone;
+    for (int idx = tid; idx < S * L; idx += kSelLanes) lists[idx] = kSelNone;
     const int rseq = lrow / TP, rt = lrow % TP;
     const float qn = m0 + rseq < a.m && rt < T ? a.qnorm[(m0 + rseq) * T + rt] : 0.0f;
     const float* __restrict__ const qp = m0 + lseq < a.m && lt < T ? a.q + (m0 + lseq) * D + lt : nullptr;
@@ -187,13 +169,13 @@ __global__ __launch_bounds__(kDtwSelectLanes, 2) void dtw_select_kernel(DtwArgs 
         if (kt + 1 < nk) stage(b ^ 1);
         __syncthreads();
       }
-      // Register r of acc[j]: query column lrow, candidate column c = wn * 64 + 32 j + 8 (r >> 2) + 4 fk + (r & 3) of the tile.  The
+      // Register r of acc[j]: query column lrow, candidate column sel_candidate(wn, fk, j, r) of the tile.  The
       // slabs were read for the last time before the barrier above: the costs go over them.
 #pragma unroll
       for (int j = 0; j < TJ; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = wn * 64 + 32 * j + 8 * (r >> 2) + 4 * fk + (r & 3);
+          const int c = sel_candidate(wn, fk, j, r);
           sbuf[lrow * kDtwCostLd + c] = fmaf(-2.0f, acc[j][r], qn + sxn[c]);
         }
       __syncthreads();
@@ -206,13 +188,13 @@ __global__ __launch_bounds__(kDtwSelectLanes, 2) void dtw_select_kernel(DtwArgs 
         for (int c = 0; c < S; ++c) {
           const long long j = n0 + c;
           if (j < a.n && !(a.exclude && j == m0 + tid))
-            dtw_insert(lists + tid * L, L, ((unsigned long long)dtw_f2ord(sres[tid * S + c]) << 32) | (unsigned)j);
+            sel_insert(lists + tid * L, L, ((unsigned long long)f2ord(sres[tid * S + c]) << 32) | (unsigned)j);
         }
       }
       __syncthreads();                                   // the costs are read, the lists written: the next tile stages its first slab
     }
     if (t1 <= t0) __syncthreads();                       // (no tile: the cleared lists are written out)
-    for (int idx = tid; idx < S * L; idx += kDtwSelectLanes) {
+    for (int idx = tid; idx < S * L; idx += kSelLanes) {
       const int row = idx / L, e = idx - row * L;
       a.keys[((m0 + row) * a.splits + split) * L + e] = lists[idx];
     }
@@ -251,49 +233,16 @@ __global__ __launch_bounds__(64) void dtw_finish_kernel(DtwArgs a) {
   const long long D = (long long)a.C * a.T;
   const long long total = (long long)a.splits * L;
   for (long long row = blockIdx.x; row < a.m; row += gridDim.x) {
-    const unsigned long long* __restrict__ keys = a.keys + row * total;
-    // the L smallest keys of the splits' lists, ascending; keys are distinct but for "none"
-    unsigned long long prev = 0;
-    int cnt = 0;
-    for (int t = 0; t < L; ++t) {
-      unsigned long long best = kDtwNone;
-      for (long long i = lane; i < total; i += 64) {
-        const unsigned long long v = keys[i];
-        if ((t == 0 || v > prev) && v < best) best = v;
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o < best ? o : best;
-      }
-      if (best == kDtwNone) break;
-      if (lane == 0) sj[t] = (unsigned)best;
-      prev = best;
-      ++cnt;
-    }
+    const int cnt = sel_merge_split_lists(a.keys + row * total, total, L, lane, sj);
     __syncthreads();
     const float* __restrict__ q = a.q + row * D;
     for (int t = 0; t < cnt; ++t) {
       const unsigned j = sj[t];
       const double g = dtw_pair_f64(q, a.x + (long long)j * D, a.C, a.T, a.band, sc, lane);
-      if (lane == 0) sk[t] = ((unsigned long long)dtw_f2ord((float)g) << 32) | j;
+      if (lane == 0) sk[t] = sel_key((float)g, j);
     }
     __syncthreads();
-    // rank by (float32 distance, j): distinct keys, the ranks are a permutation
-    for (int t = lane; t < cnt; t += 64) {
-      const unsigned long long mine = sk[t];
-      int rank = 0;
-      for (int u = 0; u < cnt; ++u) rank += sk[u] < mine ? 1 : 0;
-      if (rank < a.k) {
-        const unsigned o = (unsigned)(mine >> 32);
-        a.index_out[row * a.k + rank] = (int)(unsigned)mine;
-        a.distance_out[row * a.k + rank] = __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-      }
-    }
-    for (int t = cnt + lane; t < a.k; t += 64) {
-      a.index_out[row * a.k + t] = -1;
-      a.distance_out[row * a.k + t] = __uint_as_float(0x7f800000u);
-    }
+    sel_rank_and_write(sk, cnt, a.k, lane, a.index_out + row * a.k, a.distance_out + row * a.k);
     __syncthreads();                                     // sj and sk are laid down anew
   }
 }
@@ -311,14 +260,6 @@ __global__ __launch_bounds__(64) void dtw_pairs_kernel(DtwArgs a, const int* __r
     }
     const double g = dtw_pair_f64(a.q + i * D, a.x + j * D, a.C, a.T, a.band, sc, lane);
     if (lane == 0) out[p] = (float)g;
-  }
-}
-
-// index = -1, distance = +inf over the m x k outputs: a call without candidates
-__global__ __launch_bounds__(256) void dtw_fill_kernel(int* __restrict__ index_out, float* __restrict__ distance_out, long long total) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    index_out[i] = -1;
-    distance_out[i] = __uint_as_float(0x7f800000u);
   }
 }
 
@@ -355,22 +296,15 @@ extern "C" int wseg_dtw_knn_f32(const float* queries, int64_t m, const float* co
   }
   if (exclude_same_index != 0 && exclude_same_index != 1) { set_error("%s: exclude_same_index must be 0 or 1", fn); return WSEG_ERR_INVALID; }
   if (m == 0) return WSEG_OK;
-  if (!queries || ((uintptr_t)queries & 3)) { set_error("%s: queries must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if ((n > 0 && !corpus) || ((uintptr_t)corpus & 3)) { set_error("%s: corpus must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!index_out || ((uintptr_t)index_out & 3)) { set_error("%s: index_out must be an int32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!distance_out || ((uintptr_t)distance_out & 3)) { set_error("%s: distance_out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
+  if (sel_bad_pointer(fn, queries, true, "queries", "a float32") || sel_bad_pointer(fn, corpus, n > 0, "corpus", "a float32") ||
+      sel_bad_pointer(fn, index_out, true, "index_out", "an int32") || sel_bad_pointer(fn, distance_out, true, "distance_out", "a float32"))
+    return WSEG_ERR_INVALID;
   if (n == 0) {
-    const long long total = (long long)m * k;
-    const long long rounds = (total + 255) / 256;
-    hipLaunchKernelGGL(dtw_fill_kernel, dim3((unsigned)(rounds < kDtwGridCap ? rounds : kDtwGridCap)), dim3(256), 0, stream, (int*)index_out,
-                       distance_out, total);
+    sel_launch_fill((int*)index_out, distance_out, (long long)m * k, stream);
     WSEG_LAUNCH_CHECK();
     return WSEG_OK;
   }
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)plan.scratch_bytes) {
-    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)plan.scratch_bytes, scratch_bytes);
-    return WSEG_ERR_INVALID;
-  }
+  if (sel_bad_scratch(fn, scratch, scratch_bytes, plan.scratch_bytes)) return WSEG_ERR_INVALID;
   DtwArgs a;
   a.q = queries;
   a.x = corpus;
@@ -393,7 +327,7 @@ extern "C" int wseg_dtw_knn_f32(const float* queries, int64_t m, const float* co
   a.distance_out = distance_out;
   hipLaunchKernelGGL(dtw_norms_kernel, dim3((unsigned)plan.norm_grid), dim3(256), 0, stream, a);
   WSEG_LAUNCH_CHECK();
-  const dim3 grid((unsigned)plan.grid), block(kDtwSelectLanes);
+  const dim3 grid((unsigned)plan.grid), block(kSelLanes);
   if (plan.padded == kDtwBlock) hipLaunchKernelGGL(dtw_select_kernel<kDtwBlock>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(dtw_select_kernel<2 * kDtwBlock>, grid, block, 0, stream, a);
   WSEG_LAUNCH_CHECK();
@@ -412,15 +346,13 @@ extern "C" int wseg_dtw_pairs_f64(const float* queries, int64_t m, const float* 
     set_error("%s: %s", fn, msg);
     return WSEG_ERR_INVALID;
   }
-  if (m < 0 || m > kDtwMaxRows) { set_error("%s: m must be 0 .. 2^31 - 1 (got %lld)", fn, (long long)m); return WSEG_ERR_INVALID; }
-  if (n < 0 || n > kDtwMaxRows) { set_error("%s: n must be 0 .. 2^31 - 1 (got %lld)", fn, (long long)n); return WSEG_ERR_INVALID; }
+  if (sel_check_rows("m", m, msg, sizeof(msg)) || sel_check_rows("n", n, msg, sizeof(msg))) { set_error("%s: %s", fn, msg); return WSEG_ERR_INVALID; }
   if (count < 0 || count > kDtwMaxRows) { set_error("%s: the pair count must be 0 .. 2^31 - 1 (got %lld)", fn, (long long)count); return WSEG_ERR_INVALID; }
   if (count == 0) return WSEG_OK;
   if (m == 0 || n == 0) { set_error("%s: pairs need rows on both sides (m %lld, n %lld)", fn, (long long)m, (long long)n); return WSEG_ERR_INVALID; }
-  if (!queries || ((uintptr_t)queries & 3)) { set_error("%s: queries must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!corpus || ((uintptr_t)corpus & 3)) { set_error("%s: corpus must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!pairs || ((uintptr_t)pairs & 3)) { set_error("%s: pairs must be an int32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!out || ((uintptr_t)out & 3)) { set_error("%s: out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
+  if (sel_bad_pointer(fn, queries, true, "queries", "a float32") || sel_bad_pointer(fn, corpus, true, "corpus", "a float32") ||
+      sel_bad_pointer(fn, pairs, true, "pairs", "an int32") || sel_bad_pointer(fn, out, true, "out", "a float32"))
+    return WSEG_ERR_INVALID;
   DtwArgs a = {};
   a.q = queries;
   a.x = corpus;

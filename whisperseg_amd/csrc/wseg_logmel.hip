@@ -20,14 +20,6 @@
 
 namespace wseg {
 
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 constexpr int LM_FB = 32;          // frames per workgroup of the fast path (one 128-byte output row segment per filter)
 constexpr int LM_CH = 8;           // bins per mel work item
 constexpr int LM_MAX_ITEMS = 256;  // mel work items (filters cut into <= LM_CH-bin chunks; <= (2 * 513 + 8 * 96) / 8 = 225 for 96 filters over 513 bins)

@@ -5,10 +5,12 @@
 // float64 direct form, strict total order (w, a, b)); linkage.py::mst drives the rounds and keeps the O(n) component bookkeeping on
 // the host; the host arithmetic — tiles, splits, grids, scratch — is wseg_mst_plan.h.  No inline assembly, no atomics.
 //
-// The 128 x 128 tile body is that of knn_select_kernel (wseg_knn.hip), kept here as a COPY: wseg_knn.hip is untouched, so its
-// kernels and their bits are the parent's (DESIGN.md §8 says why the body was not moved into a shared header).
+// The keys, the sorted lists, the norms kernel, the finish's merge and fp64 direct form and the entry points' checks are
+// wseg_select.h's.  mst_select_kernel keeps a tile loop of its own, the one wseg_select.h's select_kernel runs: instantiated from
+// the shared kernel a round measured 5 % slower (profiles/select_refactor_ab.txt), so this body stays the one that
+// was measured.
 //
-// mst_norms_kernel    |row|^2 of every row as ONE c-ordered fmaf chain (a lane per row) — as knn_norms_kernel.
+// select_norms_kernel |row|^2 of every row as ONE c-ordered fmaf chain (a lane per row).
 // mst_select_kernel   a work item is 128 rows against one split of the candidate tiles (128 candidates each); the grid strides over
 //   the items.  Per candidate tile the 128 x 128 dot products come from v_mfma_f32_32x32x2_f32, 4 x 2 waves of 32 rows x 64
 //   candidates (two accumulators) each, both operands streamed through LDS along d in slabs of 16 (double-buffered, the d tail and
@@ -17,22 +19,19 @@
 //       w^(i, j) = max(core_i, core_j, fmaf(-2, x_i . x_j, |x_i|^2 + |x_j|^2))
 //   has ONE value whatever the tiling, the grid, the split or the run.  Candidates of the row's own component (the row itself among
 //   them) and candidates behind n are masked.  Every row keeps a sorted list of the L = 1 + 8 smallest keys (ordered-uint w^ << 32 |
-//   j: one 64-bit compare is the total order (w^, j)) in LDS, inserted as in knn_select_kernel: keys are distinct and the order is
+//   j: one 64-bit compare is the total order (w^, j)) in LDS, inserted as in select_kernel: keys are distinct and the order is
 //   total, so the list does not depend on who came first.  Each (row, split) writes its list to scratch.
 //   LDS: 2 x 2 x 16 x 132 floats of slabs (33.0 KiB) + 3 x 128 words of the tile + 128 x 9 keys (9.0 KiB) = 43.5 KiB, two
 //   workgroups a CU at 128 registers (four waves a SIMD: the launch bounds).
 // mst_finish_kernel   a wave per row: merges the splits' lists into the L smallest keys, recomputes the DIRECT form sum (x_i - x_j)^2
-//   of those candidates with fp64 accumulation (lanes stride over c, one fixed xor tree — the lane striding of knn_finish_kernel;
-//   (a - b)^2 is symmetric, so d32(i, j) and d32(j, i) have the same bits), forms the exact w = max(core_i, core_j, float32 of that
-//   sum) and writes the first under (w, j); -1 / +inf where the row has no candidate.  The cancellation error of w^ therefore only
-//   decides WHICH nine candidates are looked at and never shows in a weight.
-#include "wseg_common.h"
+//   of those candidates with fp64 accumulation (sel_direct_sq_f64; (a - b)^2 is symmetric, so d32(i, j) and d32(j, i) have the same
+//   bits), forms the exact w = max(core_i, core_j, float32 of that sum) and writes the first under (w, j); -1 / +inf where the row
+//   has no candidate.  The cancellation error of w^ therefore only decides WHICH nine candidates are looked at and never shows in a
+//   weight.
 #include "wseg_mst_plan.h"
+#include "wseg_select.h"
 
 namespace wseg {
-
-constexpr unsigned long long kMstNone = ~0ull;       // the key of "no candidate": behind every real key
-constexpr int kMstSelectLanes = 512;                 // mst_select_kernel: 4 x 2 waves, a wave owns 32 rows x 64 candidates of a tile
 
 struct MstArgs {
   const float* x;                  // [n][d]
@@ -48,48 +47,8 @@ struct MstArgs {
   float* weight_out;               // [n]
 };
 
-__device__ __forceinline__ unsigned mst_f2ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float mst_ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-
-// |row|^2 of rows [0, n): acc = fmaf(v, v, acc) over c ascending — the chain the MFMA runs on a product
 template <bool VEC>
-__global__ __launch_bounds__(256) void mst_norms_kernel(MstArgs a) {
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < a.n; r += (long long)gridDim.x * 256) {
-    const float* __restrict__ p = a.x + r * a.d;
-    float acc = 0.0f;
-    if constexpr (VEC) {
-      for (int c = 0; c < a.d; c += 4) {
-        const float4 v = *(const float4*)(p + c);
-        acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
-      }
-    } else {
-      for (int c = 0; c < a.d; ++c) acc = fmaf(p[c], p[c], acc);
-    }
-    a.norm[r] = acc;
-  }
-}
-
-// the row's sorted list (ascending, kMstL entries) takes `key` if it beats the worst entry; volatile: other lanes of the workgroup
-// wrote the list a moment ago
-__device__ __forceinline__ void mst_insert(volatile unsigned long long* row, unsigned long long key) {
-  constexpr int L = kMstL;
-  if (key >= row[L - 1]) return;
-  int p = L - 1;
-  while (p > 0) {
-    const unsigned long long prev = row[p - 1];
-    if (prev <= key) break;
-    row[p] = prev;
-    --p;
-  }
-  row[p] = key;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs a) {
+__global__ __launch_bounds__(kSelLanes, 4) void mst_select_kernel(MstArgs a) {
   constexpr int BK = 16, LD = kMstTile + 4, TJ = 2, L = kMstL;
   __shared__ float sQ[2][BK][LD];
   __shared__ float sX[2][BK][LD];
@@ -121,7 +80,7 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
     const long long qt = item / a.splits;
     const int split = (int)(item - qt * a.splits);
     const long long m0 = qt * kMstTile;
-    for (int idx = tid; idx < kMstTile * L; idx += kMstSelectLanes) lists[idx] = kMstNone;
+    for (int idx = tid; idx < kMstTile * L; idx += kSelLanes) lists[idx] = kSelNone;
     const bool qok = m0 + lrow < a.n;
     const float qn = qok ? a.norm[m0 + lrow] : 0.0f;
     const float qc = qok ? a.core[m0 + lrow] : 0.0f;
@@ -163,7 +122,7 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
         if (kt + 1 < nk) stage(b ^ 1);
         __syncthreads();
       }
-      // Register r of acc[j]: row lrow, candidate c = wn * 64 + 32 j + 8 (r >> 2) + 4 fk + (r & 3) of the tile.  Value number
+      // Register r of acc[j]: row lrow, candidate sel_candidate(wn, fk, j, r) of the tile.  Value number
       // v = 16 j + r of the lane; `pass` marks those that may beat the row's worst entry (a float compare: a superset — the lists
       // only ever tighten, the insertion compares the keys).  The insertion loop exists once: it picks the marked values one by one.
       auto weight_of = [&](int c, float dot) {
@@ -172,7 +131,7 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
       const int nvalid = a.n - n0 < kMstTile ? (int)(a.n - n0) : kMstTile;
       // the worst entry's w^ (+inf while the list is not full)
       const unsigned wo = (unsigned)(mylist[L - 1] >> 32);
-      const float wf = wo == 0xffffffffu ? __uint_as_float(0x7f800000u) : mst_ord2f(wo);
+      const float wf = wo == 0xffffffffu ? sel_inf() : ord2f(wo);
       // (four neighbouring candidates at a time, one 16-byte LDS read per array; the scheduling barrier keeps the compiler from
       // fetching all 96 words ahead, which does not fit 128 registers beside the accumulators)
       unsigned pass = 0;
@@ -207,9 +166,8 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
                 for (int j = 0; j < TJ; ++j)
 #pragma unroll
                   for (int r = 0; r < 16; ++r) dot = v == 16 * j + r ? acc[j][r] : dot;
-                const int j = v >> 4, r = v & 15;
-                const int c = wn * 64 + 32 * j + 8 * (r >> 2) + 4 * fk + (r & 3);
-                mst_insert(mylist, ((unsigned long long)mst_f2ord(weight_of(c, dot)) << 32) | (unsigned)(n0 + c));
+                const int c = sel_candidate(wn, fk, v >> 4, v & 15);
+                sel_insert(mylist, L, ((unsigned long long)f2ord(weight_of(c, dot)) << 32) | (unsigned)(n0 + c));
               }
             }
             __builtin_amdgcn_wave_barrier();
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
       }
     }
     if (t1 <= t0) __syncthreads();                       // (no tile: the cleared lists are written out)
-    for (int idx = tid; idx < kMstTile * L; idx += kMstSelectLanes) {
+    for (int idx = tid; idx < kMstTile * L; idx += kSelLanes) {
       const int row = idx / L, e = idx - row * L;
       a.keys[((m0 + row) * a.splits + split) * L + e] = lists[idx];
     }
@@ -228,62 +186,24 @@ __global__ __launch_bounds__(kMstSelectLanes, 4) void mst_select_kernel(MstArgs 
 }
 
 __global__ __launch_bounds__(64) void mst_finish_kernel(MstArgs a, int vec) {
-  constexpr int L = kMstL;
-  __shared__ unsigned sj[L];
-  const int lane = threadIdx.x, D = a.d;
-  const long long total = (long long)a.splits * L;
+  __shared__ unsigned sj[kMstL];
+  const int lane = threadIdx.x;
+  const long long total = (long long)a.splits * kMstL;
   for (long long row = blockIdx.x; row < a.n; row += gridDim.x) {
-    const unsigned long long* __restrict__ keys = a.keys + row * total;
-    // the L smallest keys of the splits' lists, ascending; keys are distinct but for "none"
-    unsigned long long prev = 0;
-    int cnt = 0;
-    for (int t = 0; t < L; ++t) {
-      unsigned long long best = kMstNone;
-      for (long long i = lane; i < total; i += 64) {
-        const unsigned long long v = keys[i];
-        if ((t == 0 || v > prev) && v < best) best = v;
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o < best ? o : best;
-      }
-      if (best == kMstNone) break;
-      if (lane == 0) sj[t] = (unsigned)best;
-      prev = best;
-      ++cnt;
-    }
+    const int cnt = sel_merge_split_lists(a.keys + row * total, total, kMstL, lane, sj);
     __syncthreads();
     // the direct form with fp64 accumulation as float32, then the exact weight; the first under (w, j) — every lane holds it
-    const float* __restrict__ q = a.x + row * D;
     const float qc = a.core[row];
-    unsigned long long first = kMstNone;
+    unsigned long long first = kSelNone;
     for (int t = 0; t < cnt; ++t) {
       const unsigned j = sj[t];
-      const float* __restrict__ x = a.x + (long long)j * D;
-      double s = 0.0;
-      if (vec) {
-        for (int c = 4 * lane; c < D; c += 256) {
-          const float4 qv = *(const float4*)(q + c), xv = *(const float4*)(x + c);
-          const double d0 = (double)qv.x - (double)xv.x, d1 = (double)qv.y - (double)xv.y;
-          const double d2 = (double)qv.z - (double)xv.z, d3 = (double)qv.w - (double)xv.w;
-          s = fma(d0, d0, s); s = fma(d1, d1, s); s = fma(d2, d2, s); s = fma(d3, d3, s);
-        }
-      } else {
-        for (int c = lane; c < D; c += 64) {
-          const double df = (double)q[c] - (double)x[c];
-          s = fma(df, df, s);
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-      const float w = fmaxf(fmaxf(qc, a.core[j]), (float)s) + 0.0f;
-      const unsigned long long key = ((unsigned long long)mst_f2ord(w) << 32) | j;
+      const double s = sel_direct_sq_f64(a.x + row * a.d, a.x + (long long)j * a.d, a.d, vec, lane);
+      const unsigned long long key = sel_key(fmaxf(fmaxf(qc, a.core[j]), (float)s), j);
       first = key < first ? key : first;
     }
     if (lane == 0) {
       a.index_out[row] = cnt ? (int)(unsigned)first : -1;
-      a.weight_out[row] = cnt ? mst_ord2f((unsigned)(first >> 32)) : __uint_as_float(0x7f800000u);
+      a.weight_out[row] = cnt ? sel_key_value(first) : sel_inf();
     }
     __syncthreads();                                     // sj is laid down anew
   }
@@ -315,15 +235,10 @@ extern "C" int wseg_mst_round_f32(const float* rows, int64_t n, int32_t d, const
     return WSEG_ERR_INVALID;
   }
   if (n == 0) return WSEG_OK;
-  if (!rows || ((uintptr_t)rows & 3)) { set_error("%s: rows must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!core || ((uintptr_t)core & 3)) { set_error("%s: core must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!component || ((uintptr_t)component & 3)) { set_error("%s: component must be an int32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!index_out || ((uintptr_t)index_out & 3)) { set_error("%s: index_out must be an int32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!weight_out || ((uintptr_t)weight_out & 3)) { set_error("%s: weight_out must be a float32 device pointer", fn); return WSEG_ERR_INVALID; }
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < (size_t)plan.scratch_bytes) {
-    set_error("%s: scratch must be an 8-byte aligned device buffer of at least %lld bytes (got %zu)", fn, (long long)plan.scratch_bytes, scratch_bytes);
+  if (sel_bad_pointer(fn, rows, true, "rows", "a float32") || sel_bad_pointer(fn, core, true, "core", "a float32") ||
+      sel_bad_pointer(fn, component, true, "component", "an int32") || sel_bad_pointer(fn, index_out, true, "index_out", "an int32") ||
+      sel_bad_pointer(fn, weight_out, true, "weight_out", "a float32") || sel_bad_scratch(fn, scratch, scratch_bytes, plan.scratch_bytes))
     return WSEG_ERR_INVALID;
-  }
   MstArgs a;
   a.x = rows;
   a.n = n;
@@ -340,10 +255,13 @@ extern "C" int wseg_mst_round_f32(const float* rows, int64_t n, int32_t d, const
   a.weight_out = weight_out;
   // 16-byte loads where every row starts on 16 bytes
   const bool vec = d % 4 == 0 && !((uintptr_t)rows & 15);
-  if (vec) hipLaunchKernelGGL(mst_norms_kernel<true>, dim3((unsigned)plan.norm_grid), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(mst_norms_kernel<false>, dim3((unsigned)plan.norm_grid), dim3(256), 0, stream, a);
+  // (queries == corpus: the norms kernel's second operand is empty)
+  const dim3 ngrid((unsigned)plan.norm_grid), nblock(256);
+  const float* const none = nullptr;
+  if (vec) hipLaunchKernelGGL(select_norms_kernel<true>, ngrid, nblock, 0, stream, rows, (long long)n, none, 0ll, (int)d, a.norm, a.norm);
+  else hipLaunchKernelGGL(select_norms_kernel<false>, ngrid, nblock, 0, stream, rows, (long long)n, none, 0ll, (int)d, a.norm, a.norm);
   WSEG_LAUNCH_CHECK();
-  const dim3 grid((unsigned)plan.grid), block(kMstSelectLanes);
+  const dim3 grid((unsigned)plan.grid), block(kSelLanes);
   if (vec) hipLaunchKernelGGL(mst_select_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(mst_select_kernel<false>, grid, block, 0, stream, a);
   WSEG_LAUNCH_CHECK();

@@ -29,14 +29,6 @@ namespace wseg {
 constexpr int kPatchLanes = 256;
 constexpr int kPatchMaxFrames = kPatchFrameSlots / 256;      // 16: frames of an item at the smallest transform (n_fft 512)
 
-__device__ __forceinline__ uint32_t patch_f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float patch_ord2f(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 struct PatchArgs {
   wseg_logmel_desc d;              // hop and n_cols are not read
   const float* pcm;
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(kPatchLanes) void patch_frames_kernel(PatchArgs a) 
     if (tid < F && f_out[tid] >= 0) {
       float v = red[tid];
       for (int j = tid + F; j < kPatchLanes; j += F) v = fmaxf(v, red[j]);
-      atomicMax(&a.vmax[f_seg[tid]], patch_f2ord(v));
+      atomicMax(&a.vmax[f_seg[tid]], f2ord(v));
     }
     __syncthreads();                                 // the frame table, z, pw and red are laid down anew
   }
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(kPatchLanes) void patch_finish_kernel(const uint32_
     for (int u = 0; u < kPatchFinishPerGroup / kPatchLanes; ++u) {
       const long long idx = base + u * kPatchLanes + threadIdx.x;
       if (idx < total_values) {
-        const float floorv = patch_ord2f(vmax[idx / per_segment]) - 8.0f;
+        const float floorv = ord2f(vmax[idx / per_segment]) - 8.0f;
         out[idx] = (fmaxf(out[idx], floorv) + 4.0f) / 4.0f;
       }
     }
