@@ -63,9 +63,12 @@ import io
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
+from whisperseg_amd import dtw as DW, embed as EM, linkage as LK, neighbors as NB, pca as PC, resident as RS  # noqa: E402
 from whisperseg_amd.measure import COLUMNS as MEASURE_COLUMNS  # noqa: E402
 from whisperseg_amd.pitch import COLUMNS as PITCH_COLUMNS  # noqa: E402
 from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
@@ -256,12 +259,11 @@ def table(results, names=None, all_channels=False, measure=False, pitch=False):
     return columns, rows
 
 
-def patch_archive(results, names=None, all_channels=False, width=0):
-    """-> {name: array} of the .npz: `patch` [rows, 80, W] and the CSV's identifying columns, in table()'s row order."""
-    import numpy as np
+def identifying_columns(results, names=None, all_channels=False):
+    """-> {name: array} of the columns that say which row of the CSV a row of an archive is: `onset`, `offset`, `cluster` and, where
+    the CSV has them, `filename` / `channel`, in table()'s row order."""
     flat = [(i, channel, r) for i, res in enumerate(results) for channel, r in enumerate(res if all_channels else [res])]
-    out = {"patch": np.concatenate([r["patch"] for _, _, r in flat] or [np.zeros((0, 80, width), np.float32)], axis=0),
-           "onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
+    out = {"onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
            "offset": np.array([v for _, _, r in flat for v in r["offset"]], dtype=np.float64),
            "cluster": np.array([str(v) for _, _, r in flat for v in r["cluster"]], dtype=str)}
     if names is not None:
@@ -271,26 +273,57 @@ def patch_archive(results, names=None, all_channels=False, width=0):
     return out
 
 
+def patch_archive(results, names=None, all_channels=False, width=0):
+    """-> {name: array} of the .npz: `patch` [rows, 80, W] (neighbors.patch_pictures_of: the one statement of the row order) and the
+    CSV's identifying columns, in table()'s row order."""
+    return {"patch": NB.patch_pictures_of(results, none=(80, width)), **identifying_columns(results, names, all_channels)}
+
+
 def pitch_archive(results, names=None, all_channels=False):
     """-> {name: array} of the pitch .npz: the contours of all rows back to back, their offsets and the CSV's identifying columns,
     in table()'s row order."""
-    import numpy as np
-    flat = [(i, channel, r) for i, res in enumerate(results) for channel, r in enumerate(res if all_channels else [res])]
+    flat = [r for res in results for r in (res if all_channels else [res])]
 
     def joined(key, dtype):
-        return np.concatenate([np.asarray(a, dtype=dtype) for _, _, r in flat for a in r[key]] or [np.zeros(0, dtype)])
+        return np.concatenate([np.asarray(a, dtype=dtype) for r in flat for a in r[key]] or [np.zeros(0, dtype)])
 
-    counts = [len(a) for _, _, r in flat for a in r["f0_contour"]]
-    out = {"f0": joined("f0_contour", np.float32), "aperiodicity": joined("aperiodicity_contour", np.float32),
-           "frame_time": joined("frame_time", np.float64),
-           "frame_offsets": np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64),
-           "onset": np.array([v for _, _, r in flat for v in r["onset"]], dtype=np.float64),
-           "offset": np.array([v for _, _, r in flat for v in r["offset"]], dtype=np.float64),
-           "cluster": np.array([str(v) for _, _, r in flat for v in r["cluster"]], dtype=str)}
-    if names is not None:
-        out["filename"] = np.array([names[i] for i, _, r in flat for _ in r["onset"]], dtype=str)
-    if all_channels:
-        out["channel"] = np.array([channel for _, channel, r in flat for _ in r["onset"]], dtype=np.int64)
+    counts = [len(a) for r in flat for a in r["f0_contour"]]
+    return {"f0": joined("f0_contour", np.float32), "aperiodicity": joined("aperiodicity_contour", np.float32),
+            "frame_time": joined("frame_time", np.float64),
+            "frame_offsets": np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64),
+            **identifying_columns(results, names, all_channels)}
+
+
+def analyses(patch, args, device="cuda"):
+    """-> {name: array} of what --neighbors, --clusters, --embed and --pca add to the archive, in that order, for the archive's
+    pictures `patch` [rows, 80, W].  The pictures go to the device once and every analysis that was asked for searches that one
+    tensor where it lies; with --neighbors K of the map's K the lists are computed once."""
+    out = {}
+    if args.neighbors is None and args.clusters is None and args.embed is None and args.pca is None:
+        return out
+    pictures = RS.resident(patch, device)
+    dtw = args.neighbors_metric == "dtw"
+
+    def lists_of(k):
+        return DW.patch_dtw_neighbors(pictures, k, args.neighbors_band) if dtw else NB.patch_neighbors(pictures, k)
+
+    lists = None
+    if args.neighbors is not None:
+        lists = lists_of(args.neighbors)
+        out.update(lists)
+        if dtw:                                              # (absent: the archive as it was)
+            out.update(neighbor_metric=np.array("dtw"), neighbor_band=np.array(DW.check_band(args.neighbors_band, args.patches), dtype=np.int64))
+    if args.clusters is not None:
+        found = LK.patch_clusters(pictures, args.clusters, args.cluster_min_samples)
+        out.update(patch_cluster=found["cluster"], mst_edges=found["mst_edges"], mst_weight=found["mst_weight"])
+    if args.embed is not None:
+        if args.neighbors != args.embed_neighbors:           # (the same K: the lists are computed once)
+            lists = lists_of(args.embed_neighbors) if dtw else None      # the graph of the map is the warping distance's; else embed's own
+        out.update(EM.patch_embedding(pictures, args.embed_neighbors, args.embed, args.embed_min_dist, seed=args.embed_seed,
+                                      lists=None if lists is None else (lists["neighbor_index"], lists["neighbor_distance"]),
+                                      **({"init": "pca"} if args.embed_init == "pca" else {})))       # (absent or hash: the call as it was)
+    if args.pca is not None:
+        out.update(PC.patch_pca(pictures, args.pca))         # more components than rows - 1: pca's ValueError says so
     return out
 
 
@@ -343,35 +376,10 @@ def main(argv=None):
             tabled = ([segmenter.segment(audio, sr, **kwargs)], None, False)
     columns, rows = table(*tabled, measure=args.measure, pitch=args.pitch)
     if args.pitch_save_path is not None:
-        import numpy as np
         np.savez(args.pitch_save_path, **pitch_archive(*tabled))
     if args.patches is not None:
-        import numpy as np
         archive = patch_archive(*tabled, width=args.patches)
-        dtw = args.neighbors_metric == "dtw"
-        if dtw:
-            from whisperseg_amd.dtw import check_band, patch_dtw_neighbors
-        if args.neighbors is not None:
-            from whisperseg_amd.neighbors import patch_neighbors
-            lists = patch_dtw_neighbors(tabled[0], args.neighbors, args.neighbors_band) if dtw else patch_neighbors(tabled[0], args.neighbors)
-            archive.update(lists)
-            if dtw:                                              # (absent: the archive as it was)
-                archive.update(neighbor_metric=np.array("dtw"), neighbor_band=np.array(check_band(args.neighbors_band, args.patches), dtype=np.int64))
-        if args.clusters is not None:
-            from whisperseg_amd.linkage import patch_clusters
-            found = patch_clusters(tabled[0], args.clusters, args.cluster_min_samples)
-            archive.update(patch_cluster=found["cluster"], mst_edges=found["mst_edges"], mst_weight=found["mst_weight"])
-        if args.embed is not None:
-            from whisperseg_amd.embed import patch_embedding
-            shared = args.neighbors == args.embed_neighbors          # the same K: the lists are computed once
-            if dtw and not shared:                                   # the graph of the map is the warping distance's
-                lists, shared = patch_dtw_neighbors(tabled[0], args.embed_neighbors, args.neighbors_band), True
-            archive.update(patch_embedding(tabled[0], args.embed_neighbors, args.embed, args.embed_min_dist, seed=args.embed_seed,
-                                           lists=(lists["neighbor_index"], lists["neighbor_distance"]) if shared else None,
-                                           **({"init": "pca"} if args.embed_init == "pca" else {})))       # (absent or hash: the call as it was)
-        if args.pca is not None:
-            from whisperseg_amd.pca import patch_pca
-            archive.update(patch_pca(tabled[0], args.pca))       # more components than rows - 1: pca's ValueError says so
+        archive.update(analyses(archive["patch"], args))
         np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()

@@ -34,7 +34,7 @@ definition's to the last float32 bit and only candidates within 2 tau_i of the k
 """
 import numpy as np
 
-from . import neighbors as NB
+from . import _lib, neighbors as NB, resident as RS
 
 MAX_CHANNELS = 128                     # C (csrc/wseg_dtw_plan.h::kDtwMaxChannels)
 MAX_STEPS = 64                         # T (kDtwMaxSteps)
@@ -44,18 +44,14 @@ COST_BLOCK_BYTES = 2 << 20             # of those, the ones a chain over the cha
 
 def check_channels(channels):
     """`channels` as an int, ValueError unless it is an integer in 1 .. 128."""
-    if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or not 1 <= int(channels) <= MAX_CHANNELS:
-        raise ValueError(f"channels must be an integer in 1 .. {MAX_CHANNELS} (got {channels!r})")
-    return int(channels)
+    return RS.check_int(channels, "channels", 1, MAX_CHANNELS)
 
 
 def check_band(band, steps):
     """`band` as an int (None: max(1, T // 8) clipped to T - 1), ValueError unless it is an integer in 0 .. T - 1."""
     if band is None:
         return min(max(1, steps // 8), steps - 1)
-    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= int(band) <= steps - 1:
-        raise ValueError(f"band must be an integer in 0 .. T - 1 = {steps - 1} (got {band!r})")
-    return int(band)
+    return RS.check_int(band, "band", 0, steps - 1, f"in 0 .. T - 1 = {steps - 1}")
 
 
 def check_shapes(q_shape, x_shape, channels):
@@ -229,13 +225,7 @@ def dtw_neighbors_host(queries, corpus=None, k=15, channels=80, band=None):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(m, n, channels, steps, k):
     """wseg_dtw_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
     return _lib.size_or_raise(_lib.load().wseg_dtw_scratch_bytes(int(m), int(n), int(channels), int(steps), int(k)))
-
-
-def _device_rows(t):
-    import torch
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
 
 
 def dtw_knn_rows(queries, corpus=None, k=15, channels=80, band=None, out_index=None, out_distance=None):
@@ -243,42 +233,19 @@ def dtw_knn_rows(queries, corpus=None, k=15, channels=80, band=None, out_index=N
     the contiguous float32 device tensors `queries` [M, C T] and `corpus` [N, C T] (None: the queries, a row not its own neighbour).
     Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
     k = NB.check_k(k)
-    if not _device_rows(queries) or not (corpus is None or _device_rows(corpus)):
-        raise _lib.WsegError("dtw_knn_rows needs contiguous float32 device tensors [rows, D] (no CPU path)")
-    own = corpus is None
-    x = queries if own else corpus
-    if x.device != queries.device:
-        raise _lib.WsegError(f"the corpus is on {x.device}, the queries on {queries.device}")
+    x, own = NB.device_sides(queries, corpus, "dtw_knn_rows")
     m, n, c, t = check_shapes(queries.shape, x.shape, channels)
     band = check_band(band, t)
-    if out_index is None:
-        out_index = torch.empty((m, k), dtype=torch.int32, device=queries.device)
-    elif not (torch.is_tensor(out_index) and out_index.is_cuda and out_index.device == queries.device and out_index.dtype == torch.int32
-              and out_index.shape == (m, k) and out_index.is_contiguous()):
-        raise _lib.WsegError("out_index must be a contiguous int32 device tensor [M, k]")
-    if out_distance is None:
-        out_distance = torch.empty((m, k), dtype=torch.float32, device=queries.device)
-    elif not (torch.is_tensor(out_distance) and out_distance.is_cuda and out_distance.device == queries.device
-              and out_distance.dtype == torch.float32 and out_distance.shape == (m, k) and out_distance.is_contiguous()):
-        raise _lib.WsegError("out_distance must be a contiguous float32 device tensor [M, k]")
+    out_index, out_distance = NB.list_outputs(out_index, out_distance, m, k, queries.device)
     if m == 0:
         return out_index, out_distance
-    nbytes = scratch_bytes(m, n, c, t, k)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=queries.device)
+    scratch = RS.new_scratch(scratch_bytes(m, n, c, t, k), queries.device)
     with torch.cuda.device(queries.device):
         _lib.check(lib.wseg_dtw_knn_f32(queries.data_ptr(), m, x.data_ptr() if n else None, n, c, t, band, k, 1 if own else 0,
-                                        scratch.data_ptr(), nbytes, out_index.data_ptr(), out_distance.data_ptr(), _lib.stream_ptr()))
+                                        scratch.data_ptr(), scratch.numel(), out_index.data_ptr(), out_distance.data_ptr(), _lib.stream_ptr()))
     return out_index, out_distance
-
-
-def _resident(a, dev):
-    import torch
-    if torch.is_tensor(a):
-        return a.to(dtype=torch.float32).contiguous() if a.is_cuda else a.to(device=dev, dtype=torch.float32).contiguous()
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 
 
 def dtw_pairs(queries, corpus, pairs, channels, band=None, device="cuda"):
@@ -286,19 +253,14 @@ def dtw_pairs(queries, corpus, pairs, channels, band=None, device="cuda"):
     (uploaded to `device`) or device tensors; `pairs`: an integer array or tensor [P, 2] of (query row, corpus row).  ValueError
     for a pair outside the rows, before a launch."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not torch.is_tensor(queries):
-        queries = np.asarray(queries, dtype=np.float32)
-    if not (corpus is None or torch.is_tensor(corpus)):
-        corpus = np.asarray(corpus, dtype=np.float32)
-    m, n, c, t = check_shapes(tuple(queries.shape), tuple(queries.shape if corpus is None else corpus.shape), channels)
+    m, n, c, t = check_shapes(RS.shape_of(queries), RS.shape_of(queries if corpus is None else corpus), channels)
     band = check_band(band, t)
     pairs = check_pairs(pairs.cpu().numpy() if torch.is_tensor(pairs) else np.asarray(pairs), m, n)
     if not len(pairs):
         return np.zeros(0, np.float32)
-    q = _resident(queries, device)
-    x = q if corpus is None else _resident(corpus, q.device)
+    q = RS.resident(queries, device)
+    x = q if corpus is None else RS.resident(corpus, q.device)
     held = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(q.device)
     out = torch.empty(len(pairs), dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
@@ -311,31 +273,25 @@ def dtw_neighbors(queries, corpus=None, k=15, channels=80, band=None, device="cu
     """dtw_neighbors_host's lists, computed on the GPU -> (index int32 [M, k], distance float32 [M, k]) as numpy.  `queries`,
     `corpus`: numpy (uploaded to `device`) or device tensors, which are searched where they lie; only the two result arrays travel
     back."""
-    import torch
     k = NB.check_k(k)
-    if not torch.is_tensor(queries):
-        queries = np.asarray(queries, dtype=np.float32)
-    if not (corpus is None or torch.is_tensor(corpus)):
-        corpus = np.asarray(corpus, dtype=np.float32)
-    _, _, _, t = check_shapes(tuple(queries.shape), tuple(queries.shape if corpus is None else corpus.shape), channels)
+    _, _, _, t = check_shapes(RS.shape_of(queries), RS.shape_of(queries if corpus is None else corpus), channels)
     check_band(band, t)
-    q = _resident(queries, device)
-    x = None if corpus is None else _resident(corpus, q.device)
+    q = RS.resident(queries, device)
+    x = None if corpus is None else RS.resident(corpus, q.device)
     index, distance = dtw_knn_rows(q, x, k, channels, band)
     return index.cpu().numpy(), distance.cpu().numpy()
 
 
 def patch_dtw_neighbors(predictions, k, band=None, device="cuda"):
     """{"neighbor_index": int32 [rows, k], "neighbor_distance": float32 [rows, k]} of every call among all the calls of
-    `predictions` (see neighbors.patch_rows_of) under DTW over the pictures' columns, on the GPU; channels is the pictures' mel
-    count.  ValueError for pictures wider than 64 columns."""
+    `predictions` (see neighbors.patch_pictures_of: what segment* returned, or the pictures themselves) under DTW over the
+    pictures' columns, on the GPU; channels is the pictures' mel count.  ValueError for pictures wider than 64 columns."""
     k = NB.check_k(k)
-    rows = NB.patch_rows_of(predictions)
-    if not len(rows):
+    pictures = NB.patch_pictures_of(predictions)
+    rows, mels, width = (int(v) for v in pictures.shape)
+    if not rows:
         return {"neighbor_index": np.zeros((0, k), np.int32), "neighbor_distance": np.zeros((0, k), np.float32)}
-    flat = [r for res in predictions for r in (res if isinstance(res, (list, tuple)) else [res])]
-    mels, width = np.asarray(flat[0]["patch"]).shape[1:]
     if width > MAX_STEPS:
         raise ValueError(f"DTW takes pictures of up to {MAX_STEPS} columns (got W = {width})")
-    index, distance = dtw_neighbors(rows, None, k, int(mels), band, device=device)
+    index, distance = dtw_neighbors(pictures.reshape(rows, mels * width), None, k, mels, band, device=device)
     return {"neighbor_index": index, "neighbor_distance": distance}

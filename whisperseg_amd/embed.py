@@ -38,8 +38,7 @@ numpy's differ by (tests/embed_cases.py derives the bound of one epoch).
 """
 import numpy as np
 
-from . import neighbors as NB
-from . import pca as PC
+from . import _lib, neighbors as NB, pca as PC, resident as RS
 
 MAX_NEG = 16                           # negative samples of an active entry (csrc/wseg_embed_plan.h::kEmbedMaxNeg)
 MASK = (1 << 64) - 1
@@ -229,12 +228,16 @@ def scheduled(graph):
     return out, np.ascontiguousarray(indices[keep], dtype=np.int32), np.ascontiguousarray(rate[keep])
 
 
+def check_dim(dim):
+    """`dim` as an int, ValueError unless it is the integer 2 or 3."""
+    return RS.check_int(dim, "dim", 2, 3, "2 or 3")
+
+
 class Run:
     """The checked arguments of layout_host / layout: the scheduled CSR, the epochs (t0, t1) of T, the parameters and the start."""
 
     def __init__(self, graph, dim, epochs, total, n_neg, gamma, lr, a, b, init, seed):
-        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim not in (2, 3):
-            raise ValueError(f"dim must be 2 or 3 (got {dim!r})")
+        check_dim(dim)
         whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
         if isinstance(epochs, (tuple, list)):
             if len(epochs) != 2 or not all(whole(v) for v in epochs):
@@ -248,10 +251,8 @@ class Run:
             raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
         if not whole(total) or not 1 <= int(total) <= 2 ** 31 - 1 or not 0 <= t0 < t1 <= int(total):
             raise ValueError(f"epochs must be at least 1, and (t0, t1) must satisfy 0 <= t0 < t1 <= total (got {epochs!r} of {total!r})")
-        if not whole(n_neg) or not 0 <= int(n_neg) <= MAX_NEG:
-            raise ValueError(f"n_neg must be an integer in 0 .. {MAX_NEG} (got {n_neg!r})")
-        if not whole(seed) or not 0 <= int(seed) <= MASK:
-            raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1 (got {seed!r})")
+        RS.check_int(n_neg, "n_neg", 0, MAX_NEG)
+        RS.check_int(seed, "seed", 0, MASK, "in 0 .. 2^64 - 1")
         if (a is None) != (b is None):
             raise ValueError("give a and b together (curve_ab), or neither")
         if a is None:
@@ -332,14 +333,12 @@ def host_epochs(run):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(n, dim):
     """wseg_embed_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
     return _lib.size_or_raise(_lib.load().wseg_embed_scratch_bytes(int(n), int(dim)))
 
 
 def layout_epochs(run, device="cuda"):
     """The launches of a checked Run -> the positions as a DEVICE tensor float64 [N, dim].  Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
     dev = torch.device(device)
     indptr = torch.from_numpy(run.indptr).to(dev)
@@ -349,7 +348,7 @@ def layout_epochs(run, device="cuda"):
     y_out = torch.empty_like(y_in)
     if run.n == 0:
         return y_out
-    scratch = torch.empty(scratch_bytes(run.n, run.dim), dtype=torch.uint8, device=dev)
+    scratch = RS.new_scratch(scratch_bytes(run.n, run.dim), dev)
     with torch.cuda.device(dev):
         _lib.check(lib.wseg_embed_epochs_f64(indptr.data_ptr(), indices.data_ptr() if run.nnz else None, rate.data_ptr() if run.nnz else None,
                                              run.n, run.nnz, run.dim, y_in.data_ptr(), y_out.data_ptr(), scratch.data_ptr(), scratch.numel(),
@@ -368,10 +367,8 @@ def layout(graph, dim=2, epochs=200, total=None, n_neg=5, gamma=1.0, lr=1.0, a=N
 def check_embed(k, dim, min_dist, spread, epochs):
     """The checked arguments of embed / patch_embedding -> (k, a, b)."""
     k = NB.check_k(k)
-    if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or dim not in (2, 3):
-        raise ValueError(f"dim must be 2 or 3 (got {dim!r})")
-    if isinstance(epochs, bool) or not isinstance(epochs, (int, np.integer)) or not 1 <= int(epochs) <= 2 ** 31 - 1:
-        raise ValueError(f"epochs must be an integer of at least 1 (got {epochs!r})")
+    check_dim(dim)
+    RS.check_int(epochs, "epochs", 1, 2 ** 31 - 1, "of at least 1")
     return (k,) + curve_ab(min_dist, spread)
 
 
@@ -425,8 +422,8 @@ def embed(rows, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", sp
 
 
 def patch_embedding(predictions, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, device="cuda", lists=None, init=None):
-    """{"embedding": float32 [rows, dim]} of all the calls of `predictions` — what segment*(..., patches=W) returned, flattened as
-    neighbors.patch_rows_of does: the rows of the CLI's CSV.  `lists`: the (neighbor_index, neighbor_distance) of patch_neighbors with
+    """{"embedding": float32 [rows, dim]} of all the calls of `predictions` — what segment*(..., patches=W) returned, or the
+    pictures themselves (neighbors.patch_pictures_of): the rows of the CLI's CSV.  `lists`: the (neighbor_index, neighbor_distance) of patch_neighbors with
     this k, where the caller has them.  `init`: as embed's."""
     check_embed(k, dim, min_dist, 1.0, epochs)
     check_init(init)

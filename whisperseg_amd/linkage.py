@@ -24,11 +24,12 @@ float32, which is within tau = 2 (D + 4) 2^-24 * 2 max|x|^2 of w; it keeps 1 + 8
 edge and bit for bit; on other float rows it is a spanning tree whose every weight is the definition's w of that very edge to one
 float32 ulp and whose sorted weights lie within a derived slack of the definition's (tests/mst_cases.py).
 """
+import math
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import neighbors as NB
+from . import _lib, neighbors as NB, resident as RS
 
 MAX_SAMPLES = NB.MAX_K                 # min_samples: a core distance is a column of the nearest-neighbour search
 MAX_D = NB.MAX_D
@@ -40,9 +41,7 @@ HOST_THREADS = 8
 def check_samples(min_samples, n):
     """`min_samples` as an int; ValueError unless it is an integer in 1 .. min(64, n - 1)."""
     top = min(MAX_SAMPLES, n - 1)
-    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 1 <= int(min_samples) <= top:
-        raise ValueError(f"min_samples must be an integer in 1 .. min({MAX_SAMPLES}, N - 1) = {top} (got {min_samples!r})")
-    return int(min_samples)
+    return RS.check_int(min_samples, "min_samples", 1, top, f"in 1 .. min({MAX_SAMPLES}, N - 1) = {top}")
 
 
 def check_rows(shape):
@@ -149,7 +148,6 @@ def mst_of_weights(w):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(n, d):
     """wseg_mst_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
     return _lib.size_or_raise(_lib.load().wseg_mst_scratch_bytes(int(n), int(d)))
 
 
@@ -159,31 +157,18 @@ def mst_round(rows, core, component, out_index=None, out_weight=None, scratch=No
     candidate of another component that comes first in the order (w, j), and its weight; -1 / +inf where there is none.
     Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-
-    def device_tensor(t, dtype):
-        return torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
-
-    if not device_tensor(rows, torch.float32):
-        raise _lib.WsegError("mst_round needs a contiguous float32 device tensor [N, D] (no CPU path)")
+    RS.check_tensor(rows, "the rows of mst_round", "[N, D]")
     n, d = check_rows(rows.shape)
-    for name, t, dtype in (("core", core, torch.float32), ("component", component, torch.int32)):
-        if not (device_tensor(t, dtype) and t.device == rows.device and t.shape == (n,)):
-            raise _lib.WsegError(f"{name} must be a contiguous {str(dtype)[6:]} device tensor [N] on the rows' device")
-    if out_index is None:
-        out_index = torch.empty((n,), dtype=torch.int32, device=rows.device)
-    elif not (device_tensor(out_index, torch.int32) and out_index.device == rows.device and out_index.shape == (n,)):
-        raise _lib.WsegError("out_index must be a contiguous int32 device tensor [N]")
-    if out_weight is None:
-        out_weight = torch.empty((n,), dtype=torch.float32, device=rows.device)
-    elif not (device_tensor(out_weight, torch.float32) and out_weight.device == rows.device and out_weight.shape == (n,)):
-        raise _lib.WsegError("out_weight must be a contiguous float32 device tensor [N]")
+    RS.check_tensor(core, "core", "[N]", torch.float32, (n,), rows.device)
+    RS.check_tensor(component, "component", "[N]", torch.int32, (n,), rows.device)
+    out_index = RS.out_tensor(out_index, "out_index", "[N]", torch.int32, (n,), rows.device)
+    out_weight = RS.out_tensor(out_weight, "out_weight", "[N]", torch.float32, (n,), rows.device)
     if n == 0:
         return out_index, out_weight
     nbytes = scratch_bytes(n, d)
     if scratch is None:
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)
+        scratch = RS.new_scratch(nbytes, rows.device)
     with torch.cuda.device(rows.device):
         _lib.check(lib.wseg_mst_round_f32(rows.data_ptr(), n, d, core.data_ptr(), component.data_ptr(), scratch.data_ptr(), scratch.numel(),
                                           out_index.data_ptr(), out_weight.data_ptr(), _lib.stream_ptr()))
@@ -210,20 +195,15 @@ def mst(rows, min_samples=5, device="cuda", stats=None):
     in (w, a, b).  `rows`: numpy (uploaded to `device` once) or a device tensor, which is searched where it lies; per round only the
     two result vectors travel back and the new components up.  `stats`: a dict that receives {"rounds": the rounds taken}."""
     import torch
-    if not torch.is_tensor(rows):
-        rows = np.asarray(rows, dtype=np.float32)
-    n, d = check_rows(tuple(rows.shape))
+    n, d = check_rows(RS.shape_of(rows))
     if n < 2:
         if stats is not None:
             stats["rounds"] = 0
         return empty_tree()
     s = check_samples(min_samples, n)
-    if torch.is_tensor(rows):
-        x = rows.to(dtype=torch.float32).contiguous() if rows.is_cuda else rows.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        x = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float32)).to(device)
+    x = RS.resident(rows, device)
     core = NB.knn_rows(x, None, s)[1][:, s - 1].contiguous()
-    scratch = torch.empty(scratch_bytes(n, d), dtype=torch.uint8, device=x.device)
+    scratch = RS.new_scratch(scratch_bytes(n, d), x.device)
     out_index = torch.empty((n,), dtype=torch.int32, device=x.device)
     out_weight = torch.empty((n,), dtype=torch.float32, device=x.device)
 
@@ -268,8 +248,7 @@ def boruvka(n, round_of, stats=None):
 # ---- from the tree to labels (host) ------------------------------------------------------------------------------------------------
 def check_tree(edges, weight, n):
     edges, weight = np.asarray(edges), np.asarray(weight)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
-        raise ValueError(f"n must be a non-negative integer (got {n!r})")
+    n = RS.check_int(n, "n", 0, math.inf, "of at least 0")
     if edges.ndim != 2 or edges.shape[1] != 2 or weight.shape != (len(edges),) or len(edges) != max(int(n) - 1, 0):
         raise ValueError(f"a tree of {n} rows has edges [N - 1, 2] and weight [N - 1] (got {edges.shape} and {weight.shape})")
     if len(edges) and (edges.min() < 0 or edges.max() >= n):
@@ -278,9 +257,7 @@ def check_tree(edges, weight, n):
 
 
 def check_size(min_cluster_size, least):
-    if isinstance(min_cluster_size, bool) or not isinstance(min_cluster_size, (int, np.integer)) or min_cluster_size < least:
-        raise ValueError(f"min_cluster_size must be an integer >= {least} (got {min_cluster_size!r})")
-    return int(min_cluster_size)
+    return RS.check_int(min_cluster_size, "min_cluster_size", least, math.inf, f">= {least}")
 
 
 def by_smallest_row(group, keep):
@@ -401,15 +378,14 @@ def hdbscan_labels(edges, weight, n, min_cluster_size):
 
 def patch_clusters(predictions, min_cluster_size, min_samples=5, device="cuda"):
     """{"cluster": int32 [rows] (hdbscan_labels; -1: noise), "mst_edges": int32 [rows - 1, 2], "mst_weight": float32 [rows - 1]} of
-    all the calls of `predictions` — what segment*(..., patches=W) returned, flattened as neighbors.patch_rows_of does: the rows of
-    the CLI's CSV — with the tree built on the GPU.  min_samples is lowered to rows - 1 where there are fewer rows."""
+    all the calls of `predictions` — what segment*(..., patches=W) returned, or the pictures themselves
+    (neighbors.patch_pictures_of): the rows of the CLI's CSV — with the tree built on the GPU.  min_samples is lowered to rows - 1 where there are fewer rows."""
     mcs = check_size(min_cluster_size, 2)
-    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or not 1 <= int(min_samples) <= MAX_SAMPLES:
-        raise ValueError(f"min_samples must be an integer in 1 .. {MAX_SAMPLES} (got {min_samples!r})")
+    min_samples = RS.check_int(min_samples, "min_samples", 1, MAX_SAMPLES)
     rows = NB.patch_rows_of(predictions)
     n = len(rows)
     if n < 2:
         edges, weight = empty_tree()
         return {"cluster": np.full(n, -1, dtype=np.int32), "mst_edges": edges, "mst_weight": weight}
-    edges, weight = mst(rows, min(int(min_samples), n - 1), device=device)
+    edges, weight = mst(rows, min(min_samples, n - 1), device=device)
     return {"cluster": hdbscan_labels(edges, weight, n, mcs), "mst_edges": edges, "mst_weight": weight}

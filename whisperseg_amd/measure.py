@@ -28,9 +28,9 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, resident as RS
 from .audio_utils import get_n_fft_given_sr
-from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch, sample_bounds  # noqa: F401 (bounds_of, sample_bounds: re-exported)
+from .segments import bounds_of, device_pcm, sample_bounds  # noqa: F401 (bounds_of, sample_bounds: re-exported)
 
 COLUMNS = ("peak_amplitude", "rms", "zero_crossing_rate", "peak_frequency", "centroid_frequency", "freq_05", "freq_95",
            "spectral_entropy")
@@ -174,12 +174,12 @@ def measure_rows(pcm, bounds, n_fft, k_lo, k_hi, out=None):
     `bounds` [n_seg, 2] (host) in the device tensor `pcm` (float32 [n], contiguous).  Stream-ordered, no host synchronisation."""
     import torch
     lib = _lib.load(require_device=True)
-    check_pcm(pcm, "measure_rows")
+    RS.check_tensor(pcm, "the recording of measure_rows", "[n]", ndim=1)
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg = len(bounds)
-    out = check_out(out, (n_seg, 8), "[n_seg, 8]", pcm.device)
+    out = RS.out_tensor(out, "out", "[n_seg, 8]", torch.float32, (n_seg, 8), pcm.device)
     window, twiddle = _device_tables(n_fft, pcm.device)
-    scratch = new_scratch(scratch_bytes(bounds, n_fft), pcm.device)
+    scratch = RS.new_scratch(scratch_bytes(bounds, n_fft), pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_measure_segments_f32(pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
                                                  bounds.ctypes.data_as(C.c_void_p), n_seg, int(n_fft), int(k_lo), int(k_hi),

@@ -24,9 +24,9 @@ tau_i = 2 (D + 4) 2^-24 (|q_i|^2 + max_j |x_j|^2) of d(i, j); it keeps k + 8 can
 fp64 accumulation, so a reported distance is the definition's to the last float32 bit or the next and only candidates within
 2 tau_i of the k-th distance can be exchanged (tests/knn_cases.py).
 """
-import ctypes as C
-
 import numpy as np
+
+from . import _lib, resident as RS
 
 MAX_K = 64                             # neighbours per row (csrc/wseg_knn_plan.h::kKnnMaxK)
 MAX_D = 20480                          # columns: 80 x 256, the widest patch (kKnnMaxD)
@@ -35,9 +35,7 @@ HOST_BLOCK_BYTES = 128 << 20           # float64 differences neighbors_host hold
 
 def check_k(k):
     """`k` as an int, ValueError unless it is an integer in 1 .. 64."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
-        raise ValueError(f"k must be an integer in 1 .. {MAX_K} (got {k!r})")
-    return int(k)
+    return RS.check_int(k, "k", 1, MAX_K)
 
 
 def check_shapes(q_shape, x_shape):
@@ -91,8 +89,26 @@ def neighbors_host(queries, corpus=None, k=15):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(m, n, d, k):
     """wseg_knn_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
     return _lib.size_or_raise(_lib.load().wseg_knn_scratch_bytes(int(m), int(n), int(d), int(k)))
+
+
+def device_sides(queries, corpus, who):
+    """(x, own) of the launch function `who`: the corpus, and whether it is the queries themselves (None).  WsegError unless both
+    sides are contiguous float32 device tensors on one device."""
+    RS.check_tensor(queries, f"the queries of {who}", "[M, D]")
+    if corpus is None:
+        return queries, True
+    RS.check_tensor(corpus, f"the corpus of {who}", "[N, D]")
+    if corpus.device != queries.device:
+        raise _lib.WsegError(f"the corpus is on {corpus.device}, the queries on {queries.device}")
+    return corpus, False
+
+
+def list_outputs(out_index, out_distance, m, k, device):
+    """(index int32 [M, k], distance float32 [M, k]) on `device`: the arguments where given (checked), new tensors where None."""
+    import torch
+    return (RS.out_tensor(out_index, "out_index", "[M, k]", torch.int32, (m, k), device),
+            RS.out_tensor(out_distance, "out_distance", "[M, k]", torch.float32, (m, k), device))
 
 
 def knn_rows(queries, corpus=None, k=15, out_index=None, out_distance=None):
@@ -100,85 +116,69 @@ def knn_rows(queries, corpus=None, k=15, out_index=None, out_distance=None):
     the contiguous float32 device tensors `queries` [M, D] and `corpus` [N, D] (None: the queries, a row not its own neighbour).
     Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
     k = check_k(k)
-
-    def device_rows(t):
-        return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-
-    if not device_rows(queries) or not (corpus is None or device_rows(corpus)):
-        raise _lib.WsegError("knn_rows needs contiguous float32 device tensors [rows, D] (no CPU path)")
-    own = corpus is None
-    x = queries if own else corpus
-    if x.device != queries.device:
-        raise _lib.WsegError(f"the corpus is on {x.device}, the queries on {queries.device}")
+    x, own = device_sides(queries, corpus, "knn_rows")
     m, n, d = check_shapes(queries.shape, x.shape)
-    if out_index is None:
-        out_index = torch.empty((m, k), dtype=torch.int32, device=queries.device)
-    elif not (torch.is_tensor(out_index) and out_index.is_cuda and out_index.device == queries.device and out_index.dtype == torch.int32
-              and out_index.shape == (m, k) and out_index.is_contiguous()):
-        raise _lib.WsegError("out_index must be a contiguous int32 device tensor [M, k]")
-    if out_distance is None:
-        out_distance = torch.empty((m, k), dtype=torch.float32, device=queries.device)
-    elif not (torch.is_tensor(out_distance) and out_distance.is_cuda and out_distance.device == queries.device
-              and out_distance.dtype == torch.float32 and out_distance.shape == (m, k) and out_distance.is_contiguous()):
-        raise _lib.WsegError("out_distance must be a contiguous float32 device tensor [M, k]")
+    out_index, out_distance = list_outputs(out_index, out_distance, m, k, queries.device)
     if m == 0:
         return out_index, out_distance
-    nbytes = scratch_bytes(m, n, d, k)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=queries.device)
+    scratch = RS.new_scratch(scratch_bytes(m, n, d, k), queries.device)
     with torch.cuda.device(queries.device):
-        _lib.check(lib.wseg_knn_f32(queries.data_ptr(), m, x.data_ptr() if n else None, n, d, k, 1 if own else 0, scratch.data_ptr(), nbytes,
-                                    out_index.data_ptr(), out_distance.data_ptr(), _lib.stream_ptr()))
+        _lib.check(lib.wseg_knn_f32(queries.data_ptr(), m, x.data_ptr() if n else None, n, d, k, 1 if own else 0, scratch.data_ptr(),
+                                    scratch.numel(), out_index.data_ptr(), out_distance.data_ptr(), _lib.stream_ptr()))
     return out_index, out_distance
 
 
 def neighbors(queries, corpus=None, k=15, device="cuda"):
     """neighbors_host's lists, computed on the GPU -> (index int32 [M, k], distance float32 [M, k]) as numpy.  `queries`, `corpus`:
     numpy (uploaded to `device`) or device tensors, which are searched where they lie; only the two result arrays travel back."""
-    import torch
     k = check_k(k)
-
-    def resident(a, dev):
-        if torch.is_tensor(a):
-            return a.to(dtype=torch.float32).contiguous() if a.is_cuda else a.to(device=dev, dtype=torch.float32).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-    if not torch.is_tensor(queries):
-        queries = np.asarray(queries, dtype=np.float32)
-    if not (corpus is None or torch.is_tensor(corpus)):
-        corpus = np.asarray(corpus, dtype=np.float32)
-    check_shapes(tuple(queries.shape), tuple(queries.shape if corpus is None else corpus.shape))
-    q = resident(queries, device)
-    x = None if corpus is None else resident(corpus, q.device)
+    check_shapes(RS.shape_of(queries), RS.shape_of(queries if corpus is None else corpus))
+    q = RS.resident(queries, device)
+    x = None if corpus is None else RS.resident(corpus, q.device)
     index, distance = knn_rows(q, x, k)
     return index.cpu().numpy(), distance.cpu().numpy()
 
 
-def patch_rows_of(predictions):
-    """float32 [rows, 80 * W]: the pictures of `predictions` — a list of prediction dicts carrying "patch", or of per-channel lists of
-    them as segment_files(channel_id="all") returns — flattened in the row order of scripts/segment.py::patch_archive (file, channel,
-    row).  ValueError for a dict without "patch" or pictures of different sizes."""
+def patch_pictures_of(predictions, none=(0, 0)):
+    """[rows, n_mels, W]: the pictures of `predictions`, in THE row order of everything that is computed from them and of the CLI's
+    archive and CSV: file, channel, row.  `predictions` is what segment*(..., patches=W) returned — a list of prediction dicts
+    carrying "patch", or of per-channel lists of them as segment_files(channel_id="all") returns: float32 numpy, concatenated once —
+    or the pictures themselves, a numpy array (as float32) or a tensor [rows, n_mels, W], which is returned as it is: a device
+    tensor stays where it lies.  `none`: (n_mels, W) of the result where there is no prediction to read them from.  ValueError for a
+    dict without "patch" or pictures of different sizes."""
+    if hasattr(predictions, "shape"):
+        pictures = predictions if not isinstance(predictions, np.ndarray) else np.ascontiguousarray(predictions, dtype=np.float32)
+        if len(pictures.shape) != 3:
+            raise ValueError(f'the pictures must be [rows, n_mels, W] (got {tuple(pictures.shape)})')
+        return pictures
     flat = [r for res in predictions for r in (res if isinstance(res, (list, tuple)) else [res])]
-    rows = []
+    pictures = []
     for r in flat:
         if not isinstance(r, dict) or "patch" not in r:
             raise ValueError('every prediction must carry "patch": call segment*(..., patches=W)')
         p = np.asarray(r["patch"], dtype=np.float32)
         if p.ndim != 3:
             raise ValueError(f'"patch" must be [rows, n_mels, W] (got {p.shape})')
-        rows.append(p.reshape(len(p), p.shape[1] * p.shape[2]))
-    if len({p.shape[1] for p in rows}) > 1:
+        pictures.append(p)
+    if len({p.shape[1:] for p in pictures}) > 1:
         raise ValueError("the predictions carry patches of different sizes")
-    if not rows:
-        return np.zeros((0, 0), np.float32)
-    return np.ascontiguousarray(np.concatenate(rows, axis=0))
+    if not pictures:
+        return np.zeros((0,) + tuple(none), np.float32)
+    return np.ascontiguousarray(np.concatenate(pictures, axis=0))
+
+
+def patch_rows_of(predictions):
+    """[rows, n_mels * W]: patch_pictures_of, every picture as one row — the 2-D view of it."""
+    pictures = patch_pictures_of(predictions)
+    return pictures.reshape(pictures.shape[0], pictures.shape[1] * pictures.shape[2])
 
 
 def patch_neighbors(predictions, k, device="cuda"):
     """{"neighbor_index": int32 [rows, k], "neighbor_distance": float32 [rows, k]} of every call among all the calls of
-    `predictions` (see patch_rows_of), on the GPU; indices count rows of that flattened order — the rows of the CLI's CSV."""
+    `predictions` (see patch_pictures_of: what segment* returned, or the pictures themselves), on the GPU; indices count rows of that
+    order — the rows of the CLI's CSV."""
     k = check_k(k)
     rows = patch_rows_of(predictions)
     if not len(rows):

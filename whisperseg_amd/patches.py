@@ -25,9 +25,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, measure as M
+from . import _lib, measure as M, resident as RS
 from .audio_utils import N_MELS, get_n_fft_given_sr, slaney_mel_filters
-from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch
+from .segments import bounds_of, device_pcm
 
 MAX_WIDTH = 256                        # columns of a patch (csrc/wseg_patch_plan.h::kPatchMaxWidth)
 PATCH_BLOCK_BYTES = 256 << 20          # device output `patches` holds at a time: the rows go through in blocks of at most this
@@ -35,9 +35,7 @@ PATCH_BLOCK_BYTES = 256 << 20          # device output `patches` holds at a time
 
 def check_width(width):
     """`width` as an int, ValueError unless it is an integer in 1 .. 256."""
-    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= int(width) <= MAX_WIDTH:
-        raise ValueError(f"width must be an integer in 1 .. {MAX_WIDTH} (got {width!r})")
-    return int(width)
+    return RS.check_int(width, "width", 1, MAX_WIDTH)
 
 
 def filterbank(sr, n_fft, min_frequency=0, max_frequency=None):
@@ -123,14 +121,14 @@ def patch_rows(pcm, bounds, tables, width, out=None):
     host synchronisation."""
     import torch
     lib = _lib.load(require_device=True)
-    check_pcm(pcm, "patch_rows")
+    RS.check_tensor(pcm, "the recording of patch_rows", "[n]", ndim=1)
     if tables.window.device != pcm.device:
         raise _lib.WsegError(f"the tables are on {tables.window.device}, the recording on {pcm.device}")
     width = check_width(width)
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg, n_mels = len(bounds), int(tables.desc.n_mels)
-    out = check_out(out, (n_seg, n_mels, width), "[n_seg, n_mels, width]", pcm.device)
-    scratch = new_scratch(scratch_bytes(n_seg, n_mels, width), pcm.device)
+    out = RS.out_tensor(out, "out", "[n_seg, n_mels, width]", torch.float32, (n_seg, n_mels, width), pcm.device)
+    scratch = RS.new_scratch(scratch_bytes(n_seg, n_mels, width), pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_patches_f32(C.byref(tables.desc), pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
                                         bounds.ctypes.data_as(C.c_void_p), n_seg, width, scratch.data_ptr(), scratch.numel(),

@@ -37,7 +37,7 @@ import math
 
 import numpy as np
 
-from . import neighbors as NB
+from . import _lib, neighbors as NB, resident as RS
 
 MAX_D = 8192                           # columns (csrc/wseg_pca_plan.h::kPcaMaxD)
 MAX_R = 64                             # components (kPcaMaxR)
@@ -60,9 +60,7 @@ def check_shape(shape):
 def check_r(r, n, d):
     """`r` as an int, ValueError unless it is an integer in 1 .. min(64, D, N - 1)."""
     top = min(MAX_R, d, n - 1)
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= top:
-        raise ValueError(f"r must be an integer in 1 .. min({MAX_R}, D, N - 1) = {top} (got {r!r})")
-    return int(r)
+    return RS.check_int(r, "r", 1, top, f"in 1 .. min({MAX_R}, D, N - 1) = {top}")
 
 
 # ---- the definition (host) -----------------------------------------------------------------------------------------------------------
@@ -161,33 +159,21 @@ def pca_host(rows, r, scores=True):
 # ---- the device path ---------------------------------------------------------------------------------------------------------------
 def scratch_bytes(n, d):
     """wseg_pca_scratch_bytes (host arithmetic, no device); WsegError for invalid input."""
-    from . import _lib
     return _lib.size_or_raise(_lib.load().wseg_pca_scratch_bytes(int(n), int(d)))
-
-
-def _resident(rows, device):
-    """The rows as a contiguous float32 device tensor: numpy is uploaded to `device`, a device tensor is used where it lies."""
-    import torch
-    if torch.is_tensor(rows):
-        return rows.to(dtype=torch.float32).contiguous() if rows.is_cuda else rows.to(device=device, dtype=torch.float32).contiguous()
-    return torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float32)).to(device)
 
 
 def moments_rows(x):
     """The launches: (s float64 [D], S float64 [D, D]) as DEVICE tensors for the contiguous float32 device tensor `x` [N, D].
     Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
-        raise _lib.WsegError("moments_rows needs a contiguous float32 device tensor [N, D] (no CPU path)")
+    RS.check_tensor(x, "the rows of moments_rows", "[N, D]")
     n, d = check_shape(x.shape)
     s = torch.empty(d, dtype=torch.float64, device=x.device)
     gram = torch.empty((d, d), dtype=torch.float64, device=x.device)
-    nbytes = scratch_bytes(n, d)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    scratch = RS.new_scratch(scratch_bytes(n, d), x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.wseg_pca_moments_f64(x.data_ptr(), n, d, s.data_ptr(), gram.data_ptr(), scratch.data_ptr(), nbytes, _lib.stream_ptr()))
+        _lib.check(lib.wseg_pca_moments_f64(x.data_ptr(), n, d, s.data_ptr(), gram.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.stream_ptr()))
     return s, gram
 
 
@@ -195,10 +181,8 @@ def project_rows(x, mean, basis):
     """The launch: the scores float64 [N, r] as a DEVICE tensor for the contiguous float32 device tensor `x` [N, D] and the float64
     mean [D] and basis [D, r] (numpy, uploaded).  Stream-ordered, no host synchronisation."""
     import torch
-    from . import _lib
     lib = _lib.load(require_device=True)
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
-        raise _lib.WsegError("project_rows needs a contiguous float32 device tensor [N, D] (no CPU path)")
+    RS.check_tensor(x, "the rows of project_rows", "[N, D]")
     mean, basis = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(basis, dtype=np.float64)
     n, d, r = check_project(x.shape, mean.shape, basis.shape)
     out = torch.empty((n, r), dtype=torch.float64, device=x.device)
@@ -210,30 +194,25 @@ def project_rows(x, mean, basis):
     return out
 
 
-def _shape_of(rows):
-    import torch
-    return tuple(rows.shape) if torch.is_tensor(rows) else np.asarray(rows).shape
-
-
 def moments(rows, device="cuda"):
     """moments_host's (s, S), computed on the GPU, as numpy.  `rows`: numpy (uploaded to `device`) or a device tensor."""
-    check_shape(_shape_of(rows))
-    s, gram = moments_rows(_resident(rows, device))
+    check_shape(RS.shape_of(rows))
+    s, gram = moments_rows(RS.resident(rows, device))
     return s.cpu().numpy(), gram.cpu().numpy()
 
 
 def project(rows, mean, basis, device="cuda"):
     """project_host's scores float64 [N, r], computed on the GPU, as numpy."""
-    check_project(_shape_of(rows), np.shape(mean), np.shape(basis))
-    return project_rows(_resident(rows, device), mean, basis).cpu().numpy()
+    check_project(RS.shape_of(rows), np.shape(mean), np.shape(basis))
+    return project_rows(RS.resident(rows, device), mean, basis).cpu().numpy()
 
 
 def pca(rows, r, device="cuda", scores=True):
     """pca_host's dict with the moments and the scores computed on the GPU: the rows go up once (or are used where they lie), the
     D x D moments come back for the host decomposition, the basis goes up and the scores come back."""
-    n, d = check_shape(_shape_of(rows))
+    n, d = check_shape(RS.shape_of(rows))
     r = check_r(r, n, d)
-    x = _resident(rows, device)
+    x = RS.resident(rows, device)
     s, gram = moments_rows(x)
     out = pca_from_moments(s.cpu().numpy(), gram.cpu().numpy(), n, r)
     if scores:
@@ -250,11 +229,10 @@ def empty_result(d, r, prefix=""):
 
 def patch_pca(predictions, r, device="cuda"):
     """{"pca_mean", "pca_components", "pca_variance", "pca_variance_ratio", "pca_scores"} of all the calls of `predictions` — what
-    segment*(..., patches=W) returned, flattened as neighbors.patch_rows_of does: the rows of the CLI's CSV.  No rows or a single
-    one: empty arrays with the right trailing shapes, and nothing runs."""
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= MAX_R:
-        raise ValueError(f"r must be an integer in 1 .. {MAX_R} (got {r!r})")
+    segment*(..., patches=W) returned, or the pictures themselves (neighbors.patch_pictures_of): the rows of the CLI's CSV.  No rows
+    or a single one: empty arrays with the right trailing shapes, and nothing runs."""
+    r = RS.check_int(r, "r", 1, MAX_R)
     rows = NB.patch_rows_of(predictions)
     if len(rows) < 2:
-        return empty_result(rows.shape[1], int(r), "pca_")
-    return {"pca_" + key: value for key, value in pca(rows, int(r), device=device).items()}
+        return empty_result(int(rows.shape[1]), r, "pca_")
+    return {"pca_" + key: value for key, value in pca(rows, r, device=device).items()}

@@ -37,9 +37,9 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, resident as RS
 from .audio_utils import get_n_fft_given_sr
-from .segments import bounds_of, check_out, check_pcm, device_pcm, new_scratch
+from .segments import bounds_of, device_pcm
 
 COLUMNS = ("f0_mean", "f0_min", "f0_max", "f0_first", "f0_last", "voiced_fraction", "aperiodicity")
 CONTOUR_KEYS = ("f0_contour", "aperiodicity_contour", "frame_time")
@@ -317,14 +317,14 @@ def pitch_rows(pcm, bounds, tau_min, tau_max, hop, threshold=0.1, out=None):
     `bounds` [n_seg, 2] (host) in the device tensor `pcm` (float32 [n], contiguous).  Stream-ordered, no host synchronisation."""
     import torch
     lib = _lib.load(require_device=True)
-    check_pcm(pcm, "pitch_rows")
+    RS.check_tensor(pcm, "the recording of pitch_rows", "[n]", ndim=1)
     bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1, 2)
     n_seg = len(bounds)
     nbytes = scratch_bytes(bounds, tau_max, hop)      # (validates bounds, tau_max and hop: the frame counts below are then defined)
     offsets = frame_offsets_of(bounds, int(tau_max), int(hop))
     total = int(offsets[-1])
-    out = check_out(out, (total, 3), "[total_frames, 3]", pcm.device)
-    scratch = new_scratch(nbytes, pcm.device)
+    out = RS.out_tensor(out, "out", "[total_frames, 3]", torch.float32, (total, 3), pcm.device)
+    scratch = RS.new_scratch(nbytes, pcm.device)
     with torch.cuda.device(pcm.device):
         _lib.check(lib.wseg_pitch_frames_f64(pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
                                              bounds.ctypes.data_as(C.c_void_p), n_seg, int(tau_min), int(tau_max), int(hop),

@@ -1,10 +1,11 @@
-"""What the per-segment analyses of a recording's resident PCM share on the Python side (measure.py, patches.py, pitch.py): a row's
-sample range, the recording's way to the device, and the argument checks and scratch of their `*_rows` launch functions."""
+"""What the per-segment analyses of a recording's resident PCM share on the Python side (measure.py, patches.py, pitch.py) that is about
+segments: a row's sample range and the recording's way to the device.  The argument checks, the outputs and the scratch of their
+`*_rows` launch functions are resident.py's, as they are of every other analysis."""
 import math
 
 import numpy as np
 
-from . import _lib
+from . import resident as RS
 
 
 def sample_bounds(onset, offset, sr, n):
@@ -21,34 +22,8 @@ def bounds_of(prediction, sr, n):
 
 
 def device_pcm(audio, device):
-    """numpy [n] (uploaded to `device`) or a tensor (a device tensor stays where it lies) -> contiguous float32 device tensor [n]."""
-    import torch
-    if torch.is_tensor(audio):
-        pcm = audio.to(dtype=torch.float32).contiguous() if audio.is_cuda else audio.to(device=device, dtype=torch.float32).contiguous()
-    else:
-        pcm = torch.as_tensor(np.ascontiguousarray(audio, dtype=np.float32)).to(device)
+    """resident.resident of one mono recording [n]; ValueError for another rank."""
+    pcm = RS.resident(audio, device)
     if pcm.dim() != 1:
         raise ValueError("audio must be one mono recording [n]")
     return pcm
-
-
-def check_pcm(pcm, who):
-    """WsegError unless `pcm` is what the launch function `who` takes: a contiguous float32 device tensor [n]."""
-    import torch
-    if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype == torch.float32 and pcm.dim() == 1 and pcm.is_contiguous()):
-        raise _lib.WsegError(f"{who} needs a contiguous float32 device tensor [n] (no CPU path)")
-
-
-def check_out(out, shape, what, device):
-    """`out` (WsegError unless it is a contiguous float32 device tensor of `shape`, `what` in words), or a new one on `device`."""
-    import torch
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if not (out.is_cuda and out.dtype == torch.float32 and out.shape == tuple(shape) and out.is_contiguous()):
-        raise _lib.WsegError(f"out must be a contiguous float32 device tensor {what}")
-    return out
-
-
-def new_scratch(nbytes, device):
-    import torch
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
