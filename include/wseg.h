@@ -343,6 +343,25 @@ int wseg_embed_epochs_f64(const int64_t* indptr, const int32_t* indices, const u
                           const double* y_in, double* y_out, void* scratch, size_t scratch_bytes, int64_t t0, int64_t t1,
                           int64_t total_epochs, double lr, double a, double b, double gamma, int32_t n_neg, uint64_t seed,
                           void* stream);
+/* Placing NEW rows on a frozen map (the layout step of a UMAP transform): whisperseg_amd/embed.py::place_host is the definition and
+ * embed.py::place the caller.  (indptr, indices, rate) is a CSR over the m new rows whose entries name CORPUS vertices 0 .. n - 1
+ * (a row: at most 64 entries, nearest first); corpus: device float64 [n][dim], the frozen positions, only read; key: device uint64
+ * [m], one per new row.  ONE launch runs the epochs t0 .. t1 - 1 of total_epochs, a lane per new row: in epoch t row i moves by
+ * lr (1 - t / total_epochs) G_i, G_i the sum IN ROW ORDER over its entries q that are active in epoch t (the schedule above) of the
+ * attraction term towards corpus[indices] and then the repulsion terms of the n_neg corpus vertices
+ * ((mix(key[i] + ((t * 64 + q) * 16 + s)) >> 32) * n) >> 32, s = 0 .. n_neg - 1 — mix is splitmix64's finaliser; none is skipped.
+ * A new row reads the corpus and itself only, so its result is a function of its own row, key and start: not of the other rows of
+ * the call, their order or their number, nor of the grid.  With b == 1 every coordinate has the definition's bits.
+ * m 0 .. 2^31 - 1 (m == 0 returns 0 without a launch), n 1 .. 2^31 - 1 where m > 0, nnz, dim, the epochs, n_neg and the parameters
+ * as above.  An entry whose index is outside 0 .. n - 1 contributes nothing but keeps its position q, a row reaches no further than
+ * 0 .. nnz and its entries past the 64th contribute nothing, so nothing outside the inputs is read whatever they hold.  y_in, y_out:
+ * device float64 [m][dim]; y_out must overlap none of the inputs.  No scratch.  Every argument is validated on the host before the
+ * launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * Added without moving WSEG_ABI_VERSION (an addition). */
+int wseg_embed_place_f64(const int64_t* indptr, const int32_t* indices, const uint32_t* rate, const uint64_t* key,
+                         int64_t m, int64_t nnz, const double* corpus, int64_t n, int32_t dim,
+                         const double* y_in, double* y_out, int64_t t0, int64_t t1, int64_t total_epochs,
+                         double lr, double a, double b, double gamma, int32_t n_neg, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Principal components of float32 rows: the two heavy steps of whisperseg_amd/pca.py on the fp64 matrix cores

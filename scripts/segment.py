@@ -45,6 +45,14 @@ the archive is what it is without the flag.
 pictures (whisperseg_amd.pca; the second moments and the scores are computed on the GPU in float64): `pca_mean` float64 [80 W],
 `pca_components` float64 [R, 80 W], `pca_variance` and `pca_variance_ratio` float64 [R], `pca_scores` float32 [rows, R] in the
 archive's row order; with no row or a single one the arrays are empty ([0], [0, 80 W], [0], [0], [0, R]) and nothing runs.
+--onto LIBRARY.npz [--embed_neighbors K] [--embed_min_dist X] [--embed_seed S] [--cluster_min_samples S] (needs --patches W and
+--patches_save_path, W the library's; excludes --clusters, --embed and --pca) reads an archive an earlier run wrote as a LIBRARY
+and expresses this run's rows in it (whisperseg_amd.library.patch_onto; nothing of the library moves, and a row's values do not
+depend on the other rows of the run): `library_index` int32 [rows, K] and `library_distance` float32 [rows, K], the K (default 15)
+nearest library rows of every row; `patch_cluster` int32 [rows], the library's call type or -1, if the library was made with
+--clusters; `embedding` float32 [rows, DIM], the row on the library's map, if it was made with --embed; `pca_scores` float32
+[rows, R] on the library's axes, if it was made with --pca.  X, the seed S and the min_samples S mean what they meant when the
+library was made: give the values it was made with.
 --pitch [--pitch_min_hz F] [--pitch_max_hz F] [--pitch_threshold X] appends seven pitch columns behind the measurement columns
 (whisperseg_amd.pitch.COLUMNS: mean, lowest, highest, first and last fundamental frequency of the row's YIN contour in Hz, the voiced
 fraction and the aperiodicity), tracked on the GPU in the samples the rows were cut from; F default to the widest range the
@@ -68,7 +76,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-level shim, as upstream imports it)
-from whisperseg_amd import dtw as DW, embed as EM, linkage as LK, neighbors as NB, pca as PC, resident as RS  # noqa: E402
+from whisperseg_amd import dtw as DW, embed as EM, library as LB, linkage as LK, neighbors as NB, pca as PC, resident as RS  # noqa: E402
 from whisperseg_amd.measure import COLUMNS as MEASURE_COLUMNS  # noqa: E402
 from whisperseg_amd.pitch import COLUMNS as PITCH_COLUMNS  # noqa: E402
 from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
@@ -129,6 +137,9 @@ def build_parser():
                    help="--embed: the start of the layout — hash (default): the hashed cloud; pca: the first DIM principal-component scores")
     p.add_argument("--pca", default=None, type=int, metavar="R",
                    help="add the first R (1 .. 64) principal components of the saved pictures and their scores to --patches_save_path")
+    p.add_argument("--onto", default=None, metavar="LIBRARY.npz",
+                   help="express the saved pictures in an earlier archive's call types, map and principal axes (adds library_index, "
+                        "library_distance and, for what the library holds, patch_cluster, embedding, pca_scores to --patches_save_path)")
     p.add_argument("--pitch", action="store_true",
                    help="append the seven per-segment pitch columns (f0_mean .. aperiodicity) to every row")
     p.add_argument("--pitch_min_hz", default=None, type=float, metavar="F", help="--pitch: the lowest fundamental looked for (default 2 sr / n_fft)")
@@ -146,9 +157,19 @@ def parse_args(argv=None):
     [0, 1), a negative --embed_seed and any of the three, or --embed_init, without --embed; --pca without the patches or with an R outside
     1 .. min(64, 80 W); and --pitch_min_hz, --pitch_max_hz, --pitch_threshold or
     --pitch_save_path without --pitch, a frequency that is not positive, a range that is none, a threshold outside (0, 1) and a
-    --pitch_save_path that does not end with .npz."""
+    --pitch_save_path that does not end with .npz.  --onto without the patches, with --clusters, --embed or --pca, or with a
+    LIBRARY that does not end with .npz is one too; with --onto, --embed_neighbors, --embed_min_dist, --embed_seed and
+    --cluster_min_samples need no --embed / --clusters."""
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.onto is not None:
+        if args.patches is None:
+            parser.error("--onto LIBRARY.npz needs --patches W and --patches_save_path FILE.npz")
+        for name in ("clusters", "embed", "pca"):
+            if getattr(args, name) is not None:
+                parser.error(f"--onto LIBRARY.npz excludes --{name}: the library's own are used")
+        if not args.onto.endswith(".npz"):
+            parser.error("--onto must name a .npz archive")
     if (args.patches is None) != (args.patches_save_path is None):
         parser.error("--patches W and --patches_save_path FILE.npz need each other")
     if args.patches is not None and not 1 <= args.patches <= 256:
@@ -173,7 +194,7 @@ def parse_args(argv=None):
         parser.error("--clusters MIN_SIZE needs --patches W and --patches_save_path FILE.npz")
     if args.clusters is not None and args.clusters < 2:
         parser.error("--clusters must be at least 2 rows")
-    if args.cluster_min_samples is not None and args.clusters is None:
+    if args.cluster_min_samples is not None and args.clusters is None and args.onto is None:
         parser.error("--cluster_min_samples S needs --clusters MIN_SIZE")
     if args.cluster_min_samples is None:
         args.cluster_min_samples = 5
@@ -184,7 +205,7 @@ def parse_args(argv=None):
     if args.embed is not None and args.embed not in (2, 3):
         parser.error("--embed must be 2 or 3 dimensions")
     for name in ("embed_neighbors", "embed_min_dist", "embed_seed", "embed_init"):
-        if getattr(args, name) is not None and args.embed is None:
+        if getattr(args, name) is not None and args.embed is None and (args.onto is None or name == "embed_init"):
             parser.error(f"--{name} needs --embed DIM")
     if args.embed_neighbors is None:
         args.embed_neighbors = 15
@@ -343,6 +364,11 @@ def main(argv=None):
     args = parse_args(argv)
     assert args.csv_save_path.endswith(".csv") or args.csv_save_path == "buffer", \
         "csv_save_path must ends with .csv or be 'buffer'"
+    library = None
+    if args.onto is not None:                                # read before the model is: a wrong library costs nothing
+        library = LB.patch_library(args.onto)
+        if library["patch"].shape[2] != args.patches:
+            build_parser().error(f"--patches must be the library's {library['patch'].shape[2]} columns (got {args.patches})")
     try:
         segmenter = WhisperSegmenterFast(args.model_path, device=args.device, device_ids=args.device_ids)
     except Exception:
@@ -380,6 +406,9 @@ def main(argv=None):
     if args.patches is not None:
         archive = patch_archive(*tabled, width=args.patches)
         archive.update(analyses(archive["patch"], args))
+        if library is not None:
+            archive.update(LB.patch_onto(archive["patch"], library, args.embed_neighbors, args.embed_min_dist, args.embed_seed,
+                                         args.cluster_min_samples))
         np.savez(args.patches_save_path, **archive)
     if args.csv_save_path == "buffer":
         buf = io.StringIO()

@@ -97,6 +97,9 @@ SYMBOLS = {
     "wseg_embed_epochs_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
                                         C.c_double, C.c_int32, C.c_uint64, C.c_void_p]),
+    "wseg_embed_place_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_int32, C.c_void_p]),
     "wseg_pca_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "wseg_pca_moments_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wseg_pca_project_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

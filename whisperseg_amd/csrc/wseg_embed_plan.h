@@ -1,6 +1,7 @@
 // The host arithmetic of the layout epochs of the 2-D / 3-D embedding (wseg_embed_scratch_bytes / wseg_embed_epochs_f64), in one
 // place: the validation of a call, the grid, which buffer each epoch reads and writes, and the size of the scratch.  Plain C++ with
-// no HIP dependency, so that a host-only program can run it under a sanitizer (tools/embed_plan_check.cpp).
+// no HIP dependency, so that a host-only program can run it under a sanitizer (tools/embed_plan_check.cpp, and
+// tools/embed_place_plan_check.cpp for the placement of new rows at the end of this file).
 //
 // An epoch is ONE launch of embed_epoch_kernel: a lane per vertex, kEmbedLanes lanes a workgroup, the grid striding over the
 // vertices.  Epoch t reads the positions epoch t - 1 wrote and writes others, so the epochs t0 .. t1 - 1 of a call ping-pong between
@@ -48,11 +49,9 @@ inline int embed_sizes(int64_t n, int32_t dim, EmbedPlan* plan, char* msg, size_
   return 0;
 }
 
-// Validates a whole call and fills the plan -> 0, or -1 with the argument's name in msg.
-inline int embed_plan(int64_t n, int64_t nnz, int32_t dim, int64_t t0, int64_t t1, int64_t total, double lr, double a, double b,
-                      double gamma, int32_t n_neg, EmbedPlan* plan, char* msg, size_t msg_len) {
-  EmbedPlan p = {};
-  if (embed_sizes(n, dim, &p, msg, msg_len)) return -1;
+// Validates what a run has besides its sizes: nnz, the epochs and the parameters -> 0, or -1 with the argument's name in msg.
+inline int embed_run(int64_t nnz, int64_t t0, int64_t t1, int64_t total, double lr, double a, double b, double gamma, int32_t n_neg, char* msg,
+                     size_t msg_len) {
   if (nnz < 0 || nnz > kEmbedMaxNnz) { snprintf(msg, msg_len, "nnz must be 0 .. 2^38 (got %lld)", (long long)nnz); return -1; }
   if (total < 1 || total > kEmbedMaxEpochs) { snprintf(msg, msg_len, "total_epochs must be 1 .. 2^31 - 1 (got %lld)", (long long)total); return -1; }
   if (t0 < 0 || t0 >= t1 || t1 > total) {
@@ -64,6 +63,15 @@ inline int embed_plan(int64_t n, int64_t nnz, int32_t dim, int64_t t0, int64_t t
   if (!embed_finite(a) || a < 0) { snprintf(msg, msg_len, "a must be finite and not negative"); return -1; }
   if (!embed_finite(b) || b <= 0) { snprintf(msg, msg_len, "b must be finite and positive"); return -1; }
   if (!embed_finite(gamma)) { snprintf(msg, msg_len, "gamma must be finite"); return -1; }
+  return 0;
+}
+
+// Validates a whole call and fills the plan -> 0, or -1 with the argument's name in msg.
+inline int embed_plan(int64_t n, int64_t nnz, int32_t dim, int64_t t0, int64_t t1, int64_t total, double lr, double a, double b,
+                      double gamma, int32_t n_neg, EmbedPlan* plan, char* msg, size_t msg_len) {
+  EmbedPlan p = {};
+  if (embed_sizes(n, dim, &p, msg, msg_len)) return -1;
+  if (embed_run(nnz, t0, t1, total, lr, a, b, gamma, n_neg, msg, msg_len)) return -1;
   p.nnz = nnz;
   p.t0 = t0;
   p.t1 = t1;
@@ -76,5 +84,44 @@ inline int embed_plan(int64_t n, int64_t nnz, int32_t dim, int64_t t0, int64_t t
 // where epoch t of the plan writes (1: y_out, 0: the scratch) and reads (2: y_in, 1: y_out, 0: the scratch)
 inline int embed_writes(const EmbedPlan& p, int64_t t) { return (int)(((p.t1 - 1 - t) & 1) == 0); }
 inline int embed_reads(const EmbedPlan& p, int64_t t) { return t == p.t0 ? 2 : embed_writes(p, t - 1); }
+
+// ---- placing new rows on a frozen map (wseg_embed_place_f64) -----------------------------------------------------------------------
+// ONE launch of embed_place_kernel runs all the epochs t0 .. t1 - 1: a lane per new row, kEmbedLanes lanes a workgroup, the grid
+// striding over the m new rows.  A lane keeps its row's position in registers from y_in to y_out, so there is no ping-pong and no
+// scratch.  A row holds at most kEmbedPlaceRow entries (the k of a nearest-neighbour list); entry q of a row in epoch t draws its
+// negatives from the counters key + ((t * kEmbedPlaceRow + q) * kEmbedMaxNeg + s), which wrap in uint64 by design.
+constexpr int kEmbedPlaceRow = 64;                     // entries of a new row that count: neighbors' largest k
+
+struct EmbedPlacePlan {
+  int64_t m, nnz, n;
+  int32_t dim;
+  int64_t t0, t1, total;
+  int32_t grid;                    // workgroups of the launch, min(ceil(m / 64), cap); 0 without a new row: nothing is launched
+};
+
+// Validates a whole call and fills the plan -> 0, or -1 with the argument's name in msg.  The limits are embed_plan's; m == 0 is
+// valid and launches nothing (n may then be 0 too), and with m > 0 the corpus holds at least one vertex: n >= 1.
+inline int embed_place_plan(int64_t m, int64_t nnz, int64_t n, int32_t dim, int64_t t0, int64_t t1, int64_t total, double lr, double a,
+                            double b, double gamma, int32_t n_neg, EmbedPlacePlan* plan, char* msg, size_t msg_len) {
+  EmbedPlacePlan p = {};
+  if (dim != 2 && dim != 3) { snprintf(msg, msg_len, "dim must be 2 or 3 (got %d)", (int)dim); return -1; }
+  if (m < 0 || m > kEmbedMaxRows) { snprintf(msg, msg_len, "m must be 0 .. 2^31 - 1 (got %lld)", (long long)m); return -1; }
+  if (n < (m > 0 ? 1 : 0) || n > kEmbedMaxRows) {
+    snprintf(msg, msg_len, "n must be %d .. 2^31 - 1: new rows need a corpus (got %lld)", m > 0 ? 1 : 0, (long long)n);
+    return -1;
+  }
+  if (embed_run(nnz, t0, t1, total, lr, a, b, gamma, n_neg, msg, msg_len)) return -1;
+  p.m = m;
+  p.nnz = nnz;
+  p.n = n;
+  p.dim = dim;
+  p.t0 = t0;
+  p.t1 = t1;
+  p.total = total;
+  const int64_t groups = (m + kEmbedLanes - 1) / kEmbedLanes;
+  p.grid = (int32_t)(groups < kEmbedGridCap ? groups : kEmbedGridCap);
+  *plan = p;
+  return 0;
+}
 
 }  // namespace wseg

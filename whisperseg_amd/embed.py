@@ -35,6 +35,33 @@ result is one function of its input: no races, no atomics, nothing that depends 
 What the device may differ by: nothing where b == 1 — float64 + - * / are correctly rounded on both sides and nothing is contracted,
 so every coordinate has the definition's bits after any number of epochs; with another b a term differs by what the device's pow and
 numpy's differ by (tests/embed_cases.py derives the bound of one epoch).
+
+NEW ROWS ON AN EXISTING MAP (the layout step of a UMAP transform): the map is a library, its points stay frozen, and M new rows are
+placed among them.  `membership_host`, `row_keys`, `start_host` and `place_host` are THE definition; `place` runs the same epochs on
+the GPU (wseg_embed_place_f64: all epochs in one launch, a lane per new row) and `transform` goes from new rows to positions.  With
+the frozen corpus positions Y float64 [N, dim], N >= 1, and the new rows' lists `index` int [M, k], `distance` float32 [M, k] exactly
+as neighbors(new, corpus, k) returns them (squared, ascending, a tail of -1 / +inf):
+
+  membership     per new row, over its valid entries in list order: d_j, rho, the 64-step bisection for sigma, the 1e-3 * mean floor
+                 and p(i→j) exactly as fuzzy_graph_host states them; no entry is left out as "own" and nothing is symmetrised.  A
+                 CSR (indptr int64 [M + 1], indices int32, weight p) with the entries in list order, nearest first; an entry whose p
+                 underflowed to 0 is left out, a corpus index listed twice counts once, at its first entry
+  schedule       rate_e = floor(p_e * 65536 + 0.5): a row's nearest entry has p = 1, so w_max is 1 and a rate is the row's own;
+                 entries of rate 0 are dropped; q is an entry's position within its row of what is left, q < 64; ACTIVE as above
+  key            key_i = draw((uint64(j0) << 32) | bits32(d0)), (j0, d0) the row's first list entry and its float32 distance
+  negatives      sample s of entry q of row i in epoch t is the corpus vertex m = ((mix(key_i + ((t * 64 + q) * 16 + s)) >> 32) * N) >> 32;
+                 nothing is skipped: a corpus vertex is never the row itself
+  start          y0_i[c] = (sum_e p_e * Y[j_e][c]) / (sum_e p_e), both sums left to right over the row's scheduled entries (a row
+                 without one: the origin); or an array [M, dim], used as given
+  a term         exactly the attraction and repulsion term and clip above, with y_j = Y[j]
+  an epoch       for row i: G = 0; for its entries in order, if the entry is active: G += its attraction term, then G += the repulsion
+                 term of each of its n_neg negatives in the order of s; then y_i += alpha_t * G.  The corpus never moves and new rows
+                 never see each other
+  conventions    N == 0, an index outside -1 .. N - 1, a non-finite or negative listed distance, more than 64 entries in a row or
+                 a Y that is not finite [N, dim]: ValueError before anything runs
+
+Every output for a new row is a function of that row's list and the library alone: not of the other rows of the batch, their order
+or their number.  What the device may differ by is what it may differ by above: nothing where b == 1, the bound of one epoch otherwise.
 """
 import numpy as np
 
@@ -75,6 +102,31 @@ def fuzzy_graph_host(index, distance):
     valid = (index >= 0) & (index != np.arange(n)[:, None])
     if not np.isfinite(np.asarray(distance, np.float64)[valid]).all() or (np.asarray(distance, np.float64)[valid] < 0).any():
         raise ValueError("the distances of the listed neighbours must be finite and not negative")
+    p = directed_host(valid, distance)
+    # symmetrise over the union of (i, j) and (j, i); a pair a row lists twice counts once (its first entry)
+    i_of = np.repeat(np.arange(n, dtype=np.int64), k)[valid.ravel()]
+    j_of = index.astype(np.int64).ravel()[valid.ravel()]
+    key, first = np.unique(i_of * n + j_of, return_index=True)
+    p_of = p.ravel()[valid.ravel()][first]
+    back = (key % n) * n + key // n
+    pairs = np.union1d(key, back)
+    fwd, bwd = np.zeros(len(pairs)), np.zeros(len(pairs))
+    fwd[np.searchsorted(pairs, key)] = p_of
+    bwd[np.searchsorted(pairs, back)] = p_of
+    weight = np.minimum(1.0, fwd + bwd - fwd * bwd)
+    keep = weight > 0
+    pairs, weight = pairs[keep], weight[keep]
+    indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(pairs // n, minlength=n), out=indptr[1:])
+    return indptr, (pairs % n).astype(np.int32), weight
+
+
+def directed_host(valid, distance):
+    """p(i→j) float64 [N, k] of fuzzy_graph_host's docstring — d_j, rho, the 64-step bisection for sigma, its floor — for the lists'
+    SQUARED distances [N, k], k >= 1, over the entries `valid` says are there (their distances finite and not negative); what stands
+    at the others is not looked at and their p means nothing.  Every row is computed from that row alone: fuzzy_graph_host and
+    membership_host share this arithmetic."""
+    n, k = valid.shape
     d = np.sqrt(np.where(valid, distance, 0).astype(np.float64))
     rho = np.where(valid & (d > 0), d, np.inf).min(axis=1)
     rho = np.where(np.isinf(rho), 0.0, rho)
@@ -99,22 +151,7 @@ def fuzzy_graph_host(index, distance):
     sigma = np.maximum(mid, 1e-3 * mean)
     with np.errstate(divide="ignore", invalid="ignore"):
         p = np.where(sigma[:, None] == 0, 1.0, np.exp(-over / sigma[:, None]))
-    # symmetrise over the union of (i, j) and (j, i); a pair a row lists twice counts once (its first entry)
-    i_of = np.repeat(np.arange(n, dtype=np.int64), k)[valid.ravel()]
-    j_of = index.astype(np.int64).ravel()[valid.ravel()]
-    key, first = np.unique(i_of * n + j_of, return_index=True)
-    p_of = p.ravel()[valid.ravel()][first]
-    back = (key % n) * n + key // n
-    pairs = np.union1d(key, back)
-    fwd, bwd = np.zeros(len(pairs)), np.zeros(len(pairs))
-    fwd[np.searchsorted(pairs, key)] = p_of
-    bwd[np.searchsorted(pairs, back)] = p_of
-    weight = np.minimum(1.0, fwd + bwd - fwd * bwd)
-    keep = weight > 0
-    pairs, weight = pairs[keep], weight[keep]
-    indptr = np.zeros(n + 1, np.int64)
-    np.cumsum(np.bincount(pairs // n, minlength=n), out=indptr[1:])
-    return indptr, (pairs % n).astype(np.int32), weight
+    return p
 
 
 def curve_ab(min_dist, spread=1.0):
@@ -233,33 +270,45 @@ def check_dim(dim):
     return RS.check_int(dim, "dim", 2, 3, "2 or 3")
 
 
+def check_epochs(epochs, total):
+    """(t0, t1, T) of `epochs` — T, or (t0, t1) of `total` (default t1) — as ints; ValueError unless 0 <= t0 < t1 <= T <= 2^31 - 1."""
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if isinstance(epochs, (tuple, list)):
+        if len(epochs) != 2 or not all(whole(v) for v in epochs):
+            raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
+        t0, t1 = int(epochs[0]), int(epochs[1])
+        total = t1 if total is None else total
+    elif whole(epochs):
+        t0, t1 = 0, int(epochs)
+        total = t1 if total is None else total
+    else:
+        raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
+    if not whole(total) or not 1 <= int(total) <= 2 ** 31 - 1 or not 0 <= t0 < t1 <= int(total):
+        raise ValueError(f"epochs must be at least 1, and (t0, t1) must satisfy 0 <= t0 < t1 <= total (got {epochs!r} of {total!r})")
+    return t0, t1, int(total)
+
+
+def check_curve(a, b, gamma, lr):
+    """(a, b, gamma, lr) as floats, a and b defaulting to curve_ab(0.1); ValueError unless a >= 0, b > 0 and all four are finite."""
+    if (a is None) != (b is None):
+        raise ValueError("give a and b together (curve_ab), or neither")
+    if a is None:
+        a, b = curve_ab(0.1)
+    a, b, gamma, lr = float(a), float(b), float(gamma), float(lr)
+    if not (np.isfinite(a) and a >= 0 and np.isfinite(b) and b > 0 and np.isfinite(gamma) and np.isfinite(lr)):
+        raise ValueError(f"a >= 0, b > 0, gamma and lr must be finite (got {a!r}, {b!r}, {gamma!r}, {lr!r})")
+    return a, b, gamma, lr
+
+
 class Run:
     """The checked arguments of layout_host / layout: the scheduled CSR, the epochs (t0, t1) of T, the parameters and the start."""
 
     def __init__(self, graph, dim, epochs, total, n_neg, gamma, lr, a, b, init, seed):
         check_dim(dim)
-        whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
-        if isinstance(epochs, (tuple, list)):
-            if len(epochs) != 2 or not all(whole(v) for v in epochs):
-                raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
-            t0, t1 = int(epochs[0]), int(epochs[1])
-            total = t1 if total is None else total
-        elif whole(epochs):
-            t0, t1 = 0, int(epochs)
-            total = t1 if total is None else total
-        else:
-            raise ValueError(f"epochs must be an integer or (t0, t1) (got {epochs!r})")
-        if not whole(total) or not 1 <= int(total) <= 2 ** 31 - 1 or not 0 <= t0 < t1 <= int(total):
-            raise ValueError(f"epochs must be at least 1, and (t0, t1) must satisfy 0 <= t0 < t1 <= total (got {epochs!r} of {total!r})")
+        t0, t1, total = check_epochs(epochs, total)
         RS.check_int(n_neg, "n_neg", 0, MAX_NEG)
         RS.check_int(seed, "seed", 0, MASK, "in 0 .. 2^64 - 1")
-        if (a is None) != (b is None):
-            raise ValueError("give a and b together (curve_ab), or neither")
-        if a is None:
-            a, b = curve_ab(0.1)
-        a, b, gamma, lr = float(a), float(b), float(gamma), float(lr)
-        if not (np.isfinite(a) and a >= 0 and np.isfinite(b) and b > 0 and np.isfinite(gamma) and np.isfinite(lr)):
-            raise ValueError(f"a >= 0, b > 0, gamma and lr must be finite (got {a!r}, {b!r}, {gamma!r}, {lr!r})")
+        a, b, gamma, lr = check_curve(a, b, gamma, lr)
         self.indptr, self.indices, self.rate = scheduled(graph)
         self.n, self.nnz = len(self.indptr) - 1, len(self.indices)
         self.dim, self.t0, self.t1, self.total, self.n_neg, self.seed = int(dim), t0, t1, int(total), int(n_neg), int(seed)
@@ -431,3 +480,252 @@ def patch_embedding(predictions, k=15, dim=2, min_dist=0.1, epochs=200, seed=0, 
     if not len(rows):
         return {"embedding": np.zeros((0, dim), np.float32)}
     return {"embedding": embed(rows, k, dim, min_dist, epochs, seed, device, init=init, lists=lists)}
+
+
+# ---- new rows on an existing map (the definition, then the device path) -----------------------------------------------------------------
+PLACE_ROW = 64                         # entries of a new row: the largest k of a list (csrc/wseg_embed_plan.h::kEmbedPlaceRow)
+PLACE_EPOCHS = 100                     # umap-learn's epochs for a transform of a small set: a parameter, not a measured optimum
+
+
+def check_lists(index, distance, n):
+    """(index, distance, valid) of the lists of new rows among n corpus rows, as numpy; ValueError unless they are an integer and a
+    float array [M, k], k <= 64, n >= 1, every index in -1 .. n - 1 and every listed distance finite and not negative."""
+    index, distance = np.asarray(index), np.asarray(distance)
+    if index.ndim != 2 or index.shape != distance.shape or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"index (integer) and distance must both be [M, k] (got {index.shape} and {distance.shape})")
+    n = RS.check_int(n, "the corpus size N", 1, 2 ** 31 - 1, "of at least 1 (new rows need a corpus)")
+    if index.shape[1] > PLACE_ROW:
+        raise ValueError(f"a new row lists at most {PLACE_ROW} neighbours (got k = {index.shape[1]})")
+    if index.size and (index.max() >= n or index.min() < -1):
+        raise ValueError("an index names a corpus row outside -1 .. N - 1")
+    valid = index >= 0
+    listed = np.asarray(distance, np.float64)[valid]
+    if not np.isfinite(listed).all() or (listed < 0).any():
+        raise ValueError("the distances of the listed neighbours must be finite and not negative")
+    return index, distance, valid
+
+
+def membership_host(index, distance, n):
+    """The memberships of M NEW rows in a corpus of n rows from their lists `index` int [M, k] and `distance` [M, k] exactly as
+    neighbors.neighbors(new, corpus, k) returns them -> (indptr int64 [M + 1], indices int32 [nnz], weight float64 [nnz]): row i
+    holds p(i→j) of fuzzy_graph_host's docstring for its valid entries j (corpus rows) in LIST order, nearest first.  No entry is
+    left out as the row's own, and there is no symmetrisation: a corpus row has no list that could name a new one.  An entry whose p
+    underflowed to 0 is left out, and a corpus row listed twice counts once, at its first entry.  A row's nearest entry has p = 1."""
+    index, distance, valid = check_lists(index, distance, n)
+    m, k = index.shape
+    if m == 0 or k == 0:
+        return np.zeros(m + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64)
+    p = directed_host(valid, distance)
+    again = np.zeros_like(valid)                         # an entry that repeats an index standing earlier in its list
+    for c in range(1, k):
+        again[:, c] = (valid[:, :c] & (index[:, :c] == index[:, c:c + 1])).any(axis=1)
+    keep = valid & ~again & (p > 0)
+    indptr = np.zeros(m + 1, np.int64)
+    np.cumsum(keep.sum(axis=1), out=indptr[1:])
+    return indptr, np.ascontiguousarray(index[keep], dtype=np.int32), np.ascontiguousarray(p[keep])
+
+
+def row_keys(index, distance, seed):
+    """uint64 [M]: the key of every new row, from which its negative samples are drawn — draw(seed, (uint64(j0) << 32) | bits32(d0))
+    with (j0, d0) the row's FIRST list entry and its float32 distance (j0 as its 32-bit pattern: a row without an entry has no use
+    for its key).  A function of the row's own list: two batches that hold the same call give it the same key."""
+    index, distance = np.asarray(index), np.asarray(distance)
+    if index.ndim != 2 or index.shape != distance.shape or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"index (integer) and distance must both be [M, k] (got {index.shape} and {distance.shape})")
+    RS.check_int(seed, "seed", 0, MASK, "in 0 .. 2^64 - 1")
+    if index.shape[0] == 0 or index.shape[1] == 0:
+        return np.zeros(index.shape[0], np.uint64)
+    j0 = index[:, 0].astype(np.int32).view(np.uint32).astype(np.uint64)
+    d0 = np.ascontiguousarray(distance[:, 0], dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return draw(seed, (j0 << np.uint64(32)) | d0)
+
+
+def scheduled_onto(graph, n):
+    """(indptr int64 [M + 1], indices int32 [nnz], rate uint32 [nnz], weight float64 [nnz]) of the CSR the placement runs on: the
+    entries of `graph` (membership_host's: rows are new rows, indices corpus rows 0 .. n - 1, weights in [0, 1]) whose rate
+    floor(p * 65536 + 0.5) is not 0.  A row's nearest entry has p = 1, so w_max is 1 and a rate is the row's own, whatever else is in
+    the batch.  ValueError unless it is such a CSR and no row keeps more than 64 entries."""
+    try:
+        indptr, indices, weight = graph
+    except (TypeError, ValueError):
+        raise ValueError("a graph is (indptr [M + 1], indices [nnz], weight [nnz])") from None
+    indptr, indices, weight = np.asarray(indptr), np.asarray(indices), np.asarray(weight, dtype=np.float64)
+    if indptr.ndim != 1 or len(indptr) < 1 or indices.ndim != 1 or weight.shape != indices.shape:
+        raise ValueError("a graph is (indptr [M + 1], indices [nnz], weight [nnz])")
+    m = len(indptr) - 1
+    if m > np.iinfo(np.int32).max:
+        raise ValueError("at most 2^31 - 1 new rows")
+    indptr = indptr.astype(np.int64)
+    if indptr[0] != 0 or indptr[-1] != len(indices) or (np.diff(indptr) < 0).any():
+        raise ValueError("indptr must ascend from 0 to nnz")
+    if len(indices) and (not np.issubdtype(indices.dtype, np.integer) or indices.min() < 0 or indices.max() >= n):
+        raise ValueError("an entry names a corpus row outside 0 .. N - 1")
+    if not np.isfinite(weight).all() or (weight < 0).any() or (weight > 1).any():
+        raise ValueError("the weights must lie in [0, 1]")
+    rate = np.floor(weight * 65536.0 + 0.5).astype(np.uint32)
+    keep = rate > 0
+    out = np.zeros(m + 1, np.int64)
+    np.cumsum(np.bincount(np.repeat(np.arange(m), np.diff(indptr))[keep], minlength=m), out=out[1:])
+    if m and np.diff(out).max() > PLACE_ROW:
+        raise ValueError(f"a new row has at most {PLACE_ROW} entries (got {int(np.diff(out).max())})")
+    return out, np.ascontiguousarray(indices[keep], dtype=np.int32), np.ascontiguousarray(rate[keep]), np.ascontiguousarray(weight[keep])
+
+
+def check_positions(positions):
+    """The frozen corpus positions as float64 [N, dim]; ValueError unless N >= 1, dim is 2 or 3 and every coordinate is finite."""
+    y = np.array(positions, dtype=np.float64, order="C")
+    if y.ndim != 2 or y.shape[1] not in (2, 3) or y.shape[0] < 1 or not np.isfinite(y).all():
+        raise ValueError(f"the corpus positions must be finite [N, dim], N >= 1, dim 2 or 3 (got {y.shape})")
+    return y
+
+
+def _weighted_start(indptr, indices, weight, y):
+    """start_host on a scheduled CSR."""
+    m, dim = len(indptr) - 1, y.shape[1]
+    top, mass = np.zeros((m, dim)), np.zeros(m)
+    begin, count = indptr[:-1], np.diff(indptr)
+    for q in range(int(count.max(initial=0))):           # the q-th entry of every row that has one: left to right within a row
+        rows = np.flatnonzero(count > q)
+        e = begin[rows] + q
+        top[rows] = top[rows] + weight[e][:, None] * y[indices[e]]
+        mass[rows] = mass[rows] + weight[e]
+    out = np.zeros((m, dim))
+    has = mass > 0
+    out[has] = top[has] / mass[has][:, None]
+    return out
+
+
+def start_host(graph, positions):
+    """float64 [M, dim]: where a new row starts — y0_i[c] = (sum_e p_e Y[j_e][c]) / (sum_e p_e), both sums left to right over the
+    row's SCHEDULED entries (scheduled_onto): the membership-weighted mean of its neighbours on the map, as umap-learn's transform
+    starts.  A row without an entry starts at the origin."""
+    y = check_positions(positions)
+    indptr, indices, _, weight = scheduled_onto(graph, len(y))
+    return _weighted_start(indptr, indices, weight, y)
+
+
+class Place:
+    """The checked arguments of place_host / place: the scheduled CSR of the new rows, the frozen corpus positions, the keys, the
+    epochs (t0, t1) of T, the parameters and the start."""
+
+    def __init__(self, graph, positions, keys, epochs, total, n_neg, gamma, lr, a, b, init):
+        self.y = check_positions(positions)
+        self.n, self.dim = self.y.shape
+        self.t0, self.t1, self.total = check_epochs(epochs, total)
+        self.n_neg = RS.check_int(n_neg, "n_neg", 0, MAX_NEG)
+        self.a, self.b, self.gamma, self.lr = check_curve(a, b, gamma, lr)
+        self.indptr, self.indices, self.rate, weight = scheduled_onto(graph, self.n)
+        self.m, self.nnz = len(self.indptr) - 1, len(self.indices)
+        keys = np.asarray(keys)
+        if keys.shape != (self.m,) or keys.dtype != np.uint64:
+            raise ValueError(f"keys must be uint64 [M] = {(self.m,)} (row_keys; got {keys.dtype} {keys.shape})")
+        self.key = np.ascontiguousarray(keys)
+        if init is None:
+            self.y0 = _weighted_start(self.indptr, self.indices, weight, self.y)
+        else:
+            y0 = np.array(init, dtype=np.float64, order="C")
+            if y0.shape != (self.m, self.dim) or not np.isfinite(y0).all():
+                raise ValueError(f"init must be finite [M, dim] = {(self.m, self.dim)} (got {y0.shape})")
+            self.y0 = y0
+
+    def alpha(self, t):
+        return self.lr * (1.0 - t / self.total)
+
+
+def place_negatives(key, t, q, n_neg, n):
+    """int64 [len(key), n_neg]: the negative samples among n corpus vertices of the entries at the positions q of the rows with
+    these keys in epoch t — ((mix64(key + ((t * 64 + q) * 16 + s)) >> 32) * n) >> 32."""
+    base = np.asarray(key, np.uint64) + (np.uint64(int(t) * PLACE_ROW) + np.asarray(q).astype(np.uint64)) * np.uint64(MAX_NEG)
+    h = mix64(base[:, None] + np.arange(n_neg, dtype=np.uint64)[None, :])
+    return (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def place_host(graph, positions, keys, epochs=PLACE_EPOCHS, total=None, n_neg=5, gamma=1.0, lr=1.0, a=None, b=None, init=None):
+    """The definition of placing new rows on a frozen map -> their positions float64 [M, dim] after the epochs.  `graph`: what
+    membership_host returned; `positions`: the corpus positions Y float64 [N, dim]; `keys`: row_keys; `epochs`, `total`, a, b: as
+    layout_host's; `init`: None for start_host, or the positions a run to t0 returned.  The module docstring states an epoch."""
+    return place_epochs_host(Place(graph, positions, keys, epochs, total, n_neg, gamma, lr, a, b, init))
+
+
+def place_epochs_host(run):
+    """The epochs of a checked Place in numpy -> positions float64 [M, dim].  All terms of an epoch are formed at once and summed
+    over the position of an entry within its row, which is every row's own chain."""
+    y = run.y0.copy()
+    row = np.repeat(np.arange(run.m, dtype=np.int64), np.diff(run.indptr))
+    place = np.arange(run.nnz, dtype=np.int64) - run.indptr[row]
+    for t in range(run.t0, run.t1):
+        e = np.flatnonzero(active(run.rate, t))
+        i = row[e]
+        force = np.zeros_like(y)
+        if len(e):
+            pull = _terms(run, y[i] - run.y[run.indices[e]], True)
+            if run.n_neg:
+                v = place_negatives(run.key[i], t, place[e], run.n_neg, run.n)
+                push = _terms(run, np.repeat(y[i], run.n_neg, axis=0) - run.y[v.ravel()], False).reshape(len(e), run.n_neg, run.dim)
+            order = np.argsort(place[e], kind="stable")
+            starts = np.searchsorted(place[e][order], np.arange(place[e].max() + 2))
+            for q in range(len(starts) - 1):             # the q-th entry of every row that has one: distinct rows
+                sel = order[starts[q]:starts[q + 1]]
+                force[i[sel]] += pull[sel]
+                for s in range(run.n_neg):
+                    force[i[sel]] += push[sel, s]
+        y = y + run.alpha(t) * force
+    return y
+
+
+def place_rows(run, device="cuda"):
+    """The launch of a checked Place -> the positions as a DEVICE tensor float64 [M, dim]: one launch of wseg_embed_place_f64 for all
+    its epochs.  Stream-ordered, no host synchronisation."""
+    import torch
+    lib = _lib.load(require_device=True)
+    dev = torch.device(device)
+    y_in = torch.from_numpy(run.y0).to(dev)
+    y_out = torch.empty_like(y_in)
+    if run.m == 0:
+        return y_out
+    indptr = torch.from_numpy(run.indptr).to(dev)
+    indices = torch.from_numpy(run.indices).to(dev)
+    rate = torch.from_numpy(run.rate.view(np.int32)).to(dev)
+    key = torch.from_numpy(run.key.view(np.int64)).to(dev)
+    corpus = torch.from_numpy(run.y).to(dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.wseg_embed_place_f64(indptr.data_ptr(), indices.data_ptr() if run.nnz else None, rate.data_ptr() if run.nnz else None,
+                                            key.data_ptr(), run.m, run.nnz, corpus.data_ptr(), run.n, run.dim, y_in.data_ptr(), y_out.data_ptr(),
+                                            run.t0, run.t1, run.total, run.lr, run.a, run.b, run.gamma, run.n_neg, _lib.stream_ptr()))
+    return y_out
+
+
+def place(graph, positions, keys, epochs=PLACE_EPOCHS, total=None, n_neg=5, gamma=1.0, lr=1.0, a=None, b=None, init=None, device="cuda"):
+    """place_host's positions, with the epochs on the GPU -> float64 [M, dim] as numpy.  The arguments are place_host's.
+    epochs=(t0, t1) with init= the positions a run to t0 returned continues that run, as layout's."""
+    run = Place(graph, positions, keys, epochs, total, n_neg, gamma, lr, a, b, init)
+    return place_rows(run, device).cpu().numpy()
+
+
+def transform(rows, corpus_rows, corpus_positions, k=15, min_dist=0.1, spread=1.0, epochs=PLACE_EPOCHS, seed=0, n_neg=5, lists=None,
+              device="cuda"):
+    """float32 [M, dim]: the new `rows` (float32 [M, D]) on the map `corpus_positions` [N, dim] of `corpus_rows` [N, D] — the k nearest
+    corpus rows of every new row (neighbors.neighbors, or the caller's `lists` (index, distance) [M, k]), their memberships
+    (membership_host), keys (row_keys), start (start_host) and `epochs` epochs of place with a, b = curve_ab(min_dist, spread): the
+    values the map itself was made with.  The map does not move, and a row's position does not depend on the other new rows.
+    Rows and positions: numpy or device tensors (searched where they lie).  No new rows: [0, dim]; no corpus: ValueError.  Every
+    argument is checked before the search runs."""
+    k = NB.check_k(k)
+    a, b = curve_ab(min_dist, spread)
+    RS.check_int(epochs, "epochs", 1, 2 ** 31 - 1, "of at least 1")
+    RS.check_int(seed, "seed", 0, MASK, "in 0 .. 2^64 - 1")
+    RS.check_int(n_neg, "n_neg", 0, MAX_NEG)
+    y = check_positions(corpus_positions.cpu().numpy() if hasattr(corpus_positions, "cpu") else corpus_positions)
+    m, n, _ = NB.check_shapes(RS.shape_of(rows), RS.shape_of(corpus_rows))
+    if n != len(y):
+        raise ValueError(f"the corpus has {n} rows and {len(y)} positions")
+    if lists is not None:
+        index, distance = np.asarray(lists[0]), np.asarray(lists[1])
+        if index.shape != (m, k) or distance.shape != (m, k):
+            raise ValueError(f"lists must be (index, distance) [M, k] = {(m, k)} (got {index.shape} and {distance.shape})")
+    if m == 0:
+        return np.zeros((0, y.shape[1]), np.float32)
+    if lists is None:
+        index, distance = NB.neighbors(rows, corpus_rows, k, device=device)
+    run = Place(membership_host(index, distance, n), y, row_keys(index, distance, seed), int(epochs), None, n_neg, 1.0, 1.0, a, b, None)
+    return place_rows(run, device).cpu().numpy().astype(np.float32)

@@ -376,6 +376,91 @@ def hdbscan_labels(edges, weight, n, min_cluster_size):
     return by_smallest_row(group, group >= 0)
 
 
+# ---- call types for new rows (host) -------------------------------------------------------------------------------------------------
+def reach_of(edges, weight, labels):
+    """float32 [clusters]: for every label 0, 1, ... of `labels` int [N] (the library's, -1: noise) the largest tree weight among the
+    edges whose two ends both carry it.  A cluster of hdbscan_labels is the leaf set of one node of the hierarchy, so those edges span
+    it and the value is the level at which the cluster is fully assembled: a new row that would join it above that level joins
+    something larger than the cluster.  A cluster without such an edge (a single row) gets -inf."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"labels must be integers [N] (got {labels.dtype} {labels.shape})")
+    edges, weight, _ = check_tree(edges, weight, len(labels))
+    reach = np.full(int(labels.max(initial=-1)) + 1, -np.inf, dtype=np.float32)
+    if len(edges):
+        a, b = labels[edges[:, 0]], labels[edges[:, 1]]
+        inside = (a == b) & (a >= 0)
+        np.maximum.at(reach, a[inside], weight[inside].astype(np.float32))
+    return reach
+
+
+def assign_host(index, distance, core, labels, reach, s):
+    """int32 [M]: the library's call type of every new row, or -1, from the row's lists among the library rows `index` int [M, k] and
+    `distance` float32 [M, k] (neighbors.neighbors(new, library, k): squared, ascending), the library's core distances `core` float32
+    [N] at min_samples = s, its `labels` [N] and their `reach` (reach_of).  Per new row q, in float32 and exact like the tree's weights:
+      core(q)   = distance[q, s - 1]: the s-th nearest library row — every library row is an OTHER row
+      w(q, j)   = max(core(q), core[j], distance[q, j]) over the listed j: the mutual-reachability distance
+      anchor    = the listed j that comes first in the order (w, j): where q would hang in the tree
+      label     = labels[anchor] if that is >= 0 and w <= reach[label], else -1
+    A row is judged by its own list alone.  k < s, or a row with fewer than s valid entries: ValueError."""
+    index, distance = np.asarray(index), np.asarray(distance, dtype=np.float32)
+    core, labels, reach = np.asarray(core, dtype=np.float32), np.asarray(labels), np.asarray(reach, dtype=np.float32)
+    if index.ndim != 2 or index.shape != distance.shape or not np.issubdtype(index.dtype, np.integer):
+        raise ValueError(f"index (integer) and distance must both be [M, k] (got {index.shape} and {distance.shape})")
+    n = len(labels)
+    if labels.ndim != 1 or core.shape != (n,) or reach.ndim != 1 or (n and int(labels.max()) >= len(reach)):
+        raise ValueError(f"core and labels must be [N] and reach hold every label (got {core.shape}, {labels.shape} and {reach.shape})")
+    s = RS.check_int(s, "min_samples", 1, MAX_SAMPLES)
+    m, k = index.shape
+    if index.size and (index.max() >= n or index.min() < -1):
+        raise ValueError("an index names a library row outside -1 .. N - 1")
+    if k < s or (m and (index[:, s - 1] < 0).any()):
+        raise ValueError(f"every new row needs its {s} nearest library rows (min_samples): k = {k}, or a list is shorter")
+    if m == 0:
+        return np.zeros(0, np.int32)
+    valid = index >= 0
+    j = np.where(valid, index, 0).astype(np.int64)
+    w = np.maximum(np.maximum(distance[:, s - 1:s], core[j]), distance)
+    w = np.where(valid, w, np.float32(np.inf))
+    order = np.lexsort((np.where(valid, j, n), w), axis=1)[:, 0]         # per row: first by w, then by j
+    rows = np.arange(m)
+    anchor, at = j[rows, order], w[rows, order]
+    label = labels[anchor].astype(np.int64)
+    if not len(reach):                                   # a library without a cluster
+        return np.full(m, -1, dtype=np.int32)
+    ok = (label >= 0) & (at <= reach[np.maximum(label, 0)])
+    return np.where(ok, label, -1).astype(np.int32)
+
+
+def assign(rows, corpus_rows, labels, edges, weight, min_samples=5, k=15, lists=None, device="cuda"):
+    """assign_host's labels int32 [M] for the new `rows` [M, D] against the library `corpus_rows` [N, D] with its `labels` and tree
+    (`edges`, `weight`: mst / patch_clusters, built with this min_samples).  The lists of the new rows (or the caller's `lists`
+    (index, distance) [M, k]) and the library's core distances, neighbors(corpus_rows, None, s)[1][:, s - 1], come from the GPU; the
+    rule itself is O(M k) host work."""
+    k = NB.check_k(k)
+    s = RS.check_int(min_samples, "min_samples", 1, MAX_SAMPLES)
+    if k < s:
+        raise ValueError(f"k = {k} lists fewer library rows than min_samples = {s} needs")
+    m, n, _ = NB.check_shapes(RS.shape_of(rows), RS.shape_of(corpus_rows))
+    labels = np.asarray(labels)
+    if labels.shape != (n,):
+        raise ValueError(f"labels must be [N] = {(n,)} (got {labels.shape})")
+    reach = reach_of(edges, weight, labels)
+    if lists is not None:
+        index, distance = np.asarray(lists[0]), np.asarray(lists[1])
+        if index.shape != (m, k) or distance.shape != (m, k):
+            raise ValueError(f"lists must be (index, distance) [M, k] = {(m, k)} (got {index.shape} and {distance.shape})")
+    if m == 0:
+        return np.zeros(0, np.int32)
+    if n <= s:
+        raise ValueError(f"a library of {n} rows has no core distances at min_samples = {s}")
+    x = RS.resident(corpus_rows, device)
+    if lists is None:
+        index, distance = NB.neighbors(rows, x, k, device=device)
+    core = NB.knn_rows(x, None, s)[1][:, s - 1].cpu().numpy()
+    return assign_host(index, distance, core, labels, reach, s)
+
+
 def patch_clusters(predictions, min_cluster_size, min_samples=5, device="cuda"):
     """{"cluster": int32 [rows] (hdbscan_labels; -1: noise), "mst_edges": int32 [rows - 1, 2], "mst_weight": float32 [rows - 1]} of
     all the calls of `predictions` — what segment*(..., patches=W) returned, or the pictures themselves
