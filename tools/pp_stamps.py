@@ -52,6 +52,15 @@ for g in range(2):
             nxt = S[g][t][p + 1][0] if p < 1 else S[g][t + 1][0][0]
             row.append(f"phase {'AB'[p]}: L {s[1] - s[0]:4d} wait {s[2] - s[1]:4d} M {s[3] - s[2]:4d} tail {nxt - s[3]:4d}")
         print(f"group {g} K tile {8 + t}: " + " | ".join(row) + f" | K tile {S[g][t + 1][0][0] - S[g][t][0][0]} cycles")
+# Hand-overs of the matrix pipe: M end of one group -> M start of the other group on the same SIMD (waves 0 and 4), in issue order
+# g0 A -> g1 A -> g0 B -> g1 B -> g0 A of the next K tile.  The M-end stamp sits in front of the leaving wave's barrier, so each figure
+# carries one stamp (~100 cycles); the interval is M start -> next M start of the other group.
+for t in range(1, 3):
+    seq = [(0, t, 0), (1, t, 0), (0, t, 1), (1, t, 1), (0, t + 1, 0)]
+    row = []
+    for (ga, ta, pa), (gb, tb, pb) in zip(seq, seq[1:]):
+        row.append(f"g{ga}{'AB'[pa]}->g{gb}{'AB'[pb]}: gap {S[gb][tb][pb][2] - S[ga][ta][pa][3]:4d} interval {S[gb][tb][pb][2] - S[ga][ta][pa][2]:4d}")
+    print(f"hand-overs K tile {8 + t}: " + " | ".join(row))
 t0 = S[0][1][0][0]
 print("group 1 lags group 0 by", S[1][1][0][0] - t0, "cycles at the top of K tile 9")
 dc, dt = buf[130] - buf[128], (buf[131] - buf[129]) / 100.0

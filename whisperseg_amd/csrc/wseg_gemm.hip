@@ -683,6 +683,15 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && BN == 128) ? 2 : 1) voi
 // (Rounds 2-3 ran FOUR phases of 16 MFMAs.  Cycle stamps — build --stamps 4, tools/pp_stamps.py — showed the MFMAs themselves
 // at full rate, 16.5 cycles each, and every barrier interval bound by the OTHER group's L part plus the hand-over; two phases
 // halve the hand-overs: qkv / o-proj / fc1 / fc2 / conv2 at 256 windows -2.4 / -2.2 / -3.0 / -5.2 / -4.9 %.)
+// OVERLAPPED HAND-OVER (16-bit and x3 M parts; the M6 tiles keep the form above): the barrier that closes an M part is issued TAIL = 2
+// MFMAs EARLY,
+//     M part: MFMAs 0 .. NM-3 at priority 1 | s_setprio 2, (phase B: the vmcnt retirement,) s_barrier | MFMAs NM-2, NM-1 | s_setprio 0
+// so that the other group's wave on the SIMD is released, and runs its s_setprio 1, while the leaving wave's last MFMAs still feed the
+// matrix pipe.  MFMAs touch registers only: every LDS / LDS-DMA invariant below is stated in barriers and holds unchanged, and the
+// MFMAs run on the same accumulators in the same order (bit-identical output).  The tail runs ABOVE the entering wave's priority: at
+// equal priority the arbiter prefers the older wave, group 1's tail waits behind group 0's whole M part and group 1's L part loses its
+// cover.  The last K tile of an output tile has no closing barrier and keeps its M part whole.  Stamps at 256 windows, f16x3: barrier
+// interval 950-1 090 -> 790-930 cycles against 768-792 of MFMAs; encoder GEMMs -2.3 .. -3.2 % (profiles/pp_handover_ab.txt).
 //
 // Fragment reads of K tile g:  phase A: b0, b1, a0    phase B: a1 (into a0's registers);  quadrants (a0,b0) (a0,b1) | (a1,b1) (a1,b0).
 // Group x executes the L part of phase p (A = 0, B = 1) in barrier interval 2p + x and RETIRES its reads (lgkmcnt(0)) before
@@ -715,6 +724,13 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
   constexpr bool MXM = IsMx<T>::v;      // M6 rows: odd K tiles are MX tiles (16 scaled MFMAs per phase instead of 32 plain ones)
   constexpr bool X3M = IO<T>::split && !IsMx<T>::v;      // hi | lo K tiles: 24 instead of 16 MFMAs per phase, (W hi, A hi) (W hi, A lo) (W lo, A hi)
   constexpr int BM = 256, BN = 256, BK = 64, TM = 128, TN = 64, MI = 8, NI = 4;
+  // MFMAs of an M part issued BEHIND the barrier that closes it (0: the barrier follows the M part, the schedule before the overlapped
+  // hand-over, instruction for instruction), per kind of M part: 2 / 4 / 6 / 8 measured alike for x3 (-2.8 % of the encoder GEMMs), 2 best
+  // for the plain 16-bit modes (-1.9 %), every candidate of the M6 tiles neutral or worse (profiles/pp_handover_ab.txt)
+  constexpr int TAIL_X3 = 2, TAIL_H16 = 2, TAIL_M6_HI = 0, TAIL_M6_MX = 0;
+  // Priority of the tail.  At EQUAL priority the SIMD's arbiter prefers the older wave: row group 1's tail then waits behind the
+  // whole M part of row group 0 and its L part slides out from under it (stamps: intervals 1 320 / 828 instead of 1 010) — +4-8 %.
+  constexpr int TAIL_PRIO = 2;
   constexpr int HTILE = 128 * BK;                      // elements per half-tile (16 KB)
   constexpr int BUF = 4 * HTILE;                       // elements per K-tile buffer: [A0 | A1 | B0 | B1]
   __shared__ __attribute__((aligned(16))) HT smem[2 * BUF];
@@ -842,14 +858,16 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
   const int fb0 = (2 + (wc >> 1)) * HTILE + (wc & 1) * 64 * BK + frag0, fb1 = fb0 ^ 32;
   [[maybe_unused]] const MxOff mxo = mx_offsets(fr, fg);
 
-#define WSEG_PP_QUADRANT(JA, IB)                                                                                      \
-  _Pragma("unroll") for (int kk = 0; kk < (X3M ? 3 : 2); ++kk)                                                        \
-    _Pragma("unroll") for (int i = 2 * (IB); i < 2 * (IB) + 2; ++i)                                                   \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                   \
-        acc[i][4 * (JA) + j] = H16<HT>::mfma16(bfr[i][X3M ? (kk >> 1) : kk], afr[j][X3M ? (kk & 1) : kk], acc[i][4 * (JA) + j]);
+  // The M part of a phase is ONE numbered sequence of MFMAs — quadrant (JA, IB0) then (JA, IB1), each kk-major over its 2 x 4 output
+  // tiles — so that it can be cut anywhere: MFMAs [FROM, TO) of the NM (32; 48 in the split-precision modes).
+#define WSEG_PP_RUN(JA, IB0, IB1, FROM, TO)                                                                           \
+  _Pragma("unroll") for (int n = (FROM); n < (TO); ++n) {                                                             \
+    const int ib = n < NM / 2 ? (IB0) : (IB1), kk = (n % (NM / 2)) / 8, i = 2 * ib + (n % 8) / 4, j = n % 4;          \
+    acc[i][4 * (JA) + j] = H16<HT>::mfma16(bfr[i][X3M ? (kk >> 1) : kk], afr[j][X3M ? (kk & 1) : kk], acc[i][4 * (JA) + j]); \
+  }
   // closes an L part (this wave's fragment reads have RETURNED before it signals: the stage may be refilled behind this barrier)
-  // and runs the M part of two quadrants
-#define WSEG_PP_MFMA(JA, IB0, IB1)                                                                                    \
+  // and takes the matrix pipe
+#define WSEG_PP_ENTER()                                                                                               \
   do {                                                                                                                \
     WSEG_PP_STAMP(pp_phase, 1);                                                                                       \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
@@ -857,11 +875,21 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
     WSEG_PP_STAMP(pp_phase, 2);                                                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                                                \
     __builtin_amdgcn_s_setprio(1);                                                                                    \
-    WSEG_PP_QUADRANT(JA, IB0)                                                                                         \
-    WSEG_PP_QUADRANT(JA, IB1)                                                                                         \
+  } while (0)
+#define WSEG_PP_LEAVE()                                                                                               \
+  do {                                                                                                                \
     __builtin_amdgcn_s_setprio(0);                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                                \
     WSEG_PP_STAMP(pp_phase, 3);                                                                                       \
+  } while (0)
+  // the barrier that closes an M part, issued TAIL MFMAs early, the tail above the entering wave's priority (the fences keep the
+  // compiler from moving an MFMA across the barrier)
+#define WSEG_PP_HANDOVER()                                                                                            \
+  do {                                                                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                                \
+    __builtin_amdgcn_s_setprio(TAIL_PRIO);                                                                            \
+    __builtin_amdgcn_s_barrier();                                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                                                \
   } while (0)
 
   int g = 0;                                           // K tiles consumed so far
@@ -885,6 +913,7 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
     const bool first = !MID && kt == 0 && g > 0, final = !MID && kt == nkt - 1;
     constexpr int PAR = MXM ? 0 : -1;                  // this tile's LDS buffer (M6 rows: hi tiles in buffer 0), -1: g & 1
     constexpr int NPAR = MXM ? 1 : -1;
+    constexpr int NM = X3M ? 48 : 32, TAIL = X3M ? TAIL_X3 : (MXM ? TAIL_M6_HI : TAIL_H16);
     const HT* cur = smem + (MXM ? 0 : (g & 1)) * BUF;
     bf16x8 afr[4][2], bfr[NI][2];
     // ---- phase A: b0, b1, a0 -> quadrants (a0, b0), (a0, b1); A pair of K tile g+1 ----
@@ -904,8 +933,14 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
     if (first && g + 1 < KT) issue_b(NPAR);                     // B pair of K tile g+1, held back over the epilogue
     if (MID || g + 1 < KT) issue_a(NPAR);                       // A pair of K tile g+1
     __builtin_amdgcn_sched_barrier(0);
-    WSEG_PP_MFMA(0, 0, 1);
-    __builtin_amdgcn_s_barrier();
+    WSEG_PP_ENTER();
+    WSEG_PP_RUN(0, 0, 1, 0, NM - TAIL);
+    if constexpr (TAIL > 0) {
+      WSEG_PP_HANDOVER();
+      WSEG_PP_RUN(0, 0, 1, NM - TAIL, NM);
+    }
+    WSEG_PP_LEAVE();
+    if constexpr (TAIL == 0) __builtin_amdgcn_s_barrier();
     // ---- phase B: a1 -> quadrants (a1, b1), (a1, b0); B pair of K tile g+2, retire K tile g+1 ----
     pp_phase = 1;
     WSEG_PP_STAMP(1, 0);
@@ -922,9 +957,26 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
     if (pb) issue_b(PAR);                                           // B pair of K tile g+2
     if (wr == 1) { if (pb) wait_vmcnt<8>(); else wait_vmcnt<4>(); }
     __builtin_amdgcn_sched_barrier(0);
-    WSEG_PP_MFMA(1, 1, 0);
-    if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
-    if (!final) __builtin_amdgcn_s_barrier();
+    WSEG_PP_ENTER();
+    WSEG_PP_RUN(1, 1, 0, 0, NM - TAIL);
+    if constexpr (TAIL > 0) {
+      // the retirement of K tile g+1 stays in front of the barrier (the other group relies on it), hence in front of the tail; the
+      // last K tile of an output tile has no closing barrier and retires behind its MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+      if (!final) {
+        __builtin_amdgcn_s_setprio(TAIL_PRIO);
+        if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      WSEG_PP_RUN(1, 1, 0, NM - TAIL, NM);
+      WSEG_PP_LEAVE();
+      if (final) wait_vmcnt<0>();
+    } else {
+      WSEG_PP_LEAVE();
+      if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
+      if (!final) __builtin_amdgcn_s_barrier();
+    }
   };
   [[maybe_unused]] auto mx_tile = [&](int kt, auto mid_tag) {
     constexpr bool MID = decltype(mid_tag)::value;
@@ -935,6 +987,7 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
       const unsigned aT = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(cur + wr * HTILE);      // this row group's 128-row A half-tile
       const unsigned bT = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(cur + (2 + (wc >> 1)) * HTILE + (wc & 1) * 64 * BK);   // this wave's 64 W rows
       MxFrag7 bm[NI], am[4];
+      constexpr int TAIL = TAIL_M6_MX;
       WSEG_PP_STAMP(0, 0);
       const lds_cp a0 = (lds_cp)(uintptr_t)(aT + (unsigned)mxo.p0), a1 = (lds_cp)(uintptr_t)(aT + (unsigned)mxo.p1);
       const lds_cp b0 = (lds_cp)(uintptr_t)(bT + (unsigned)mxo.p0), b1 = (lds_cp)(uintptr_t)(bT + (unsigned)mxo.p1);
@@ -950,13 +1003,16 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int i = 0; i < NI; ++i)
+      for (int n = 0; n < 16 - TAIL; ++n) mfma_mx6_asm(acc[n / 4][n % 4], bm[n / 4], am[n % 4]);
+      if constexpr (TAIL > 0) {
+        WSEG_PP_HANDOVER();
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mfma_mx6_asm(acc[i][j], bm[i], am[j]);
+        for (int n = 16 - TAIL; n < 16; ++n) mfma_mx6_asm(acc[n / 4][n % 4], bm[n / 4], am[n % 4]);
+      }
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       WSEG_PP_STAMP(0, 3);
-      __builtin_amdgcn_s_barrier();
+      if constexpr (TAIL == 0) __builtin_amdgcn_s_barrier();
       WSEG_PP_STAMP(1, 0);
       am[0] = ld_mx_frag7<8192>(a0, a1); am[1] = ld_mx_frag7<10240>(a0, a1); am[2] = ld_mx_frag7<12288>(a0, a1); am[3] = ld_mx_frag7<14336>(a0, a1);
       const bool pb = MID || (!final && g + 2 < KT);
@@ -970,14 +1026,28 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int i = 0; i < NI; ++i)
+      for (int n = 0; n < 16 - TAIL; ++n) mfma_mx6_asm(acc[n / 4][4 + n % 4], bm[n / 4], am[n % 4]);
+      if constexpr (TAIL > 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (!final) {
+          __builtin_amdgcn_s_setprio(TAIL_PRIO);
+          if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
+          __builtin_amdgcn_s_barrier();
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mfma_mx6_asm(acc[i][4 + j], bm[i], am[j]);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
-      WSEG_PP_STAMP(1, 3);
-      if (!final) __builtin_amdgcn_s_barrier();
+        for (int n = 16 - TAIL; n < 16; ++n) mfma_mx6_asm(acc[n / 4][4 + n % 4], bm[n / 4], am[n % 4]);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (final) wait_vmcnt<0>();
+        WSEG_PP_STAMP(1, 3);
+      } else {
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (pb) wait_vmcnt<4>(); else wait_vmcnt<0>();
+        WSEG_PP_STAMP(1, 3);
+        if (!final) __builtin_amdgcn_s_barrier();
+      }
   };
   constexpr std::false_type EDGE{};
   constexpr std::true_type MIDDLE{};
@@ -1019,8 +1089,10 @@ __global__ __launch_bounds__(512) void gemm_h16_pp_kernel(const typename IO<T>::
     if (wr == 1) __builtin_amdgcn_s_barrier();
   }
   }
-#undef WSEG_PP_MFMA
-#undef WSEG_PP_QUADRANT
+#undef WSEG_PP_HANDOVER
+#undef WSEG_PP_LEAVE
+#undef WSEG_PP_ENTER
+#undef WSEG_PP_RUN
   if (wr == 0) __builtin_amdgcn_s_barrier();          // pair group 1's extra barrier
 }
 
