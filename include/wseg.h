@@ -457,6 +457,40 @@ int wseg_pitch_frames_f64(const float* pcm, int64_t n, const int64_t* bounds_hos
                           void* scratch, size_t scratch_bytes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-segment signal-to-noise ratio from the resident PCM: how far a row lies above the recording's noise floor.
+ * whisperseg_amd/snr.py holds the definition (numpy, float64).  Two calls, so that each stage can be pinned on its own.
+ * wseg_frame_energy_f32: the band-energy track of a recording.  pcm: device float32 [n]; n_fft 512 .. 8192 (a power of two), hop =
+ * n_fft / 4; window: device float32 [n_fft]; twiddle: device float32 [n_fft / 2][2] (W_n^k, 8-byte aligned), the log-mel
+ * descriptor's.  WHOLE frames only: frame j = pcm[j hop : j hop + n_fft], J = wseg_frame_energy_frames(n, n_fft) = 0 for n < n_fft,
+ * else 1 + (n - n_fft) / hop (host arithmetic; -1 with the reason in wseg_last_error() for an n_fft that is none or n outside
+ * 0 .. 2^52) — no sample at or behind n is ever read.  track_out: device float32 [J], E[j] = sum_{k = k_lo .. k_hi}
+ * |rfft(window * frame_j)[k]|^2, 0 <= k_lo <= k_hi <= n_fft / 2: the transform in fp32, the band sum in fp64 in a fixed order,
+ * rounded to float32 once; the same bits on every run and for every grid.  Nothing outside the J values is written; J == 0 returns 0
+ * without a launch.
+ * wseg_snr_rows_f64: per row the mean and the maximum of its frames' energies and the noise floor of its window.  track: device
+ * float32 [J], non-negative values, +inf and NaN (a NaN sorts last, as numpy.sort has it; negative values: unspecified).
+ * table_host: HOST int64 [n_seg][3] = (j0, j1, window): the row's signal frames [j0, j1), 0 <= j0 <= j1 <= J, and the index of its
+ * window in windows_host.  windows_host: HOST int64 [n_win][3] = (w0, w1, r): the frames [w0, w1), 0 <= w0 < w1 <= J, and the rank
+ * 0 <= r <= w1 - w0 - 1.  All time arithmetic is the caller's.  Equal triples are selected once.
+ * rows_out: device float64 [n_seg][3] = (S, M, N): S the float64 sum of the float32 energies of [j0, j1) over their count, M their
+ * maximum (NaN if one is NaN), N = sort(track[w0:w1])[r] EXACTLY (a radix select over the bit patterns: integer counts only, the
+ * same bits for every grid; a NaN floor is the quiet NaN); a row with j0 == j1 gets three NaN.
+ * scratch: device, 8-byte aligned, wseg_snr_rows_scratch_bytes(J, table_host, n_seg, windows_host, n_win) bytes — host arithmetic,
+ * no device; 0 with the reason in wseg_last_error() for invalid input.  The call copies its tables through a pinned buffer of the
+ * library's on the stream and waits for nothing: both host arrays may be reused on return.  The number of launches depends on the
+ * windows' lengths only, never on the track's values.  n_seg == 0 returns 0 without a launch.  Every argument is validated on the
+ * host before a launch (WSEG_ERR_INVALID, the argument's name in wseg_last_error()).  Stream-ordered, no host synchronisation.
+ * $WSEG_SNR_GRID: a TEST knob, the cap on the grids (the same bits for every value).
+ * Added without moving WSEG_ABI_VERSION (an addition).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t wseg_frame_energy_frames(int64_t n, int32_t n_fft);
+int wseg_frame_energy_f32(const float* pcm, int64_t n, int32_t n_fft, int32_t k_lo, int32_t k_hi, const float* window,
+                          const float* twiddle, float* track_out, void* stream);
+size_t wseg_snr_rows_scratch_bytes(int64_t J, const int64_t* table_host, int32_t n_seg, const int64_t* windows_host, int32_t n_win);
+int wseg_snr_rows_f64(const float* track, int64_t J, const int64_t* table_host, int32_t n_seg, const int64_t* windows_host,
+                      int32_t n_win, void* scratch, size_t scratch_bytes, double* rows_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Whisper encoder-decoder.
  * Replaces HF WhisperForConditionalGeneration as the reference drives it:
  *   construction  reference model.py:626-644 (WhisperSegmenter.__init__, from_pretrained)

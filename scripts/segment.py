@@ -61,6 +61,14 @@ estimator takes at the recording's rate (2 sr / n_fft .. sr / 8), X (0 < X < 1, 
 `frame_time` (seconds), all float [frames], the frames of row 0, then of row 1, ... in the CSV's row order, `frame_offsets` int64
 [rows + 1] — row r owns the frames frame_offsets[r] .. frame_offsets[r + 1] — and `onset`, `offset`, `cluster`, `filename` / `channel`
 as --patches_save_path has them.
+--snr [--snr_quantile Q] [--snr_context SECONDS] appends four signal-to-noise columns behind the pitch columns
+(whisperseg_amd.snr.COLUMNS: the row's level and the recording's noise floor in dB re a full-scale sine inside the band, their ratio
+and the ratio of the row's loudest frame to the floor), rated on the GPU in the samples the rows were cut from: the floor is the
+Q-quantile (0 <= Q <= 1, default 0.1) of the band energy of every frame of the recording or, with --snr_context, of the frames up
+to SECONDS around the row.
+--snr_save_path FILE.npz (needs --snr) saves the band-energy tracks themselves: `frame_energy` float32 [frames], the frames of
+recording 0, then of recording 1, ... (a recording is a file, or with --channel_id all a channel of a file, in the CSV's order),
+`frame_offsets` int64 [recordings + 1], `hop` and `n_fft` int64 [recordings] in samples of the rate the recording was segmented at.
 --audio_ext EXT [EXT ...] names the extensions folder mode looks for: for each one in order `*.ext`, then `*.EXT`; absent, `*.wav`
 then `*.WAV`, as in the reference's CLI.
 """
@@ -79,6 +87,7 @@ from model import WhisperSegmenter, WhisperSegmenterFast  # noqa: E402  (root-le
 from whisperseg_amd import dtw as DW, embed as EM, library as LB, linkage as LK, neighbors as NB, pca as PC, resident as RS  # noqa: E402
 from whisperseg_amd.measure import COLUMNS as MEASURE_COLUMNS  # noqa: E402
 from whisperseg_amd.pitch import COLUMNS as PITCH_COLUMNS  # noqa: E402
+from whisperseg_amd.snr import COLUMNS as SNR_COLUMNS  # noqa: E402
 from whisperseg_amd.wavio import load_audio, load_wav_device  # noqa: E402
 
 
@@ -146,6 +155,12 @@ def build_parser():
     p.add_argument("--pitch_max_hz", default=None, type=float, metavar="F", help="--pitch: the highest fundamental looked for (default sr / 8)")
     p.add_argument("--pitch_threshold", default=None, type=float, metavar="X", help="--pitch: YIN's threshold, 0 < X < 1 (default 0.1)")
     p.add_argument("--pitch_save_path", default=None, metavar="FILE.npz", help="--pitch: where to save the pitch contours (numpy .npz)")
+    p.add_argument("--snr", action="store_true",
+                   help="append the four per-segment signal-to-noise columns (signal_level_db .. peak_snr_db) to every row")
+    p.add_argument("--snr_quantile", default=None, type=float, metavar="Q", help="--snr: the noise floor is this quantile of the frame energies, 0 <= Q <= 1 (default 0.1)")
+    p.add_argument("--snr_context", default=None, type=float, metavar="SECONDS",
+                   help="--snr: take the floor from the frames up to SECONDS around a row (default: from the whole recording)")
+    p.add_argument("--snr_save_path", default=None, metavar="FILE.npz", help="--snr: where to save the band-energy tracks (numpy .npz)")
     return p
 
 
@@ -159,7 +174,8 @@ def parse_args(argv=None):
     --pitch_save_path without --pitch, a frequency that is not positive, a range that is none, a threshold outside (0, 1) and a
     --pitch_save_path that does not end with .npz.  --onto without the patches, with --clusters, --embed or --pca, or with a
     LIBRARY that does not end with .npz is one too; with --onto, --embed_neighbors, --embed_min_dist, --embed_seed and
-    --cluster_min_samples need no --embed / --clusters."""
+    --cluster_min_samples need no --embed / --clusters.  --snr_quantile, --snr_context or --snr_save_path without --snr, a Q outside
+    [0, 1], a negative or non-finite context and a --snr_save_path that does not end with .npz are errors as well."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.onto is not None:
@@ -235,6 +251,15 @@ def parse_args(argv=None):
         parser.error("--pitch_threshold must lie in (0, 1)")
     if args.pitch_save_path is not None and not args.pitch_save_path.endswith(".npz"):
         parser.error("--pitch_save_path must end with .npz")
+    for name in ("snr_quantile", "snr_context", "snr_save_path"):
+        if getattr(args, name) is not None and not args.snr:
+            parser.error(f"--{name} needs --snr")
+    if args.snr_quantile is not None and not 0 <= args.snr_quantile <= 1:
+        parser.error("--snr_quantile must lie in [0, 1]")
+    if args.snr_context is not None and not 0 <= args.snr_context < float("inf"):
+        parser.error("--snr_context must be a non-negative number of seconds")
+    if args.snr_save_path is not None and not args.snr_save_path.endswith(".npz"):
+        parser.error("--snr_save_path must end with .npz")
     return args
 
 
@@ -246,6 +271,16 @@ def pitch_keyword(args):
              if value is not None}
     if args.pitch_save_path is not None:
         given["contour"] = True
+    return given or True
+
+
+def snr_keyword(args):
+    """The `snr=` of the segmenter calls for the parsed flags (None without --snr): True, or the dict of what was given."""
+    if not args.snr:
+        return None
+    given = {key: value for key, value in (("quantile", args.snr_quantile), ("context", args.snr_context)) if value is not None}
+    if args.snr_save_path is not None:
+        given["track"] = True
     return given or True
 
 
@@ -264,13 +299,13 @@ def write_csv(columns, rows, dest):
         w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
-def table(results, names=None, all_channels=False, measure=False, pitch=False):
+def table(results, names=None, all_channels=False, measure=False, pitch=False, snr=False):
     """-> (columns, rows) of the CSV.  `results`: one prediction dict per recording, or with all_channels one LIST of dicts (one
     per channel) per recording, which adds the `channel` column; `names`: the recordings' file names for the `filename` column
     (folder mode); `measure`: the dicts carry the eight measurement columns, appended behind `cluster`; `pitch`: the seven pitch
-    columns, behind those.  Rows run in file, channel, row order."""
+    columns, behind those; `snr`: the four signal-to-noise columns, behind those.  Rows run in file, channel, row order."""
     columns = (["filename"] if names is not None else []) + (["channel"] if all_channels else []) + ["onset", "offset", "cluster"]
-    extra = (list(MEASURE_COLUMNS) if measure else []) + (list(PITCH_COLUMNS) if pitch else [])
+    extra = (list(MEASURE_COLUMNS) if measure else []) + (list(PITCH_COLUMNS) if pitch else []) + (list(SNR_COLUMNS) if snr else [])
     columns += extra
     rows = []
     for i, res in enumerate(results):
@@ -313,6 +348,16 @@ def pitch_archive(results, names=None, all_channels=False):
             "frame_time": joined("frame_time", np.float64),
             "frame_offsets": np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64),
             **identifying_columns(results, names, all_channels)}
+
+
+def snr_archive(results, all_channels=False):
+    """-> {name: array} of the signal-to-noise .npz: the tracks of all recordings back to back, their offsets, hops and transform sizes,
+    in table()'s recording order."""
+    flat = [r for res in results for r in (res if all_channels else [res])]
+    tracks = [np.asarray(r["frame_energy"], dtype=np.float32) for r in flat]
+    return {"frame_energy": np.concatenate(tracks or [np.zeros(0, np.float32)]),
+            "frame_offsets": np.concatenate([[0], np.cumsum([len(t) for t in tracks], dtype=np.int64)]).astype(np.int64),
+            "hop": np.array([r["hop"] for r in flat], dtype=np.int64), "n_fft": np.array([r["n_fft"] for r in flat], dtype=np.int64)}
 
 
 def analyses(patch, args, device="cuda"):
@@ -376,7 +421,8 @@ def main(argv=None):
     kwargs = dict(min_frequency=args.min_frequency, spec_time_step=args.spec_time_step, num_trials=args.num_trials,
                   batch_size=args.batch_size, **({"measure": True} if args.measure else {}),      # (absent: the calls as they were)
                   **({} if args.patches is None else {"patches": args.patches}),
-                  **({} if not args.pitch else {"pitch": pitch_keyword(args)}))
+                  **({} if not args.pitch else {"pitch": pitch_keyword(args)}),
+                  **({} if not args.snr else {"snr": snr_keyword(args)}))
     rate = {} if args.sr is None else {"sr": args.sr}        # (absent: the calls as they were)
     if args.audio_path is None:
         assert args.audio_folder is not None, "Either audio_path or audio_folder needs to be specified!"
@@ -400,7 +446,9 @@ def main(argv=None):
             tabled = ([segmenter.segment_channels(audio, sr, **kwargs)], None, True)
         else:
             tabled = ([segmenter.segment(audio, sr, **kwargs)], None, False)
-    columns, rows = table(*tabled, measure=args.measure, pitch=args.pitch)
+    columns, rows = table(*tabled, measure=args.measure, pitch=args.pitch, **({"snr": True} if args.snr else {}))
+    if args.snr_save_path is not None:
+        np.savez(args.snr_save_path, **snr_archive(tabled[0], tabled[2]))
     if args.pitch_save_path is not None:
         np.savez(args.pitch_save_path, **pitch_archive(*tabled))
     if args.patches is not None:

@@ -106,6 +106,12 @@ SYMBOLS = {
     "wseg_pitch_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "wseg_pitch_frames_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "wseg_frame_energy_frames": (C.c_int64, [C.c_int64, C.c_int32]),
+    "wseg_frame_energy_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "wseg_snr_rows_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "wseg_snr_rows_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_void_p]),
     "wseg_model_create": (C.c_int, [C.POINTER(ModelConfig), C.POINTER(C.c_void_p)]),
     "wseg_model_destroy": (None, [C.c_void_p]),
     "wseg_model_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),

@@ -292,7 +292,8 @@ class SegmenterBase:
     @torch.no_grad()
     def segment(self, audio, sr, min_frequency=None, spec_time_step=None, min_segment_length=None, eps=None,
                 time_per_frame_for_voting=None, consolidation_method="clustering", max_length=448, batch_size=4,
-                num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False, patches=None, pitch=None):
+                num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False, patches=None, pitch=None,
+                snr=None):
         """`measure=True`: every prediction dict additionally carries the eight columns of whisperseg_amd.measure.COLUMNS as
         lists aligned with `onset` — level, peak frequency, centroid, 5 % / 95 % frequencies and entropy of every returned row,
         measured on the GPU from the device PCM the front-end read, in the band min_frequency .. sr / 2.
@@ -303,8 +304,13 @@ class SegmenterBase:
         columns of whisperseg_amd.pitch.COLUMNS as lists aligned with `onset` — the fundamental frequency of every returned row (mean,
         extremes, first and last of its YIN contour, the voiced fraction and the aperiodicity), computed on the GPU from the same
         held PCM; with `contour=True` also the per-row contours (pitch.CONTOUR_KEYS).  A range whose lags the estimator does not
-        take is a ValueError before anything runs."""
-        hold = self._holds_pcm(measure, patches, pitch, sr)
+        take is a ValueError before anything runs.
+        `snr=True`, or a dict of `quantile`, `context`, `max_frequency`, `track`: every prediction dict additionally carries the four
+        columns of whisperseg_amd.snr.COLUMNS as lists aligned with `onset` — the level of every returned row, the noise floor of the
+        recording (the `quantile`, default 0.1, of its band-energy track; with `context` seconds, of the frames that far around the
+        row) and their ratios in dB — computed on the GPU from the same held PCM in the band min_frequency .. `max_frequency`; with
+        `track=True` also the recording's track (snr.TRACK_KEYS)."""
+        hold = self._holds_pcm(measure, patches, pitch, sr, snr)
         min_frequency, spec_time_step, min_segment_length, eps, time_per_frame_for_voting = self.resolve_segmentation_params(
             min_frequency, spec_time_step, min_segment_length, eps, time_per_frame_for_voting)
         held = [] if hold else None      # (absent: the call as it was)
@@ -316,23 +322,27 @@ class SegmenterBase:
                                            num_trials, eps, time_per_frame_for_voting, consolidation_method)
         prediction = postprocess.correct_fft_blur(prediction, get_n_fft_given_sr(sr), sr)
         prediction = postprocess.drop_consecutive_duplicates(prediction)
-        return self._finished(prediction, held[0], sr, min_frequency, measure, patches, pitch) if hold else prediction
+        return self._finished(prediction, held[0], sr, min_frequency, measure, patches, pitch, snr) if hold else prediction
 
     @staticmethod
-    def _holds_pcm(measure, patches, pitch=None, sr=None):
-        """Whether a call keeps the device PCM of its recordings for its final rows; a `patches` that is no width and a `pitch` that
-        is no option set — or, where the rate is known, no lag range at `sr` — fail here, before any device work."""
+    def _holds_pcm(measure, patches, pitch=None, sr=None, snr=None):
+        """Whether a call keeps the device PCM of its recordings for its final rows; a `patches` that is no width, a `pitch` that
+        is no option set — or, where the rate is known, no lag range at `sr` — and an `snr` that is no option set fail here, before
+        any device work."""
         if patches is not None:
             from .patches import check_width
             check_width(patches)
         if pitch is not None:
             from .pitch import options
             options(pitch, sr)
-        return bool(measure) or patches is not None or pitch is not None
+        if snr is not None:
+            from .snr import options as snr_options
+            snr_options(snr)
+        return bool(measure) or patches is not None or pitch is not None or snr is not None
 
     @staticmethod
-    def _finished(prediction, pcm, sr, min_frequency, measure, patches, pitch=None):
-        """The final rows of a recording + what was asked for of its device PCM: the measurements, the pitch, the pictures, or all
+    def _finished(prediction, pcm, sr, min_frequency, measure, patches, pitch=None, snr=None):
+        """The final rows of a recording + what was asked for of its device PCM: the measurements, the pitch, the ratios, the pictures, or all
         (a launch or a launch pair each; only the rows come back)."""
         out = prediction
         if measure:
@@ -341,6 +351,9 @@ class SegmenterBase:
         if pitch is not None:
             from . import pitch as F0
             out = F0.with_columns(out, F0.pitch(pcm, sr, prediction, **F0.options(pitch, sr)))
+        if snr is not None:
+            from . import snr as SN
+            out = SN.with_columns(out, SN.snr(pcm, sr, prediction, min_frequency=min_frequency, **SN.options(snr, sr, min_frequency)))
         if patches is not None:
             from . import patches as P
             out = P.with_patch(out, P.patches(pcm, sr, prediction, width=patches, min_frequency=min_frequency))
@@ -350,7 +363,8 @@ class SegmenterBase:
     @torch.no_grad()
     def segment_batch(self, audios, srs=None, min_frequency=None, spec_time_step=None, min_segment_length=None, eps=None,
                       time_per_frame_for_voting=None, consolidation_method="clustering", max_length=448, batch_size=4,
-                      num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False, patches=None, pitch=None):
+                      num_trials=1, num_beams=4, top_k=1, top_p=1.0, length_penalty=1.0, status_monitor=None, measure=False, patches=None, pitch=None,
+                      snr=None):
         """segment() for a list of recordings with their windows POOLED into shared decode batches.
 
         The reference batches only inside one file (model.py:653) and its folder mode is a serial loop
@@ -370,6 +384,7 @@ class SegmenterBase:
         `patches=W` as in segment(): the pictures of a group's rows are taken on the same held PCM.
         `pitch=True` / a dict as in segment(): the pitch columns of a group's rows, from the same held PCM; a recording at whose
         rate the range gives no valid lags raises when it is taken, before its front-end runs.
+        `snr=True` / a dict as in segment(): the four ratio columns of a group's rows, each recording's floor taken from its own held PCM.
         Returns a list of prediction dicts."""
         if srs is None:
             pairs = iter(audios)
@@ -379,7 +394,7 @@ class SegmenterBase:
             pairs = zip(audios, srs)
         per_item = [_per_item(v) for v in (min_frequency, spec_time_step, min_segment_length, eps, time_per_frame_for_voting,
                                           num_trials, consolidation_method)]
-        hold = self._holds_pcm(measure, patches, pitch)
+        hold = self._holds_pcm(measure, patches, pitch, None, snr)
         out, group, pending = [], [], 0
 
         def flush():
@@ -395,7 +410,7 @@ class SegmenterBase:
                                              g["num_trials"], g["eps"], g["frame"], g["method"])
                 pred = postprocess.correct_fft_blur(pred, get_n_fft_given_sr(g["sr"]), g["sr"])
                 pred = postprocess.drop_consecutive_duplicates(pred)
-                out.append(self._finished(pred, g["pcm"], g["sr"], g["min_frequency"], measure, patches, pitch) if hold else pred)
+                out.append(self._finished(pred, g["pcm"], g["sr"], g["min_frequency"], measure, patches, pitch, snr) if hold else pred)
             group, pending = [], 0
 
         # recordings are pooled in bounded groups (~POOL_WINDOWS windows): features of a group are freed before the next
@@ -426,7 +441,7 @@ class SegmenterBase:
         """segment() of every channel of a recording kept apart (`librosa.load(..., mono=False)` upstream, wavio.load_wav(mono=False)
         / load_wav_device(mono=False) here): `audio` is [channels, n] (numpy or a device tensor) or 1-D -> a list with one
         prediction dict per channel.  Computed as segment_batch over the rows: the windows of all channels share one pooled decode.
-        `measure=True` / `patches=W` / `pitch=` (segment_batch's) measure every channel's rows on that channel's plane."""
+        `measure=True` / `patches=W` / `pitch=` / `snr=` (segment_batch's) measure every channel's rows on that channel's plane."""
         if getattr(audio, "ndim", None) not in (1, 2):
             raise ValueError("audio must be [n] or [channels, n]")
         return self.segment_batch([audio] if audio.ndim == 1 else list(audio), sr, **segment_kwargs)
@@ -447,7 +462,7 @@ class SegmenterBase:
         piece as it is decoded, all its planes in one launch per piece (wseg_resample_planar_range_f32: no native-rate copy of the
         file), and the front-end sees the target rate.
         `measure=True` (segment_batch's): the rows are measured on the decoded — with `sr`, the resampled — device PCM of their file,
-        or of their channel's plane; no file is read twice and no PCM comes back to the host.  `patches=W` and `pitch=` likewise."""
+        or of their channel's plane; no file is read twice and no PCM comes back to the host.  `patches=W`, `pitch=` and `snr=` likewise."""
         paths = list(paths)
         if not paths:
             return []
