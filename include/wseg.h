@@ -741,6 +741,45 @@ int wseg_debug_gemm_out_is_mx(int32_t dtype, int32_t M, int32_t N, int32_t K);
 int wseg_debug_gemm_resid_ln(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, const void* W, const void* bias, void* x,
                              const void* gamma, const void* beta, void* y, void* splitk_ws, size_t splitk_ws_bytes, void* stream);
 
+/* Model-free taps of the decode step's cross-attention and of the K / V rows it reads (tests/test_cross_attn_gpu.py,
+ * oracle/cross_kv.py): caller-owned device memory, no model, no workspace plan, no arithmetic of their own.  d = 64 n_heads.
+ *
+ * wseg_debug_cross_kv_bytes (host only): bytes of ONE cross K (or V) buffer of n_slots slots and, in *format (may be NULL), the
+ * storage the mode takes at this beam count: 0 plain rows [slot][head][t_len][64] (fp32 in the split modes), 2 / 3 the packed
+ * block-floating-point rows (132 / 196 bytes per (position, head) row).  0 with the reason in wseg_last_error() for an
+ * unsupported geometry.
+ *
+ * wseg_debug_cross_kv: the cross K / V projection of one decoder layer exactly as the encode pass of wseg_generate launches it:
+ * k | v = a w^T + bias through the library's GEMM with the K / V epilogue, rows of window i into slot slot_map[i] (NULL: slot i).
+ *   a         operand rows of the mode [n_windows * t_len][d] (fp32 / 16-bit rows; hi | lo rows; M6 rows), a_bytes must cover
+ *             the row count rounded up to 256
+ *   w, bias   weight operand rows [2 d][d] (M6: weight order) and the bias [2 d] in the mode's parameter type (NULL: none)
+ *   slot_map  device [n_windows], distinct slots; read back and checked before the launch
+ *   plan_m    the row count the launch is PLANNED for (>= the rows launched; wseg_generate: a whole encoder chunk), which fixes the
+ *             kernel family and with it the summation order
+ *   k, v      device buffers of kv_bytes >= wseg_debug_cross_kv_bytes each; splitk_ws: the GEMM's split-K workspace (the packed rows
+ *             need it whenever the plan is the weight-stream family)
+ *
+ * wseg_debug_cross_attention: the decode step's cross-attention launcher on such buffers.  Query row r = window * num_beams + beam;
+ * window w reads the K / V of slot kv_slot[w] (NULL: slot w; the map exists for the packed rows only).  The query is given either
+ *   q         finished, pre-scaled rows [R][d] in the mode's plain type (fp32; 16-bit in WSEG_BF16 / WSEG_F16), or
+ *   q_part    split-K partial planes fp32 [q_splits][m_pad][d], m_pad >= R, which the kernel sums in plane order, adds q_bias [d]
+ *             (may be NULL) to and multiplies by `scale` (not WSEG_F32).
+ * done: device [n_windows], 1 = the window is idle and its output rows stay untouched.  out: [R][d] in the mode's operand format
+ * (fp32 / 16-bit rows, hi | lo rows, M6 rows from the 16-bit block-floating-point kernel), out_bytes must cover it.
+ *
+ * Both taps check every argument on the host before anything is launched (WSEG_ERR_INVALID, the argument's name in
+ * wseg_last_error()) and synchronise the stream.  Not covered by them: the co-proj GEMM behind the attention, the scheduler's
+ * admission and the replay of the step graph. */
+size_t wseg_debug_cross_kv_bytes(int32_t dtype, int32_t num_beams, int32_t n_slots, int32_t n_heads, int32_t t_len, int32_t* format);
+int wseg_debug_cross_kv(int32_t dtype, int32_t num_beams, int32_t n_windows, int32_t n_slots, int32_t t_len, int32_t n_heads,
+                        int32_t plan_m, const void* a, size_t a_bytes, const void* w, const void* bias, const int32_t* slot_map,
+                        void* k, void* v, size_t kv_bytes, void* splitk_ws, size_t splitk_ws_bytes, void* stream);
+int wseg_debug_cross_attention(int32_t dtype, int32_t num_beams, int32_t n_windows, int32_t n_slots, int32_t t_len, int32_t n_heads,
+                               const void* q, const float* q_part, int32_t q_splits, int32_t m_pad, const void* q_bias, float scale,
+                               const int32_t* done, const int32_t* kv_slot, const void* k, const void* v, size_t kv_bytes, void* out,
+                               size_t out_bytes, void* stream);
+
 /* Test tap of the cross-lane exchanges every wave reduction of the library is built on (csrc/wseg_common.h lane_xor<M>: DPP
  * quad_perm / row_shl / row_shr / row_ror, v_permlane16_swap, v_permlane32_swap instead of ds_bpermute): out[m][l] = the value
  * lane l ^ (1 << m) holds, for m = 0..5 and l = 0..63, where lane l holds 7 l + 3.  out: device, 6 * 64 uint32.

@@ -138,6 +138,12 @@ SYMBOLS = {
     "wseg_debug_gemm_out_is_mx": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "wseg_debug_gemm_resid_ln": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wseg_debug_cross_kv_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "wseg_debug_cross_kv": (C.c_int, [C.c_int32] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wseg_debug_cross_attention": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
     "wseg_debug_lane_xor": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wseg_profile_begin": (C.c_int, []),
     "wseg_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

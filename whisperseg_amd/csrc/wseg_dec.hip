@@ -1541,7 +1541,7 @@ static void launch_cross_t(const DecodeState& st, const void* q, const void* ck,
 // wseg_kernels.h.  The three-MFMA modes' GEMMs are exact to ~6e-6 of a logit on the parity sweeps' models; the 24-bit FLOAT rows they
 // stored from r03 to mid r06 added 2e-5 — which cost f16x3 one of 4 200 sweep recordings (a greedy decision with a margin of 2.8e-5;
 // fp32 rows reproduce it) —, 16-bit block-floating-point rows 6e-5: since r06 these modes store 24-bit block floating point (format 3:
-// CrossKv<3>, error <= 2^-24 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven sweeps.  The
+// CrossKv<3>, error <= 2^(ceil(log2 max) - 24): between 2^-24 and 2^-23 of the row maximum), with which f16x3 reproduces all 6 200 recordings of the seven sweeps.  The
 // mixed mode's own fp6 cross terms cost 8e-5: it takes the 31 % smaller 16-bit rows (format 2, 1.3e-4 in all).
 int x3_cross_kv_format(int dtype, int nb) {
   if (nb > 4) return 0;
@@ -1742,7 +1742,70 @@ static int decode_step_tap(const wseg_decode_step_params* p, const wseg_decode_s
 #undef WSEG_TRY
 }
 
+// ------------------------------------------------------------------------------------------------
+// wseg_debug_cross_attention: launch_dec_cross_attn on the caller's query, K / V and output (include/wseg.h).  Checks and the minimal
+// state the kernels read (W, nb, done); no arithmetic.
+static size_t cross_tap_elem_bytes(int dtype) { return (dtype == WSEG_BF16 || dtype == WSEG_F16) ? 2 : 4; }      // plain rows, query and output alike
+
+static int cross_attention_tap(int dtype, int nb, int W, int S, int Tk, int H, const void* q, const float* q_part, int q_splits, int m_pad,
+                               const void* q_bias, float scale, const int32_t* done, const int32_t* kv_slot, const void* k, const void* v,
+                               size_t kv_bytes, void* out, size_t out_bytes, hipStream_t s) {
+#define WSEG_TAP_REQUIRE(COND, ...) do { if (!(COND)) { set_error("wseg_debug_cross_attention: " __VA_ARGS__); return WSEG_ERR_INVALID; } } while (0)
+  WSEG_TAP_REQUIRE(dtype >= WSEG_F32 && dtype <= WSEG_F16M6, "dtype %d unsupported", dtype);
+  WSEG_TAP_REQUIRE(nb >= 1 && nb <= MAX_BEAMS, "num_beams %d unsupported (1..%d)", nb, MAX_BEAMS);
+  WSEG_TAP_REQUIRE(H >= 1 && H <= 64, "n_heads %d unsupported (1..64)", H);
+  WSEG_TAP_REQUIRE(Tk >= 1 && Tk <= 1500, "t_len %d unsupported (1..1500)", Tk);
+  WSEG_TAP_REQUIRE(S >= 1 && S <= (1 << 16), "n_slots %d unsupported (1..65536)", S);
+  WSEG_TAP_REQUIRE(W >= 1 && W <= (1 << 16) && (kv_slot || W <= S), "n_windows %d does not fit n_slots %d (%s kv_slot)", W, S, kv_slot ? "with" : "without");
+  const int d = 64 * H, R = W * nb;
+  const bool split = dtype == WSEG_BF16X3 || dtype == WSEG_F16X3 || dtype == WSEG_F16M6;
+  const int fmt = split ? x3_cross_kv_format(dtype, nb) : 0;
+  WSEG_TAP_REQUIRE(!kv_slot || fmt != 0, "kv_slot exists for the block-floating-point K / V kernels only (dtype %d, num_beams %d store plain rows)", dtype, nb);
+  WSEG_TAP_REQUIRE((q != nullptr) != (q_part != nullptr), "exactly one of q and q_part is given");
+  if (q_part) {
+    WSEG_TAP_REQUIRE(dtype != WSEG_F32, "q_part: the exact mode has no split-K planes");
+    WSEG_TAP_REQUIRE(q_splits >= 1 && q_splits <= 16, "q_splits %d unsupported (1..16)", q_splits);
+    WSEG_TAP_REQUIRE(m_pad >= R, "m_pad %d is short of the %d query rows", m_pad, R);
+    WSEG_TAP_REQUIRE(((uintptr_t)q_part & 15) == 0, "q_part is not 16-byte aligned");
+  } else {
+    WSEG_TAP_REQUIRE(!q_bias && q_splits == 0 && m_pad == 0, "q_bias, q_splits and m_pad belong to q_part");
+    WSEG_TAP_REQUIRE(((uintptr_t)q & 15) == 0, "q is not 16-byte aligned");
+  }
+  WSEG_TAP_REQUIRE(done, "done is null");
+  WSEG_TAP_REQUIRE(k, "k is null");
+  WSEG_TAP_REQUIRE(v, "v is null");
+  WSEG_TAP_REQUIRE(out, "out is null");
+  WSEG_TAP_REQUIRE((((uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0, "k, v and out must be 16-byte aligned");
+  const size_t kv_need = cross_kv_layer_bytes(fmt, cross_tap_elem_bytes(dtype), (size_t)S, (size_t)H, (size_t)Tk);
+  WSEG_TAP_REQUIRE(kv_bytes >= kv_need, "kv_bytes %zu is short of the %zu bytes of %d slots", kv_bytes, kv_need, S);
+  const size_t out_need = (size_t)R * d * cross_tap_elem_bytes(dtype);      // operand rows of a split mode: 4 bytes per column as well
+  WSEG_TAP_REQUIRE(out_bytes >= out_need, "out_bytes %zu is short of the %zu bytes of %d rows", out_bytes, out_need, R);
+  if (kv_slot) {      // what the kernels index with is checked before they run
+    std::vector<int> h_slot(W);
+    WSEG_HIP_CHECK(hipMemcpyAsync(h_slot.data(), kv_slot, (size_t)W * sizeof(int), hipMemcpyDeviceToHost, s));
+    WSEG_HIP_CHECK(hipStreamSynchronize(s));
+    for (int w = 0; w < W; ++w) WSEG_TAP_REQUIRE(h_slot[w] >= 0 && h_slot[w] < S, "kv_slot[%d] = %d is no slot of %d", w, h_slot[w], S);
+  }
+#undef WSEG_TAP_REQUIRE
+  DecodeState st = DecodeState();
+  st.W = W; st.nb = nb; st.done = const_cast<int*>(done);
+  PartialInfo pi;
+  if (q_part) { pi.part = q_part; pi.splits = q_splits; pi.m_pad = m_pad; pi.n = d; }
+  const int status = launch_dec_cross_attn(dtype, st, q, k, v, out, H, Tk, d, q_part ? &pi : nullptr, q_bias, scale, s, kv_slot);
+  if (status != WSEG_OK) return status;
+  WSEG_HIP_CHECK(hipStreamSynchronize(s));
+  return WSEG_OK;
+}
+
 }  // namespace wseg
+
+extern "C" int wseg_debug_cross_attention(int32_t dtype, int32_t num_beams, int32_t n_windows, int32_t n_slots, int32_t t_len, int32_t n_heads,
+                                          const void* q, const float* q_part, int32_t q_splits, int32_t m_pad, const void* q_bias, float scale,
+                                          const int32_t* done, const int32_t* kv_slot, const void* k, const void* v, size_t kv_bytes, void* out,
+                                          size_t out_bytes, void* stream) {
+  return wseg::cross_attention_tap(dtype, num_beams, n_windows, n_slots, t_len, n_heads, q, q_part, q_splits, m_pad, q_bias, scale, done, kv_slot,
+                                   k, v, kv_bytes, out, out_bytes, (hipStream_t)stream);
+}
 
 extern "C" size_t wseg_debug_decode_step_scratch_bytes(int32_t n_slots, int32_t num_beams, int32_t vocab) {
   if (!wseg::step_tap_geometry_ok(n_slots, num_beams, vocab)) return 0;

@@ -1659,6 +1659,72 @@ extern "C" int wseg_debug_gemm(int32_t dtype, int32_t epi, int32_t M, int32_t N,
   return launch_gemm(dtype, epi == 0 ? EPI_STORE : (epi == 1 ? EPI_GELU : EPI_RESID), g, (hipStream_t)stream);
 }
 
+// wseg_debug_cross_kv: the cross K / V projection of one decoder layer as the encode pass of wseg_generate launches it (include/wseg.h).
+// Checks only; the product is launch_gemm's.
+static bool cross_kv_tap_split(int dtype) { return dtype == WSEG_BF16X3 || dtype == WSEG_F16X3 || dtype == WSEG_F16M6; }
+static size_t cross_kv_tap_elem_bytes(int dtype) { return (dtype == WSEG_BF16 || dtype == WSEG_F16) ? 2 : 4; }      // plain K / V rows; operand rows per column alike
+
+extern "C" size_t wseg_debug_cross_kv_bytes(int32_t dtype, int32_t num_beams, int32_t n_slots, int32_t n_heads, int32_t t_len, int32_t* format) {
+  using namespace wseg;
+  if (dtype < WSEG_F32 || dtype > WSEG_F16M6 || num_beams < 1 || num_beams > 8 || n_slots < 1 || n_slots > (1 << 16) || n_heads < 1 || n_heads > 64 ||
+      t_len < 1 || t_len > 1500) {
+    set_error("wseg_debug_cross_kv_bytes: unsupported geometry (dtype %d, num_beams %d, n_slots %d, n_heads %d, t_len %d)", dtype, num_beams, n_slots, n_heads, t_len);
+    return 0;
+  }
+  const int fmt = cross_kv_tap_split(dtype) ? x3_cross_kv_format(dtype, num_beams) : 0;
+  if (format) *format = fmt;
+  return cross_kv_layer_bytes(fmt, cross_kv_tap_elem_bytes(dtype), (size_t)n_slots, (size_t)n_heads, (size_t)t_len);
+}
+
+extern "C" int wseg_debug_cross_kv(int32_t dtype, int32_t num_beams, int32_t n_windows, int32_t n_slots, int32_t t_len, int32_t n_heads,
+                                   int32_t plan_m, const void* a, size_t a_bytes, const void* w, const void* bias, const int32_t* slot_map,
+                                   void* k, void* v, size_t kv_bytes, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
+  using namespace wseg;
+#define WSEG_TAP_REQUIRE(COND, ...) do { if (!(COND)) { set_error("wseg_debug_cross_kv: " __VA_ARGS__); return WSEG_ERR_INVALID; } } while (0)
+  WSEG_TAP_REQUIRE(dtype >= WSEG_F32 && dtype <= WSEG_F16M6, "dtype %d unsupported", dtype);
+  WSEG_TAP_REQUIRE(num_beams >= 1 && num_beams <= 8, "num_beams %d unsupported (1..8)", num_beams);
+  WSEG_TAP_REQUIRE(n_heads >= 1 && n_heads <= 64 && n_heads % 2 == 0, "n_heads %d unsupported (even, 2..64: d_model is a multiple of 128)", n_heads);
+  WSEG_TAP_REQUIRE(t_len >= 128 && t_len <= 1500, "t_len %d unsupported (128..1500)", t_len);
+  WSEG_TAP_REQUIRE(n_slots >= 1 && n_slots <= (1 << 16), "n_slots %d unsupported (1..65536)", n_slots);
+  WSEG_TAP_REQUIRE(n_windows >= 1 && n_windows <= n_slots, "n_windows %d does not fit n_slots %d", n_windows, n_slots);
+  const int d = 64 * n_heads, M = n_windows * t_len;
+  WSEG_TAP_REQUIRE(plan_m >= M, "plan_m %d is short of the %d rows launched", plan_m, M);
+  WSEG_TAP_REQUIRE(a, "a is null");
+  WSEG_TAP_REQUIRE(w, "w is null");
+  WSEG_TAP_REQUIRE(k, "k is null");
+  WSEG_TAP_REQUIRE(v, "v is null");
+  WSEG_TAP_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)k | (uintptr_t)v | (uintptr_t)bias | (uintptr_t)splitk_ws) & 15) == 0,
+                   "a, w, bias, k, v and splitk_ws must be 16-byte aligned");
+  const size_t a_need = (size_t)((M + 255) / 256 * 256) * d * cross_kv_tap_elem_bytes(dtype);      // the GEMMs read whole 256-row tiles of A
+  WSEG_TAP_REQUIRE(a_bytes >= a_need, "a_bytes %zu is short of the %zu bytes of %d rows rounded up to 256", a_bytes, a_need, M);
+  const int fmt = cross_kv_tap_split(dtype) ? x3_cross_kv_format(dtype, num_beams) : 0;
+  const size_t kv_need = cross_kv_layer_bytes(fmt, cross_kv_tap_elem_bytes(dtype), (size_t)n_slots, (size_t)n_heads, (size_t)t_len);
+  WSEG_TAP_REQUIRE(kv_bytes >= kv_need, "kv_bytes %zu is short of the %zu bytes of %d slots", kv_bytes, kv_need, n_slots);
+  WSEG_TAP_REQUIRE((splitk_ws != nullptr) == (splitk_ws_bytes != 0), "splitk_ws and splitk_ws_bytes go together");
+  hipStream_t s = (hipStream_t)stream;
+  if (slot_map) {      // what the epilogue indexes with is checked before it runs
+    std::vector<int> h_map(n_windows);
+    WSEG_HIP_CHECK(hipMemcpyAsync(h_map.data(), slot_map, (size_t)n_windows * sizeof(int), hipMemcpyDeviceToHost, s));
+    WSEG_HIP_CHECK(hipStreamSynchronize(s));
+    std::vector<char> taken(n_slots, 0);
+    for (int i = 0; i < n_windows; ++i) {
+      WSEG_TAP_REQUIRE(h_map[i] >= 0 && h_map[i] < n_slots, "slot_map[%d] = %d is no slot of %d", i, h_map[i], n_slots);
+      WSEG_TAP_REQUIRE(!taken[h_map[i]], "slot_map names slot %d twice", h_map[i]);
+      taken[h_map[i]] = 1;
+    }
+  }
+#undef WSEG_TAP_REQUIRE
+  GemmArgs g;      // encode_run (wseg_model.hip): A = the windows' encoder rows, W = the layer's k | v weight, planned for a full encoder chunk
+  g.plan_m = plan_m;
+  g.A = a; g.lda = d; g.W = w; g.ldw = d; g.M = M; g.N = 2 * d; g.K = d;
+  g.ep.bias = bias; g.ep.k = k; g.ep.v = v; g.ep.d_model = d; g.ep.t_len = t_len; g.ep.n_heads = n_heads; g.ep.slot_map = slot_map; g.ep.kv24 = fmt;
+  g.splitk_ws = (float*)splitk_ws; g.splitk_ws_bytes = splitk_ws_bytes;
+  const int status = launch_gemm(dtype, EPI_KV_CROSS, g, s);
+  if (status != WSEG_OK) return status;
+  WSEG_HIP_CHECK(hipStreamSynchronize(s));
+  return WSEG_OK;
+}
+
 extern "C" int wseg_debug_gemm_out_is_mx(int32_t dtype, int32_t M, int32_t N, int32_t K) {
   return wseg::gemm_out_is_mx(dtype, M, N, K, (size_t)1 << 40) ? 1 : 0;      // wseg_debug_gemm with a workspace that never limits the split
 }

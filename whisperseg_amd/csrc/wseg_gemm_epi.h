@@ -40,9 +40,11 @@ template <typename PT, int NC> struct VecN {
 //   FMT 2 (r05): MANT = 15, q as int16, scale 2^s.
 //   FMT 3 (r06): MANT = 23, q as two's-complement 24-bit integers in two planes (q >> 8 as int16, q & 0xff as bytes), scale 2^(s - 8): the
 //   reader rebuilds the 32-bit word [q >> 8 | q & 0xff | 0] = 256 q with one v_perm, converts it with v_cvt_f32_i32 and multiplies the
-//   finished score / the probability by the stored scale.  Error <= 2^-24 of the ROW maximum instead of the 2^-17 of every element that the
-//   24-bit floats stored until mid r06 had: those were the largest term of f16x3's logit error (2e-5 of 2.5e-5) and cost it one of 4 200
-//   sweep recordings.
+//   finished score / the probability by the stored scale.  Error <= half a unit = 2^(ceil(log2 max) - MANT - 1) per element: 2^-24 of the
+//   ROW maximum when that is a power of two, just under 2^-23 of it otherwise; a maximum of exactly 2^k scales to 2^MANT and is clamped to
+//   QMAX, a whole unit (2^-23 of the maximum) off (tests/test_cross_attn_gpu.py asserts these).  The 24-bit floats stored until mid r06
+//   had 2^-17 of EVERY element: those were the largest term of f16x3's logit error (2e-5 of 2.5e-5) and cost it one of 4 200 sweep
+//   recordings.
 // blk: the (slot, head) block.
 template <int FMT, int NC>
 __device__ __forceinline__ void st_bfp_row(unsigned char* blk, int t_len, int t, int e, const float (&v)[NC], bool first_lane) {

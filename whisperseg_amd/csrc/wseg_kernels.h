@@ -129,7 +129,8 @@ int launch_enc_attention(int dtype, const void* q, const void* k, const void* vt
 // quantised is 200 / 200 and the first-step logit error stays at the mixed mode's own 1.5e-4 (plain half: 7.5e-4, 4 of 200 recordings differ;
 // tools/precision_study.py "ckv=bfp16r", profiles/r05_precision_study.json) for two thirds of the bytes of an HBM-bound stream
 // (wseg_dec.hip, x3_cross_kv_format, says why the three-MFMA modes do not take it).
-// 3 = per-row block floating point with 24-bit integer elements (r06, bf16x3 / f16x3): error <= 2^-24 of the row maximum
+// 3 = per-row block floating point with 24-bit integer elements (r06, bf16x3 / f16x3): error <= 2^(ceil(log2 max) - 24) per element, i.e.
+// 2^-24 of the row maximum when that is a power of two and just under 2^-23 of it otherwise; 2^-23 of it at a maximum of exactly 2^k
 // (st_bfp_row, wseg_gemm_epi.h).
 int x3_cross_kv_format(int dtype, int nb);
 // THE definition of the packed formats' bytes (writers st_bfp_row, readers dec_cross_attn_bfp_kernel / dec_cross_attn_k24_kernel, host
